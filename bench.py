@@ -201,6 +201,38 @@ def pmc_gemm_traffic(config, B, ctx_mean):
         "profiles/" + os.path.basename(files[-1])
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tokens, logprobs=None, logits=None):
+    """--dump-outputs: one decode step as a caller receives it — per request its id and the chosen token id — plus what
+    the step computed them from: the chosen tokens' logprobs and the [B, V] logits (a seeded sample of rows if they
+    exceed the size limit)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"request_ids": np.array([t.request_id for t in tokens], dtype=np.float64),
+              "token_ids": np.array([t.token_id for t in tokens], dtype=np.float64)}
+    if logprobs is not None:
+        arrays["logprobs"] = logprobs[:len(tokens)].float().cpu().numpy()
+    if logits is not None:
+        arrays.update(_logits_sample(logits[:len(tokens)].float().cpu().numpy(),
+                                     DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values())))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
+def _logits_sample(lg, room):
+    """{"logits": lg} if it fits in `room` bytes, else a fixed seeded choice of rows and their indices."""
+    import numpy as np
+
+    if lg.nbytes <= room:
+        return {"logits": lg}
+    rows = max(1, room // (lg.shape[1] * 4 + 8))
+    keep = np.sort(np.random.default_rng(0).choice(lg.shape[0], size=rows, replace=False))
+    return {"logits": lg[keep], "logits_rows": keep.astype(np.float64)}
+
+
 def bench_causal_lm_cpu(args):
     """BASELINE config 1: GPT-2 small (124 M, random init, fp32) through CausalLMBatch / CausalLM.generate_token on the
     hf_transformers engine, CPU, batch 4, prompts of 16 tokens.  A step = one NextToken-equivalent generate_token call.
@@ -252,6 +284,8 @@ def bench_causal_lm_cpu(args):
             step_ms.append((time.perf_counter() - ts) * 1e3)
             ids.append([t.token_id for t in toks])
         elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, toks)
     out = {"metric": f"decode tokens/sec (GPT-2 small fp32 CPU causal_lm, batch {B}) + p50 step latency",
            "value": round(B * K / elapsed, 2), "unit": "tokens/s", "n_gpus": 0, "steps": K, "warmup": W,
            "ms_per_step": round(elapsed / K * 1e3, 4),
@@ -400,6 +434,9 @@ def main():
     ap.add_argument("--churn-steps", type=int, default=240)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: what the last timed step returned (token ids, their logprobs, the logits "
+                         "they were chosen from) as DIR/<name>.npy, so that two builds can be compared output for output")
     args = ap.parse_args()
     if args.config in CPU_CONFIGS:
         return bench_causal_lm_cpu(args)
@@ -414,9 +451,11 @@ def main():
         with socket.socket() as so:
             so.bind(("127.0.0.1", 0))
             port = so.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
-                                  f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1", "--master-port",
-                                  str(port), os.path.abspath(__file__), *sys.argv[1:]])
+        import subprocess
+
+        raise SystemExit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
+                                          f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1", "--master-port",
+                                          str(port), os.path.abspath(__file__), *sys.argv[1:]]))
     if args.gpus != world:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     assert torch.cuda.is_available(), "bench.py needs a GPU: the hot path has no CPU fallback"
@@ -493,6 +532,15 @@ def main():
         # as much between boxes (and between runs on one box) as a round of kernel work did.
         blocks = []
         batch = None
+        last_step, last_forward = None, [None]
+        if args.dump_outputs:
+            decode_forward = lm._decode_forward
+
+            def tapped_decode_forward(b):  # keeps what the step's forward returned: (logits, (ids, logprobs, graph))
+                last_forward[0] = decode_forward(b)
+                return last_forward[0]
+
+            lm._decode_forward = tapped_decode_forward
         for blk in range(args.blocks):
             if batch is not None:
                 batch.release()
@@ -505,7 +553,7 @@ def main():
             t0 = time.perf_counter()
             for _ in range(K):
                 ts = time.perf_counter()
-                lm.generate_token(batch)
+                last_step = lm.generate_token(batch)
                 blk_ms.append((time.perf_counter() - ts) * 1e3)
             sync()
             blk_elapsed = time.perf_counter() - t0
@@ -514,6 +562,11 @@ def main():
                 torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
                 blk_elapsed = float(t.item())
             blocks.append((blk_elapsed, blk_ms))
+        if args.dump_outputs:
+            lm._decode_forward = decode_forward
+            if rank == 0:  # the last timed step of the last block; nothing has run on the device since
+                logits, (_ids, logprobs, _g) = last_forward[0]
+                dump_outputs(args.dump_outputs, last_step[0], logprobs, logits)
         order = sorted(range(len(blocks)), key=lambda i: blocks[i][0])
         elapsed, step_ms = blocks[order[len(order) // 2]]
         block_ms_per_step = [round(b[0] / K * 1e3, 4) for b in blocks]

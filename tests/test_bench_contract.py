@@ -70,3 +70,25 @@ def test_gpt2_cpu_bench_leg_runs_and_prints_the_contract_line():
               "vs_baseline", "dtype", "data", "config", "cpu_baseline"):
         assert k in d, k
     assert d["n_gpus"] == 0 and d["dtype"] == "f32" and d["steps"] == 1 and d["value"] > 0
+
+
+def test_gpt2_cpu_bench_leg_dumps_its_last_step(tmp_path):
+    """--dump-outputs DIR: the token ids the last timed step handed back, as float .npy files; the same arguments give the
+    same arrays."""
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "gpt2-cpu", "--steps", "2", "--warmup",
+                            "0", "--no-cpu-baseline", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        dumps.append({f.name: np.load(f) for f in sorted(out.glob("*.npy"))})
+    assert set(dumps[0]) == {"request_ids.npy", "token_ids.npy"}
+    for name, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and a.shape == (4,), name
+        assert np.array_equal(a, dumps[1][name]), name
+    assert dumps[0]["request_ids.npy"].tolist() == [0, 1, 2, 3]

@@ -615,3 +615,35 @@ def test_bench_churn_mode_runs(gpu_device):
     for r in d["runs"]:
         assert r["decode_steps"] == 48 and r["p50_ms"] > 0 and r["membership_events"] >= 4
     assert d["runs"][3]["graph_captures"] >= d["runs"][1]["graph_captures"]
+
+
+def test_bench_dump_outputs_of_the_last_timed_step(gpu_device, tmp_path):
+    """`bench.py --dump-outputs DIR` on the tiny configuration: the last timed step's token ids, logprobs and logits as
+    float .npy files (ids = argmax of the logits, logprobs = their log-softmax), identical between two runs with the same
+    arguments."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "llama-tiny-gptq", "--steps", "3",
+                            "--warmup", "1", "--no-cpu-baseline", "--no-roofline", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads(p.stdout.strip().splitlines()[-1])  # the dump leaves the timing contract as it was
+        assert line["steps"] == 3 and line["timed_blocks"] == 3 and len(line["ms_per_step_blocks"]) == 3
+        dumps.append({f.stem: np.load(f) for f in sorted(out.glob("*.npy"))})
+    d = dumps[0]
+    assert set(d) == {"request_ids", "token_ids", "logprobs", "logits"}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    assert d["logits"].shape == (4, 512) and d["token_ids"].shape == d["logprobs"].shape == (4,)
+    ids = d["token_ids"].astype(np.int64)
+    assert np.array_equal(d["logits"][np.arange(4), ids], d["logits"].max(axis=1)), "ids are the argmax of the logits"
+    lsm = torch.log_softmax(torch.from_numpy(d["logits"]).double(), dim=1).numpy()
+    assert np.allclose(d["logprobs"], lsm[np.arange(4), ids], atol=1e-3)
+    for name, a in d.items():
+        assert np.array_equal(a, dumps[1][name]), name
