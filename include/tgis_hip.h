@@ -210,11 +210,28 @@ int tgis_layernorm_residual_partial(const float* slabs, int num_slabs, int64_t s
                                     void* res_out, int64_t rows, int64_t hidden, float eps, int dtype,
                                     void* stream);
 
+/* Parallel-residual boundary of a GPT-NeoX layer (flash_neox_modeling.py:238-259): res_out = h' = residual + A + B, with
+ * A = a (+ a_bias) and B = b (+ b_bias) summed in fp32 in that order and rounded to the model dtype once;
+ * y1 = LayerNorm(h'; w1, b1) and y2 = LayerNorm(h'; w2, b2) from ONE set of fp32 statistics of the unrounded h'.
+ * a / b / biases may be NULL (absent); y2 == NULL (w2, b2 ignored) is a single LayerNorm (final_layer_norm).
+ * res_out may alias residual; NULL skips the store. */
+int tgis_layernorm2_residual(const void* residual, const void* a, const void* a_bias, const void* b, const void* b_bias,
+                             const void* w1, const void* b1, const void* w2, const void* b2, void* y1, void* y2,
+                             void* res_out, int64_t rows, int64_t hidden, float eps, int dtype, void* stream);
+/* The same with either addend given as split-K partial sums (a_slabs [ceil(rows/32)][a_num_slabs][32][a_slab_ld] fp32 of
+ * tgis_dense_gemm_partial / tgis_gptq_gemm_f16_partial; the two may have different numbers of slabs) or as a tensor: per
+ * addend at most one of (tensor, slabs) is non-NULL.  A slab sum is NOT rounded before it joins h' (h' is rounded once). */
+int tgis_layernorm2_residual_partial(const void* residual, const void* a, const float* a_slabs, int a_num_slabs,
+                                     int64_t a_slab_ld, const void* a_bias, const void* b, const float* b_slabs,
+                                     int b_num_slabs, int64_t b_slab_ld, const void* b_bias, const void* w1, const void* b1,
+                                     const void* w2, const void* b2, void* y1, void* y2, void* res_out, int64_t rows,
+                                     int64_t hidden, float eps, int dtype, void* stream);
+
 /* ---- RoPE + KV-cache write (replaces rotary_emb.apply_rotary + the index_put at
  *      flash_llama_modeling.py:262-268,282; utils/layers.py:466-472) ---------------------------- */
 /* qkv [T, (H + 2*Hkv)*D] (row stride ld_qkv): rotates q heads and k heads in place with the
  * half-split (NeoX) rotation using cos/sin tables [max_pos, rot_dim/2] of the model dtype gathered by
- * positions[T] (int32), then writes k and v of token t into KV page slot slots[t]
+ * positions[T] (int32) — dims [0, rot_dim) of each head, rot_dim even and <= D (partial rotary: gpt-neox-20b 24 of 96), then writes k and v of token t into KV page slot slots[t]
  * (= page_id*32 + offset).  cos == NULL skips the rotation (learned-position models).
  * k_pool / v_pool: this layer's K and V page pools, [num_pages][Hkv][32*D] each.  Inside a (page, kv head) block of
  * 32 tokens x D: K as [token >> 4][D / 8][16 tokens][8], V as [4 column groups][D][8] with token t in column
@@ -245,6 +262,7 @@ int tgis_rope_kv_write_prefill(void* qkv, int64_t ld_qkv, const void* cos, const
  *      utils/flash_attn.py:43-78) ---------------------------------------------------------------- */
 /* Number of key-range splits the launcher will use for this shape (so callers can size workspace). */
 int tgis_attn_num_splits(int64_t B, int Hkv, int H, int64_t max_q_len, int64_t max_ctx);
+/* head_dim D of tgis_attn_paged: 64, 96 or 128. */
 int64_t tgis_attn_workspace_bytes(int64_t total_q_tokens, int H, int Hkv, int D, int num_splits);
 /* Causal softmax(q k^T * scale) v over the paged cache.
  *   q: [total_q, H, D] with token stride ld_q (elements); out: [total_q, H*D] contiguous (ld_out = 0 or

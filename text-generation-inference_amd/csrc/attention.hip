@@ -472,21 +472,24 @@ template <typename T, int D, int MAXS>
 __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restrict__ ws_o,
                                                            const float* __restrict__ ws_ml, T* __restrict__ out,
                                                            int NS, int H, int out_frag, int64_t rows) {
+    // lane covers columns i 64 + lane; a D that is not a multiple of 64 (96) leaves the top lanes of its last slice idle
+    constexpr int DL = (D + 63) / 64;
     const int64_t th = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // tok*H + head
     if (th >= rows) return;
     const int lane = threadIdx.x & 63;
+    auto in_row = [&](int i) { return D % 64 == 0 || i * 64 + lane < D; };
     float mstar = NEG_BIG;
     float l = 0.f;
-    float acc[D / 64] = {};
+    float acc[DL] = {};
     if (MAXS > 0) {
-        float ms[MAXS ? MAXS : 1], ls[MAXS ? MAXS : 1], os[MAXS ? MAXS : 1][D / 64];
+        float ms[MAXS ? MAXS : 1], ls[MAXS ? MAXS : 1], os[MAXS ? MAXS : 1][DL];
 #pragma unroll
         for (int s = 0; s < MAXS; ++s) {
             const int64_t r = th * NS + min(s, NS - 1);
             ms[s] = ws_ml[r * 2];
             ls[s] = ws_ml[r * 2 + 1];
 #pragma unroll
-            for (int i = 0; i < D / 64; ++i) os[s][i] = ws_o[r * D + i * 64 + lane];
+            for (int i = 0; i < DL; ++i) os[s][i] = in_row(i) ? ws_o[r * D + i * 64 + lane] : 0.f;
         }
 #pragma unroll
         for (int s = 0; s < MAXS; ++s)
@@ -497,7 +500,7 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restri
                 const float f = exp2f(ms[s] - mstar);
                 l += ls[s] * f;
 #pragma unroll
-                for (int i = 0; i < D / 64; ++i) acc[i] += os[s][i] * f;
+                for (int i = 0; i < DL; ++i) acc[i] += os[s][i] * f;
             }
     } else {
         for (int s = 0; s < NS; ++s) mstar = fmaxf(mstar, ws_ml[(th * NS + s) * 2]);
@@ -505,12 +508,14 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restri
             float f = exp2f(ws_ml[(th * NS + s) * 2] - mstar);
             l += ws_ml[(th * NS + s) * 2 + 1] * f;
 #pragma unroll
-            for (int i = 0; i < D / 64; ++i) acc[i] += ws_o[(th * NS + s) * D + i * 64 + lane] * f;
+            for (int i = 0; i < DL; ++i)
+                if (in_row(i)) acc[i] += ws_o[(th * NS + s) * D + i * 64 + lane] * f;
         }
     }
     const float inv = l > 0.f ? 1.f / l : 0.f;
 #pragma unroll
-    for (int i = 0; i < D / 64; ++i) {
+    for (int i = 0; i < DL; ++i) {
+        if (!in_row(i)) continue;
         const int64_t o = out_frag ? xf_off(th / H, (th % H) * D + i * 64 + lane, (int64_t)H * D) : th * D + i * 64 + lane;
         out[o] = from_f32<T>(acc[i] * inv);
     }
@@ -788,7 +793,7 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
     TGIS_CHECK_ARG(q && k_pool && v_pool && block_tables && ctx_lens && cu_seqlens_q && out,
                    "tgis_attn_paged: null tensor");
     TGIS_CHECK_ARG(H > 0 && Hkv > 0 && H % Hkv == 0, "tgis_attn_paged: H (%d) must be a multiple of Hkv (%d)", H, Hkv);
-    TGIS_CHECK_ARG(D == 64 || D == 128, "tgis_attn_paged: head_dim %d not supported (64, 128)", D);
+    TGIS_CHECK_ARG(D == 64 || D == 96 || D == 128, "tgis_attn_paged: head_dim %d not supported (64, 96, 128)", D);
     TGIS_CHECK_ARG(dtype == TGIS_F16 || dtype == TGIS_BF16, "tgis_attn_paged: bad dtype");
     TGIS_CHECK_ARG(ld_q % 8 == 0 && ((uintptr_t)q % 16) == 0, "tgis_attn_paged: q must be 16-byte aligned");
     TGIS_CHECK_ARG(max_q_len > 0 && max_pages > 0 && num_splits >= 1, "tgis_attn_paged: bad launch bounds");
@@ -873,9 +878,11 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
     TgisTimedScope timed(TGIS_OP_ATTN, st);
     if (dtype == TGIS_F16) {
         if (D == 128) return launch_attn<f16, 128>(a, grid, total_q, st, nw, ch);
+        if (D == 96) return launch_attn<f16, 96>(a, grid, total_q, st, nw, ch);  // KS = 3, NB = 6 (gpt-neox-20b)
         return launch_attn<f16, 64>(a, grid, total_q, st, nw, ch);
     } else {
         if (D == 128) return launch_attn<bf16, 128>(a, grid, total_q, st, nw, ch);
+        if (D == 96) return launch_attn<bf16, 96>(a, grid, total_q, st, nw, ch);
         return launch_attn<bf16, 64>(a, grid, total_q, st, nw, ch);
     }
 }

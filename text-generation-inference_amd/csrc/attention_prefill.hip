@@ -86,8 +86,11 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs a) {
         lsum[cg] = 0.f;
     }
 
-    // ---- page staging: 2*PAGE_ELEMS/8 16-byte pieces per page, NP per thread ---------------------------------
-    constexpr int NP = (2 * PAGE_ELEMS / 8) / 256;  // 4 (D = 64) or 8 (D = 128)
+    // ---- page staging: PAGE_ELEMS/8 16-byte pieces of K and as many of V per page, KP of each per thread ---------------
+    constexpr int PIECES = PAGE_ELEMS / 8;
+    constexpr int KP = (PIECES + 255) / 256;  // 1 (D = 64), 2 (D = 96: 384 pieces, the last round half empty), 2 (D = 128)
+    constexpr int NP = 2 * KP;
+    auto piece_ok = [&](int i) { return PIECES % 256 == 0 || i * 256 + tid < PIECES; };
     const int32_t* btrow = a.bt + (int64_t)b * a.max_pages;
     V8 stage[NP];
     auto page_load = [&](int p) {
@@ -95,21 +98,23 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs a) {
         const T* kp = reinterpret_cast<const T*>(a.kpool) + ((int64_t)pg * a.Hkv + hk) * PAGE_ELEMS;
         const T* vp = reinterpret_cast<const T*>(a.vpool) + ((int64_t)pg * a.Hkv + hk) * PAGE_ELEMS;
 #pragma unroll
-        for (int i = 0; i < NP / 2; ++i) {
+        for (int i = 0; i < KP; ++i) {
+            if (!piece_ok(i)) continue;
             stage[i] = ld16<V8>(kp + (i * 256 + tid) * 8);
-            stage[NP / 2 + i] = ld16<V8>(vp + (i * 256 + tid) * 8);
+            stage[KP + i] = ld16<V8>(vp + (i * 256 + tid) * 8);
         }
     };
     auto page_store = [&](int buf) {
         T* kl = lds + buf * 2 * PAGE_ELEMS;
         T* vl = kl + PAGE_ELEMS;
 #pragma unroll
-        for (int i = 0; i < NP / 2; ++i) {
+        for (int i = 0; i < KP; ++i) {
+            if (!piece_ok(i)) continue;
             const int piece = i * 256 + tid;
             st16(kl + piece * 8, stage[i]);
             // global V^T piece = (chunk cc, row d) ([4][D][8]); LDS piece = (d/16)*64 + cc*16 + d%16
             const int d = piece % D, cc = piece / D;
-            st16(vl + (((d >> 4) * 64 + cc * 16 + (d & 15)) * 8), stage[NP / 2 + i]);
+            st16(vl + (((d >> 4) * 64 + cc * 16 + (d & 15)) * 8), stage[KP + i]);
         }
     };
 
@@ -233,10 +238,17 @@ int tgis_launch_attn_prefill(const AttnArgs& a, int64_t B, int Hkv, int D, int64
     dim3 grid((unsigned)q_tiles, (unsigned)(Hkv * a.HC), (unsigned)B);
     const size_t lds = (size_t)2 * 2 * 32 * D * 2;  // two buffers of (K page + V page); >= 4 wave slices of D*16 floats
 #define TGIS_PREFILL_LAUNCH(T, DD) hipLaunchKernelGGL((attn_prefill_kernel<T, DD>), grid, dim3(256), lds, st, a)
+    // every head size by name: a size the caller lets through without a kernel here is an error, not the 64 path
     if (dtype == TGIS_F16) {
-        if (D == 128) TGIS_PREFILL_LAUNCH(f16, 128); else TGIS_PREFILL_LAUNCH(f16, 64);
+        if (D == 128) TGIS_PREFILL_LAUNCH(f16, 128);
+        else if (D == 96) TGIS_PREFILL_LAUNCH(f16, 96);
+        else if (D == 64) TGIS_PREFILL_LAUNCH(f16, 64);
+        else TGIS_CHECK_ARG(false, "tgis_attn_paged: no prefill kernel for head_dim %d", D);
     } else {
-        if (D == 128) TGIS_PREFILL_LAUNCH(bf16, 128); else TGIS_PREFILL_LAUNCH(bf16, 64);
+        if (D == 128) TGIS_PREFILL_LAUNCH(bf16, 128);
+        else if (D == 96) TGIS_PREFILL_LAUNCH(bf16, 96);
+        else if (D == 64) TGIS_PREFILL_LAUNCH(bf16, 64);
+        else TGIS_CHECK_ARG(false, "tgis_attn_paged: no prefill kernel for head_dim %d", D);
     }
 #undef TGIS_PREFILL_LAUNCH
     TGIS_CHECK_LAUNCH();

@@ -173,6 +173,151 @@ static int launch_norm(const void* x, const void* residual, const void* weight, 
     return TGIS_OK;
 }
 
+// Parallel-residual layer boundary of GPT-NeoX (flash_neox_modeling.py:238-259): h' = h + A + B (+ biases) and two
+// LayerNorms of h'.  Each addend is a model-dtype tensor, split-K fp32 slabs [S][32][slab_ld] (S may differ between the
+// two), or absent; its bias is added to it in fp32.  h' = ((h + A) + B) in fp32, rounded once for res_out; y1 and y2 take
+// the same fp32 statistics of the unrounded sum, like norm_kernel.  y2 == nullptr: one LayerNorm (final_layer_norm).
+struct Addend {
+    const void* x;        // model-dtype [rows, hidden], or nullptr
+    const float* slabs;   // or split-K partial sums, or nullptr
+    int S;
+    int64_t slab_ld;
+    const void* bias;     // [hidden] or nullptr
+};
+
+template <typename T>
+__device__ __forceinline__ void add_addend(float (&v)[8], const Addend& ad, int64_t row, int hidden, int c) {
+    using V8 = typename VecT<T>::x8;
+    if (ad.slabs) {
+        f32x4 lo, hi;
+        sum_slabs8(ad.slabs + ((row >> 5) * ad.S * 32 + (row & 31)) * ad.slab_ld + c * 8, 32 * ad.slab_ld, ad.S, lo, hi);
+        if (ad.bias) {
+            const V8 bv = ld16<V8>(reinterpret_cast<const T*>(ad.bias) + c * 8);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                lo[e] += to_f32(bv[e]);
+                hi[e] += to_f32(bv[e + 4]);
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            v[e] += lo[e];
+            v[e + 4] += hi[e];
+        }
+    } else if (ad.x) {
+        const V8 a = ld16<V8>(reinterpret_cast<const T*>(ad.x) + row * hidden + c * 8);
+        if (ad.bias) {
+            const V8 bv = ld16<V8>(reinterpret_cast<const T*>(ad.bias) + c * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] += to_f32(a[e]) + to_f32(bv[e]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] += to_f32(a[e]);
+        }
+    } else if (ad.bias) {
+        const V8 bv = ld16<V8>(reinterpret_cast<const T*>(ad.bias) + c * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += to_f32(bv[e]);
+    }
+}
+
+template <typename T, int NT>
+__global__ __launch_bounds__(NT) void layernorm2_kernel(const T* h, Addend A, Addend B, const T* __restrict__ w1,
+                                                        const T* __restrict__ b1, const T* __restrict__ w2,
+                                                        const T* __restrict__ b2, T* y1, T* y2, T* res_out, int hidden,
+                                                        float eps) {
+    using V8 = typename VecT<T>::x8;
+    constexpr int MAXV = MAX_HIDDEN / (NT * 8);
+    __shared__ float sh[NT / 64];
+    const int64_t row = blockIdx.x;
+    float v[MAXV][8];
+    const int nchunk = hidden >> 3;
+    float s1 = 0.f;
+#pragma unroll
+    for (int it = 0; it < MAXV; ++it) {
+        const int c = threadIdx.x + it * NT;
+        if (c < nchunk) {
+            const V8 hv = ld16<V8>(h + row * hidden + c * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[it][e] = to_f32(hv[e]);
+            add_addend<T>(v[it], A, row, hidden, c);
+            add_addend<T>(v[it], B, row, hidden, c);
+            V8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                o[e] = from_f32<T>(v[it][e]);
+                s1 += v[it][e];
+            }
+            if (res_out) st16(res_out + row * hidden + c * 8, o);
+        }
+    }
+    const float mean = block_sum<NT>(s1, sh) / hidden;
+    float d2 = 0.f;
+#pragma unroll
+    for (int it = 0; it < MAXV; ++it) {
+        const int c = threadIdx.x + it * NT;
+        if (c < nchunk) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float d = v[it][e] - mean;
+                d2 += d * d;
+            }
+        }
+    }
+    const float rstd = rsqrtf(block_sum<NT>(d2, sh) / hidden + eps);
+#pragma unroll
+    for (int it = 0; it < MAXV; ++it) {
+        const int c = threadIdx.x + it * NT;
+        if (c < nchunk) {
+            float n[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) n[e] = (v[it][e] - mean) * rstd;
+            const V8 wa = ld16<V8>(w1 + c * 8), ba = ld16<V8>(b1 + c * 8);
+            V8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = from_f32<T>(n[e] * to_f32(wa[e]) + to_f32(ba[e]));
+            st16(y1 + row * hidden + c * 8, o);
+            if (y2) {
+                const V8 wb = ld16<V8>(w2 + c * 8), bb = ld16<V8>(b2 + c * 8);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[e] = from_f32<T>(n[e] * to_f32(wb[e]) + to_f32(bb[e]));
+                st16(y2 + row * hidden + c * 8, o);
+            }
+        }
+    }
+}
+
+static int launch_layernorm2(const void* h, const Addend& A, const Addend& B, const void* w1, const void* b1,
+                             const void* w2, const void* b2, void* y1, void* y2, void* res_out, int64_t rows,
+                             int64_t hidden, float eps, int dtype, void* stream) {
+    TGIS_CHECK_ARG(h && w1 && b1 && y1, "tgis_layernorm2_residual: null tensor");
+    TGIS_CHECK_ARG(!y2 || (w2 && b2), "tgis_layernorm2_residual: y2 needs w2 and b2");
+    TGIS_CHECK_ARG(!(A.x && A.slabs) && !(B.x && B.slabs), "tgis_layernorm2_residual: an addend is a tensor OR slabs");
+    TGIS_CHECK_ARG((!A.slabs || (A.S >= 1 && A.slab_ld >= hidden && A.slab_ld % 4 == 0)) &&
+                       (!B.slabs || (B.S >= 1 && B.slab_ld >= hidden && B.slab_ld % 4 == 0)),
+                   "tgis_layernorm2_residual: slab input needs S >= 1 and a row stride >= hidden (multiple of 4)");
+    TGIS_CHECK_ARG(hidden > 0 && hidden % 8 == 0 && hidden <= MAX_HIDDEN,
+                   "tgis_layernorm2_residual: hidden (%ld) must be a multiple of 8 and <= %d", (long)hidden, MAX_HIDDEN);
+    TGIS_CHECK_ARG(rows >= 0 && rows <= 2147483647LL, "tgis_layernorm2_residual: bad rows");
+    TGIS_CHECK_ARG(dtype == TGIS_F16 || dtype == TGIS_BF16, "tgis_layernorm2_residual: bad dtype");
+    if (rows == 0) return TGIS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    TgisTimedScope timed(TGIS_OP_NORM, st);
+    const bool wide = rows <= 64 && hidden >= 2048;
+#define TGIS_LN2_LAUNCH(T, NT)                                                                                       \
+    hipLaunchKernelGGL((layernorm2_kernel<T, NT>), dim3((unsigned)rows), dim3(NT), 0, st, (const T*)h, A, B,         \
+                       (const T*)w1, (const T*)b1, (const T*)w2, (const T*)b2, (T*)y1, (T*)y2, (T*)res_out,          \
+                       (int)hidden, eps)
+    if (dtype == TGIS_F16) {
+        if (wide) TGIS_LN2_LAUNCH(f16, 512); else TGIS_LN2_LAUNCH(f16, 256);
+    } else {
+        if (wide) TGIS_LN2_LAUNCH(bf16, 512); else TGIS_LN2_LAUNCH(bf16, 256);
+    }
+#undef TGIS_LN2_LAUNCH
+    TGIS_CHECK_LAUNCH();
+    return TGIS_OK;
+}
+
 }  // namespace
 
 extern "C" int tgis_rmsnorm_residual(const void* x, const void* residual, const void* weight, void* y, int64_t ldy,
@@ -203,4 +348,22 @@ extern "C" int tgis_layernorm_residual(const void* x, const void* residual, cons
                                        const void* bias, void* y, void* res_out, int64_t rows, int64_t hidden,
                                        float eps, int dtype, void* stream) {
     return launch_norm<false>(x, residual, weight, bias, y, res_out, rows, hidden, eps, dtype, stream);
+}
+
+extern "C" int tgis_layernorm2_residual(const void* residual, const void* a, const void* a_bias, const void* b,
+                                        const void* b_bias, const void* w1, const void* b1, const void* w2, const void* b2,
+                                        void* y1, void* y2, void* res_out, int64_t rows, int64_t hidden, float eps,
+                                        int dtype, void* stream) {
+    const Addend A{a, nullptr, 0, 0, a_bias}, B{b, nullptr, 0, 0, b_bias};
+    return launch_layernorm2(residual, A, B, w1, b1, w2, b2, y1, y2, res_out, rows, hidden, eps, dtype, stream);
+}
+
+extern "C" int tgis_layernorm2_residual_partial(const void* residual, const void* a, const float* a_slabs, int a_num_slabs,
+                                                int64_t a_slab_ld, const void* a_bias, const void* b, const float* b_slabs,
+                                                int b_num_slabs, int64_t b_slab_ld, const void* b_bias, const void* w1,
+                                                const void* b1, const void* w2, const void* b2, void* y1, void* y2,
+                                                void* res_out, int64_t rows, int64_t hidden, float eps, int dtype,
+                                                void* stream) {
+    const Addend A{a, a_slabs, a_num_slabs, a_slab_ld, a_bias}, B{b, b_slabs, b_num_slabs, b_slab_ld, b_bias};
+    return launch_layernorm2(residual, A, B, w1, b1, w2, b2, y1, y2, res_out, rows, hidden, eps, dtype, stream);
 }

@@ -13,7 +13,22 @@
 
 namespace {
 
+// x[d] of row t, one element: the model-dtype tensor, or the slab sum (+ bias) rounded to the model dtype like load_chunk
 template <typename T>
+__device__ __forceinline__ float load_elem(const T* hp, int64_t t, int col, const PartialIn<T>& pin) {
+    if (pin.slabs == nullptr) return to_f32(*hp);
+    const float* sp = pin.slabs + ((t >> 5) * pin.S * 32 + (t & 31)) * pin.slab_ld + col;
+    float acc = 0.f;
+    for (int s = 0; s < pin.S; ++s) acc += sp[(int64_t)s * 32 * pin.slab_ld];
+    if (pin.bias) acc += to_f32(pin.bias[col]);
+    return to_f32(from_f32<T>(acc));
+}
+
+// GEN: a rotary span that is not a whole number of 16-byte chunk pairs (rot % 16 != 0: gpt-neox-20b rotates 24 of its 96
+// dims, so a half-span is 12 elements).  The work items of the first rc8 = ceil(rot / 8) chunks of a head then share the
+// span's rot / 2 pairs, rotated element by element (same fp32 expressions as the chunk path), and the copies of the dims in
+// [rot, 8 rc8); the chunks behind take the chunk path.  GEN = false is the rot % 16 == 0 kernel.
+template <typename T, bool GEN>
 __global__ __launch_bounds__(256) void rope_kv_kernel(T* qkv, int64_t ld, const T* __restrict__ cosb,
                                                       const T* __restrict__ sinb,
                                                       const int32_t* __restrict__ positions,
@@ -26,6 +41,7 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(T* qkv, int64_t ld, const 
     const int c8 = D >> 3;
     const int items = (H + 2 * Hkv) * c8;
     const int rh8 = rot >> 4;  // 8-element chunks in half the rotary span
+    const int rc8 = (rot + 7) >> 3;  // GEN: 8-element chunks that hold the rotary span
     const int slot = slots ? slots[t] : 0;
     const int page = slot >> 5, tok = slot & 31;
     const T* cr = cosb ? cosb + (int64_t)positions[t] * (rot >> 1) : nullptr;
@@ -36,9 +52,44 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(T* qkv, int64_t ld, const 
         const bool is_v = head >= H + Hkv;
         const bool is_k = head >= H && !is_v;
         const bool roped = cr != nullptr && !is_v;
-        if (roped && j >= rh8 && j < 2 * rh8) continue;  // second half: handled with its partner
+        if (GEN && roped && j < rc8) {
+            // the rc8 items of the span share its pairs: item j takes pairs j, j + rc8, j + 2 rc8, ... in batches of 4 whose
+            // loads are all in flight together, and the copies rot + j, rot + j + rc8, ... (every pair and dim has one owner)
+            T* kb = is_k && kpool ? kpool + ((int64_t)page * Hkv + (head - H)) * 32 * D : nullptr;
+            const int half = rot >> 1;
+            for (int i0 = j; i0 < half; i0 += 4 * rc8) {
+                float x1[4], x2[4], cf[4], sf[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int i = min(i0 + u * rc8, half - 1);  // (clamped: a duplicate of a valid pair, not stored)
+                    x1[u] = load_elem<T>(hp + i, t, head * D + i, pin);
+                    x2[u] = load_elem<T>(hp + i + half, t, head * D + i + half, pin);
+                    cf[u] = to_f32(cr[i]);
+                    sf[u] = to_f32(sr[i]);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int i = i0 + u * rc8;
+                    if (i >= half) break;
+                    const T o1 = from_f32<T>(x1[u] * cf[u] - x2[u] * sf[u]), o2 = from_f32<T>(x1[u] * sf[u] + x2[u] * cf[u]);
+                    hp[i] = o1;
+                    hp[i + half] = o2;
+                    if (kb) {
+                        kb[k_off(tok, i, D)] = o1;
+                        kb[k_off(tok, i + half, D)] = o2;
+                    }
+                }
+            }
+            for (int d = rot + j; d < rc8 * 8; d += rc8) {
+                const T x = from_f32<T>(load_elem<T>(hp + d, t, head * D + d, pin));
+                if (pin.slabs) hp[d] = x;
+                if (kb) kb[k_off(tok, d, D)] = x;
+            }
+            continue;
+        }
+        if (!GEN && roped && j >= rh8 && j < 2 * rh8) continue;  // second half: handled with its partner
         V8 a = load_chunk<T>(hp + j * 8, t, head * D + j * 8, pin);
-        if (roped && j < rh8) {
+        if (!GEN && roped && j < rh8) {
             V8 b = load_chunk<T>(hp + (j + rh8) * 8, t, head * D + (j + rh8) * 8, pin);
             V8 c = ld16<V8>(cr + j * 8), s = ld16<V8>(sr + j * 8);
             V8 o1, o2;
@@ -79,7 +130,7 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(T* qkv, int64_t ld, const 
 // (k) and 2-byte (v) stores scattered over the page: fine for the 32 tokens of a decode step, ~4x slower than this on a
 // 32k-token prefill.  Precondition: token i of sequence b sits at cache position i (a fresh prefill; its rotary
 // position comes from `positions` like everywhere else).  Slots of the last page past the sequence end get zeros.
-template <typename T>
+template <typename T, bool GEN>
 __global__ __launch_bounds__(256) void rope_kv_prefill_kernel(const T* __restrict__ qkv, int64_t ld,
                                                               const T* __restrict__ cosb, const T* __restrict__ sinb,
                                                               const int32_t* __restrict__ positions,
@@ -105,11 +156,30 @@ __global__ __launch_bounds__(256) void rope_kv_prefill_kernel(const T* __restric
     for (int e = 0; e < 8; ++e) zero[e] = (T)0.f;
 
     // ---- K: item = (token, 8-element chunk j); the rotary partner chunk j + rot/16 is handled with it ----------
+    const int rc8 = (rot + 7) >> 3;  // GEN: chunks that hold the rotary span, shared by their items (see rope_kv_kernel)
     for (int it = tid; it < 32 * c8; it += 256) {
         const int tok = it & 31, j = it >> 5;
         const bool roped = cosb != nullptr;
-        if (roped && j >= rh8 && j < 2 * rh8) continue;
-        const bool pair = roped && j < rh8;
+        if (GEN && roped && j < rc8) {  // item j of the span takes pairs j, j + rc8, ... (see rope_kv_kernel)
+            const int half = rot >> 1;
+            const T* kp = tok < ntok ? qkv + (int64_t)(t0 + i0 + tok) * ld + (int64_t)(H + hk) * D : nullptr;
+            const int pos = tok < ntok ? positions[t0 + i0 + tok] : 0;
+            for (int i = j; i < half; i += rc8) {
+                T o1 = (T)0.f, o2 = (T)0.f;
+                if (kp) {
+                    const float x1 = to_f32(kp[i]), x2 = to_f32(kp[i + half]);
+                    const float cf = to_f32(cosb[(int64_t)pos * half + i]), sf = to_f32(sinb[(int64_t)pos * half + i]);
+                    o1 = from_f32<T>(x1 * cf - x2 * sf);
+                    o2 = from_f32<T>(x1 * sf + x2 * cf);
+                }
+                kb[k_off(tok, i, D)] = o1;
+                kb[k_off(tok, i + half, D)] = o2;
+            }
+            for (int d = rot + j; d < rc8 * 8; d += rc8) kb[k_off(tok, d, D)] = kp ? kp[d] : (T)0.f;
+            continue;
+        }
+        if (!GEN && roped && j >= rh8 && j < 2 * rh8) continue;
+        const bool pair = !GEN && roped && j < rh8;
         V8 o1 = zero, o2 = zero;
         if (tok < ntok) {
             const int64_t t = t0 + i0 + tok;
@@ -162,8 +232,8 @@ static int rope_launch(void* qkv, int64_t ld_qkv, const void* cos, const void* s
     TGIS_CHECK_ARG(H > 0 && Hkv >= 0 && D > 0 && D % 16 == 0, "tgis_rope_kv_write: head_dim must be a multiple of 16");
     TGIS_CHECK_ARG(ld_qkv % 8 == 0 && ld_qkv >= (int64_t)(H + 2 * Hkv) * D, "tgis_rope_kv_write: bad row stride");
     TGIS_CHECK_ARG((cos == nullptr) == (sin == nullptr), "tgis_rope_kv_write: cos and sin go together");
-    TGIS_CHECK_ARG(!cos || (positions && rot_dim > 0 && rot_dim <= D && rot_dim % 16 == 0),
-                   "tgis_rope_kv_write: rot_dim must be a multiple of 16 and <= head_dim");
+    TGIS_CHECK_ARG(!cos || (positions && rot_dim > 0 && rot_dim <= D && rot_dim % 2 == 0),
+                   "tgis_rope_kv_write: rot_dim must be even and <= head_dim");
     TGIS_CHECK_ARG((!k_pool && !v_pool) || slots, "tgis_rope_kv_write: cache write needs slots");
     TGIS_CHECK_ARG(dtype == TGIS_F16 || dtype == TGIS_BF16, "tgis_rope_kv_write: bad dtype");
     TGIS_CHECK_ARG(!slabs || (S >= 1 && slab_ld >= (int64_t)(H + 2 * Hkv) * D && slab_ld % 4 == 0),
@@ -175,17 +245,19 @@ static int rope_launch(void* qkv, int64_t ld_qkv, const void* cos, const void* s
     const int items = (H + 2 * Hkv) * (D >> 3);
     const unsigned gy = T <= 64 ? (unsigned)std::min(16, (items + 255) / 256) : 1u;
     const dim3 grid((unsigned)T, gy);
+    const bool gen = cos && rot_dim % 16 != 0;  // partial span off the 16-element grid (rope_kv_kernel GEN)
+#define TGIS_ROPE_LAUNCH(T, G)                                                                                         \
+    do {                                                                                                               \
+        PartialIn<T> pin{slabs, S, slab_ld, (const T*)bias};                                                           \
+        hipLaunchKernelGGL((rope_kv_kernel<T, G>), grid, dim3(256), 0, st, (T*)qkv, ld_qkv, (const T*)cos,             \
+                           (const T*)sin, positions, slots, (T*)k_pool, (T*)v_pool, H, Hkv, D, rot_dim, pin);          \
+    } while (0)
     if (dtype == TGIS_F16) {
-        PartialIn<f16> pin{slabs, S, slab_ld, (const f16*)bias};
-        hipLaunchKernelGGL(rope_kv_kernel<f16>, grid, dim3(256), 0, st, (f16*)qkv, ld_qkv,
-                           (const f16*)cos, (const f16*)sin, positions, slots, (f16*)k_pool, (f16*)v_pool, H, Hkv,
-                           D, rot_dim, pin);
+        if (gen) TGIS_ROPE_LAUNCH(f16, true); else TGIS_ROPE_LAUNCH(f16, false);
     } else {
-        PartialIn<bf16> pin{slabs, S, slab_ld, (const bf16*)bias};
-        hipLaunchKernelGGL(rope_kv_kernel<bf16>, grid, dim3(256), 0, st, (bf16*)qkv, ld_qkv,
-                           (const bf16*)cos, (const bf16*)sin, positions, slots, (bf16*)k_pool, (bf16*)v_pool, H,
-                           Hkv, D, rot_dim, pin);
+        if (gen) TGIS_ROPE_LAUNCH(bf16, true); else TGIS_ROPE_LAUNCH(bf16, false);
     }
+#undef TGIS_ROPE_LAUNCH
     TGIS_CHECK_LAUNCH();
     return TGIS_OK;
 }
@@ -215,8 +287,8 @@ extern "C" int tgis_rope_kv_write_prefill(void* qkv, int64_t ld_qkv, const void*
     TGIS_CHECK_ARG(B >= 0 && T >= 0 && max_len >= 0 && max_pages > 0, "tgis_rope_kv_write_prefill: bad sizes");
     TGIS_CHECK_ARG(H > 0 && Hkv > 0 && D > 0 && D % 16 == 0, "tgis_rope_kv_write_prefill: head_dim must be a multiple of 16");
     TGIS_CHECK_ARG((cos == nullptr) == (sin == nullptr), "tgis_rope_kv_write_prefill: cos and sin go together");
-    TGIS_CHECK_ARG(!cos || (positions && rot_dim > 0 && rot_dim <= D && rot_dim % 16 == 0),
-                   "tgis_rope_kv_write_prefill: rot_dim must be a multiple of 16 and <= head_dim");
+    TGIS_CHECK_ARG(!cos || (positions && rot_dim > 0 && rot_dim <= D && rot_dim % 2 == 0),
+                   "tgis_rope_kv_write_prefill: rot_dim must be even and <= head_dim");
     TGIS_CHECK_ARG(dtype == TGIS_F16 || dtype == TGIS_BF16, "tgis_rope_kv_write_prefill: bad dtype");
     if (B == 0 || T == 0) return TGIS_OK;
     // q heads: rotated in place by the per-token kernel (no cache traffic: Hkv = 0, no pools)
@@ -229,14 +301,17 @@ extern "C" int tgis_rope_kv_write_prefill(void* qkv, int64_t ld_qkv, const void*
     TgisTimedScope timed(TGIS_OP_ROPE_KV, st);
     const dim3 grid((unsigned)(B * pps), (unsigned)Hkv);
     const size_t lds = (size_t)32 * (D + 8) * 2;
-    if (dtype == TGIS_F16)
-        hipLaunchKernelGGL(rope_kv_prefill_kernel<f16>, grid, dim3(256), lds, st, (const f16*)qkv, ld_qkv, (const f16*)cos,
-                           (const f16*)sin, positions, cu_seqlens, block_tables, max_pages, (f16*)k_pool, (f16*)v_pool, H,
-                           Hkv, D, rot_dim, pps);
-    else
-        hipLaunchKernelGGL(rope_kv_prefill_kernel<bf16>, grid, dim3(256), lds, st, (const bf16*)qkv, ld_qkv,
-                           (const bf16*)cos, (const bf16*)sin, positions, cu_seqlens, block_tables, max_pages,
-                           (bf16*)k_pool, (bf16*)v_pool, H, Hkv, D, rot_dim, pps);
+    const bool gen = cos && rot_dim % 16 != 0;
+#define TGIS_ROPE_PREFILL_LAUNCH(T, G)                                                                                  \
+    hipLaunchKernelGGL((rope_kv_prefill_kernel<T, G>), grid, dim3(256), lds, st, (const T*)qkv, ld_qkv, (const T*)cos,  \
+                       (const T*)sin, positions, cu_seqlens, block_tables, max_pages, (T*)k_pool, (T*)v_pool, H, Hkv, D, \
+                       rot_dim, pps)
+    if (dtype == TGIS_F16) {
+        if (gen) TGIS_ROPE_PREFILL_LAUNCH(f16, true); else TGIS_ROPE_PREFILL_LAUNCH(f16, false);
+    } else {
+        if (gen) TGIS_ROPE_PREFILL_LAUNCH(bf16, true); else TGIS_ROPE_PREFILL_LAUNCH(bf16, false);
+    }
+#undef TGIS_ROPE_PREFILL_LAUNCH
     TGIS_CHECK_LAUNCH();
     return TGIS_OK;
 }

@@ -121,3 +121,32 @@ def bigcode_tensors(config, seed: int, device="cpu", dtype=torch.bfloat16) -> Di
         lin(f"{p}.mlp.c_proj", E, I)
     ln("transformer.ln_f")
     return t
+
+
+def neox_tensors(config, seed: int, device="cpu", dtype=torch.float16) -> Dict[str, torch.Tensor]:
+    """Seeded full GPT-NeoX checkpoint in HF naming (gpt_neox.*, embed_out): N(0, 1/sqrt(fan_in)) weights, small biases,
+    unit LayerNorms; query_key_value rows in the checkpoint's head-interleaved [H, 3, D] order."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    E, I, V = config.hidden_size, config.intermediate_size, config.vocab_size
+    t: Dict[str, torch.Tensor] = {}
+
+    def lin(name, n, k):
+        t[f"{name}.weight"] = (torch.randn(n, k, generator=g, device=device) * k ** -0.5).to(dtype)
+        t[f"{name}.bias"] = (torch.randn(n, generator=g, device=device) * 0.02).to(dtype)
+
+    def ln(name):
+        t[f"{name}.weight"] = torch.ones(E, device=device, dtype=dtype)
+        t[f"{name}.bias"] = torch.zeros(E, device=device, dtype=dtype)
+
+    t["gpt_neox.embed_in.weight"] = (torch.randn(V, E, generator=g, device=device) * 0.02).to(dtype)
+    for i in range(config.num_hidden_layers):
+        p = f"gpt_neox.layers.{i}"
+        ln(f"{p}.input_layernorm")
+        ln(f"{p}.post_attention_layernorm")
+        lin(f"{p}.attention.query_key_value", 3 * E, E)
+        lin(f"{p}.attention.dense", E, E)
+        lin(f"{p}.mlp.dense_h_to_4h", I, E)
+        lin(f"{p}.mlp.dense_4h_to_h", E, I)
+    ln("gpt_neox.final_layer_norm")
+    t["embed_out.weight"] = (torch.randn(V, E, generator=g, device=device) * E ** -0.5).to(dtype)
+    return t

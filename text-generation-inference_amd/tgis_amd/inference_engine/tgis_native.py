@@ -1,6 +1,6 @@
 """The native engine: model type -> MI355X model class, process group, safetensors `Weights`, GPTQ params
 (mirrors inference_engine/tgis_native.py:23-139 of the reference; model families of the configs in
-BASELINE.json: llama, and gpt_bigcode when flash_santacoder_modeling is present)."""
+BASELINE.json: llama, and gpt_bigcode when flash_santacoder_modeling is present; gpt_neox)."""
 import os
 from typing import Any, Optional
 
@@ -12,7 +12,7 @@ from tgis_amd.utils.dist import initialize_torch_distributed
 from tgis_amd.utils.hub import local_weight_files
 from tgis_amd.utils.weights import Weights
 
-FLASH_TYPES = ["llama", "gpt_bigcode"]
+FLASH_TYPES = ["llama", "gpt_bigcode", "gpt_neox"]
 
 
 def _barrier(group):
@@ -38,6 +38,11 @@ def model_class_for(config):
             raise NotImplementedError("gpt_bigcode (Santacoder/Starcoder) is not built yet in this round") from e
         config.transpose = config.architectures[0].startswith("GPT2")
         return FlashSantacoderForCausalLM, {"transformer.wte.weight": ["lm_head.weight"]}
+    if model_type == "gpt_neox":
+        from tgis_amd.models.custom_modeling.flash_neox_modeling import FlashGPTNeoXForCausalLM
+
+        # checkpoints saved by transformers 5.x name the output head lm_head
+        return FlashGPTNeoXForCausalLM, {"embed_out.weight": ["lm_head.weight"]}
     raise NotImplementedError(f"Flash attention currently only supported by the following model types: {FLASH_TYPES}")
 
 

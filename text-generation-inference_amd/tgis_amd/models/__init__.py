@@ -17,14 +17,31 @@ from tgis_amd.models.model import Model
 # grads are never needed in a serving shard (reference models/__init__.py:28)
 torch.set_grad_enabled(False)
 
-FLASH_MODEL_TYPES = ("llama", "gpt_bigcode")
+FLASH_MODEL_TYPES = ("llama", "gpt_bigcode", "gpt_neox")
 
 
-def _flash_requested(model_type: str) -> bool:
+def _flash_supports(model_type: str, config: Optional[dict]) -> bool:
+    """Whether the flash port serves this checkpoint.  gpt_neox: only head sizes 64 / 96 / 128 and the gelu family (the
+    rest — Pythia-2.8B, Pythia-1B, ... — stays on the padded path, which served every gpt_neox before the flash port)."""
+    if model_type not in FLASH_MODEL_TYPES:
+        return False
+    if model_type == "gpt_neox" and config is not None:
+        from types import SimpleNamespace
+
+        from tgis_amd.models.custom_modeling.flash_neox_modeling import check_neox_config
+
+        try:
+            check_neox_config(SimpleNamespace(**config), quantize="none")
+        except (NotImplementedError, AttributeError, TypeError, ZeroDivisionError):
+            return False
+    return True
+
+
+def _flash_requested(model_type: str, config: Optional[dict] = None) -> bool:
     env = os.getenv("FLASH_ATTENTION")
     if env is not None:
         return env.lower() == "true"
-    return torch.cuda.is_available() and model_type in FLASH_MODEL_TYPES
+    return torch.cuda.is_available() and _flash_supports(model_type, config)
 
 
 def get_model(model_name: str, revision: Optional[str], deployment_framework: str, dtype_str: Optional[str],
@@ -34,7 +51,8 @@ def get_model(model_name: str, revision: Optional[str], deployment_framework: st
 
     model_path = get_model_path(model_name, revision)
     with open(os.path.join(model_path, "config.json")) as f:
-        model_type = json.load(f).get("model_type")
+        config_dict = json.load(f)
+    model_type = config_dict.get("model_type")
     on_gpu = torch.cuda.is_available()
     # fp16 on GPU, fp32 on CPU unless told otherwise (server.py:287-288)
     dtype = get_torch_dtype(dtype_str) if dtype_str else (torch.float16 if on_gpu else torch.float32)
@@ -43,7 +61,7 @@ def get_model(model_name: str, revision: Optional[str], deployment_framework: st
     if quantize is not None and quantize != "gptq":
         raise ValueError(f"{quantize} quantization is not supported")
 
-    if _flash_requested(model_type):
+    if _flash_requested(model_type, config_dict):
         if not on_gpu:
             raise NotImplementedError("FLASH_ATTENTION is set but no GPU is visible: the flash path has no CPU fallback")
         if model_type not in FLASH_MODEL_TYPES:

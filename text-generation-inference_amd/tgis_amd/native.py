@@ -68,6 +68,10 @@ SIGNATURES = {
     "tgis_layernorm_residual": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_f, _c_int, _vp]),
     "tgis_layernorm_residual_partial": (_c_int, [_vp, _c_int, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64,
                                                  _c_f, _c_int, _vp]),
+    "tgis_layernorm2_residual": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64,
+                                          _c_f, _c_int, _vp]),
+    "tgis_layernorm2_residual_partial": (_c_int, [_vp, _vp, _vp, _c_int, _c_i64, _vp, _vp, _vp, _c_int, _c_i64, _vp, _vp,
+                                                  _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_f, _c_int, _vp]),
     "tgis_rope_kv_write": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_int, _c_int, _c_int,
                                     _c_int, _c_int, _vp]),
     "tgis_rope_kv_write_partial": (_c_int, [_vp, _c_int, _c_i64, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64,
@@ -583,6 +587,34 @@ def layernorm_residual(x, residual, weight, bias, eps: float, y=None, res_out=No
                                                float(eps), dtype_code(x.dtype), _stream()),
         "tgis_layernorm_residual")
     return y, res_out
+
+
+def layernorm2_residual(residual, a, b, w1, b1, eps: float, w2=None, b2=None, res_out=None, a_bias=None, b_bias=None):
+    """GPT-NeoX parallel-residual boundary: h' = residual + a (+ a_bias) + b (+ b_bias) in fp32, rounded once, then
+    y1 = LN(h'; w1, b1) and (w2 given) y2 = LN(h'; w2, b2).  `a` / `b` are tensors, `Partial`s or None.
+    Returns (y1, y2 or None, h')."""
+    assert residual.dim() == 2 and residual.is_contiguous()
+    rows, hidden = residual.shape
+    y1 = torch.empty_like(residual)
+    y2 = torch.empty_like(residual) if w2 is not None else None
+    if res_out is None:
+        res_out = torch.empty_like(residual)
+
+    def parts(x, bias):
+        if isinstance(x, Partial):
+            assert x.shape == (rows, hidden) and (bias is None or x.bias is None)
+            return None, x.slabs, x.S, x.ld, x.bias if bias is None else bias
+        if x is not None:
+            assert x.shape == (rows, hidden) and x.is_contiguous() and x.dtype == residual.dtype
+        return x, None, 0, 0, bias
+
+    pa, pb = parts(a, a_bias), parts(b, b_bias)
+    _check(
+        load_library().tgis_layernorm2_residual_partial(
+            _ptr(residual), _ptr(pa[0]), _ptr(pa[1]), pa[2], pa[3], _ptr(pa[4]), _ptr(pb[0]), _ptr(pb[1]), pb[2], pb[3],
+            _ptr(pb[4]), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(y1), _ptr(y2), _ptr(res_out), rows, hidden,
+            float(eps), dtype_code(residual.dtype), _stream()), "tgis_layernorm2_residual_partial")
+    return y1, y2, res_out
 
 
 # ---- rope + kv write, attention --------------------------------------------------------------------------
