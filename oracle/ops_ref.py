@@ -199,3 +199,18 @@ def kv_page_unpack(k_pool: torch.Tensor, v_pool: torch.Tensor, page: int, Hkv: i
     col = (i >> 2) * 8 + (tok >> 4) * 4 + (i & 3)
     V = vb[:, :, col].permute(2, 0, 1)
     return K, V
+
+
+def kv_page_pack(k_pool: torch.Tensor, v_pool: torch.Tensor, page: int, K: torch.Tensor, V: torch.Tensor):
+    """Write K, V [n <= 32, Hkv, D] as tokens 0..n-1 of one page of the pools [num_pages, Hkv, 32*D], in place; the
+    page's other slots keep what they hold.  The exact inverse of kv_page_unpack: lets tests build a pool on the host
+    (and poison single slots) without the product's cache writer."""
+    n, Hkv, D = K.shape
+    assert n <= 32 and V.shape == K.shape and k_pool.shape[1:] == (Hkv, 32 * D) and v_pool.shape == k_pool.shape
+    tok = torch.arange(n)
+    i = tok & 15
+    kb = k_pool[page].view(Hkv, 2, D // 8, 16, 8)  # [h][tile][chunk][tok][8]
+    kb[:, tok >> 4, :, i, :] = K.to(k_pool.dtype).reshape(n, Hkv, D // 8, 8)  # (advanced dims first: [tok][h][chunk][8])
+    col = (i >> 2) * 8 + (tok >> 4) * 4 + (i & 3)
+    vb = v_pool[page].view(Hkv, 4, D, 8)  # [h][column group][d][8]
+    vb[:, col >> 3, :, col & 7] = V.to(v_pool.dtype)  # ([tok][h][d])
