@@ -104,15 +104,20 @@ static int launch_dense_one(dim3 grid, size_t lds, hipStream_t st, const DenseAr
     hipLaunchKernelGGL((dense_gemm_kernel<T, TN, WK, ACT, MR, R16>), grid, dim3(64 * TN * WK), lds, st, a);
     return TGIS_OK;
 }
+// rows per pass of the kernel a plan runs: 2 (64-row passes, two-k-part blocks only), 1, or 0 for the 16-row staging (R16)
+static int dense_row_class(const DensePlan& pl, int64_t M) {
+    if (pl.WK == 2 && pl.MR == 2) return 2;
+    // batches of up to 16 rows stage 16 rows of x (dense_gemm_body.h, R16); the LDS request shrinks with them.  Same box,
+    // 32-row staging patched back in: cfg2 1.066 / 1.067 -> 1.038 / 1.044 ms per step (profiles/r06d_bench_cfg2_rows16_*.json)
+    return M <= 16 ? 0 : 1;
+}
+
 template <typename T, int TN, int WK, int ACT>
 static int launch_dense_variant(int mr, dim3 grid, size_t lds, hipStream_t st, const DenseArgs& a) {
     if constexpr (WK == 2) {
         if (mr == 2) return launch_dense_one<T, TN, WK, ACT, 2>(grid, lds, st, a);
     }
-    // batches of up to 16 rows stage 16 rows of x (dense_gemm_body.h, R16); the LDS request shrinks with them.  Same box,
-    // 32-row staging patched back in: cfg2 1.066 / 1.067 -> 1.038 / 1.044 ms per step (profiles/r06d_bench_cfg2_rows16_*.json)
-    if (a.M <= 16)
-        return launch_dense_one<T, TN, WK, ACT, 1, true>(grid, (size_t)WK * 2 * 16 * DRS * sizeof(T) + 64, st, a);
+    if (mr == 0) return launch_dense_one<T, TN, WK, ACT, 1, true>(grid, (size_t)WK * 2 * 16 * DRS * sizeof(T) + 64, st, a);
     return launch_dense_one<T, TN, WK, ACT, 1>(grid, lds, st, a);
 }
 
@@ -120,15 +125,16 @@ template <typename T>
 static int launch_dense(const DenseArgs& a, const DensePlan& pl, int act, int64_t mslabs32, hipStream_t st) {
     dim3 grid((unsigned)cdiv64(a.NT, pl.TN), (unsigned)pl.S, (unsigned)cdiv64(mslabs32, pl.MR));
     const size_t lds = (size_t)pl.WK * 2 * 32 * pl.MR * DRS * sizeof(T) + 64;
+    const int rows = dense_row_class(pl, a.M);
     int rc = TGIS_EINVAL;
 #define TGIS_DENSE_CASE(T_, W_)                                                        \
     if (pl.TN == T_ && pl.WK == W_)                                                    \
-        rc = act == 3   ? launch_dense_variant<T, T_, W_, 3>(pl.MR, grid, lds, st, a)                                           \
-             : act == 2 ? launch_dense_variant<T, T_, W_, 2>(pl.MR, grid, lds, st, a)                                           \
-             : act == 1 ? launch_dense_variant<T, T_, W_, 1>(pl.MR, grid, lds, st, a)                                           \
-                        : launch_dense_variant<T, T_, W_, 0>(pl.MR, grid, lds, st, a)
+        rc = act == 3   ? launch_dense_variant<T, T_, W_, 3>(rows, grid, lds, st, a)                                             \
+             : act == 2 ? launch_dense_variant<T, T_, W_, 2>(rows, grid, lds, st, a)                                             \
+             : act == 1 ? launch_dense_variant<T, T_, W_, 1>(rows, grid, lds, st, a)                                             \
+                        : launch_dense_variant<T, T_, W_, 0>(rows, grid, lds, st, a)
     // one tile per k-part group: the fused qkv + rotary launch of a narrow projection (TinyLlama: 80 tiles, unsplit)
-    if (pl.TN == 1 && pl.WK == 4 && act == 3) rc = launch_dense_variant<T, 1, 4, 3>(pl.MR, grid, lds, st, a);
+    if (pl.TN == 1 && pl.WK == 4 && act == 3) rc = launch_dense_variant<T, 1, 4, 3>(rows, grid, lds, st, a);
     TGIS_DENSE_CASE(2, 2);
     TGIS_DENSE_CASE(2, 4);
     TGIS_DENSE_CASE(3, 4);
@@ -187,6 +193,23 @@ extern "C" int64_t tgis_dense_gemm_workspace_bytes(int64_t M, int64_t K, int64_t
     return 4096 + (pl.S > 1 ? dense_slab_bytes(M, N, pl.S) : 0);
 }
 
+// The unsplit plan of the fused qkv + rotary launch: plan_dense's SiLU plan, with ONE tile per k-part group where two would
+// leave fewer than 128 blocks (round 5: TinyLlama's 80 tiles ran as 40 blocks of 262 KB each — one CU takes in ~50 GB/s).
+static DensePlan plan_dense_rope(int64_t K, int64_t N, int64_t M) {
+    DensePlan pl = plan_dense(K, N, M, 2);
+    const int64_t tiles = cdiv64(N, 32);
+    if (M <= 32 && pl.WK == 4 && cdiv64(tiles, pl.TN) < 128) pl.TN = 1;
+    return pl;
+}
+
+// The plan each entry point launches (entry 0 tgis_dense_gemm, 1 _partial, 2 _gemm_rope); tgis_debug_gemm_plan reports it.
+// GELU (act 4 / 5) is applied to the finished sum: its plan is the plain one.
+static DensePlan choose_dense(int entry, int64_t M, int64_t K, int64_t N, int act) {
+    if (entry == 2) return plan_dense_rope(K, N, M);
+    if (entry == 1 || act == 4 || act == 5) return plan_dense(K, N, M);
+    return plan_dense(K, N, M, act);
+}
+
 static int dense_check(const void* x, int64_t ldx, const void* prepared, int64_t M, int64_t K, int64_t N, int dtype,
                        int act) {
     TGIS_CHECK_ARG(x && prepared, "tgis_dense_gemm: null tensor");
@@ -234,8 +257,8 @@ extern "C" int tgis_dense_gemm(const void* x, int64_t ldx, const void* prepared,
     if (M == 0) return TGIS_OK;
     hipStream_t st = (hipStream_t)stream;
     const int gelu = act == 4 ? 1 : act == 5 ? 2 : 0;  // GELU of the finished sum: epilogue (unsplit) or split-K reduce
+    const DensePlan pl = choose_dense(0, M, K, N, act);
     if (gelu) act = 0;
-    DensePlan pl = plan_dense(K, N, M, act);
     TGIS_CHECK_ARG(act != 2 || (!out_f32 && pl.S == 1), "tgis_dense_gemm: act 2 writes the model dtype, unsplit");
     TGIS_CHECK_ARG(!gelu || !out_f32, "tgis_dense_gemm: act 4 / 5 (GELU) write the model dtype");
     const int64_t need = tgis_dense_gemm_workspace_bytes(M, K, N);
@@ -250,14 +273,6 @@ extern "C" int tgis_dense_gemm(const void* x, int64_t ldx, const void* prepared,
 }
 
 // ---- qkv projection with the rotary embedding and the cache write in its epilogue (dense weights) ---------------------
-// The unsplit plan of the fused qkv + rotary launch: plan_dense's SiLU plan, with ONE tile per k-part group where two would
-// leave fewer than 128 blocks (round 5: TinyLlama's 80 tiles ran as 40 blocks of 262 KB each — one CU takes in ~50 GB/s).
-static DensePlan plan_dense_rope(int64_t K, int64_t N, int64_t M) {
-    DensePlan pl = plan_dense(K, N, M, 2);
-    const int64_t tiles = cdiv64(N, 32);
-    if (M <= 32 && pl.WK == 4 && cdiv64(tiles, pl.TN) < 128) pl.TN = 1;
-    return pl;
-}
 
 extern "C" int tgis_dense_rope_ok(int64_t M, int64_t K, int64_t N, int64_t D) {
     if (M < 1 || M > 64 || D < 32 || D % 32 || N <= 0 || N % D || K <= 0 || K % 8) return 0;
@@ -280,7 +295,7 @@ extern "C" int tgis_dense_gemm_rope(const void* x, int64_t ldx, const void* prep
     TGIS_CHECK_ARG(H >= 1 && Hkv >= 1 && (H + 2 * Hkv) * D == N && ldq >= H * D,
                    "tgis_dense_gemm_rope: N must be (H + 2 Hkv) * D and q rows must hold H * D elements");
     hipStream_t st = (hipStream_t)stream;
-    DensePlan pl = plan_dense_rope(K, N, M);  // as the SiLU epilogue: the whole k range in one block (S == 1)
+    const DensePlan pl = choose_dense(2, M, K, N, 3);  // as the SiLU epilogue: the whole k range in one block (S == 1)
     TgisTimedScope timed(TGIS_OP_DENSE_GEMM, st);
     DenseArgs a;
     dense_fill(a, x, ldx, prepared, bias, q_out, ldq, M, K, N, 0, nullptr, 0, pl);
@@ -311,7 +326,7 @@ extern "C" int tgis_dense_gemm_partial(const void* x, int64_t ldx, const void* p
     TGIS_CHECK_ARG(slabs && slabs_bytes >= tgis_dense_gemm_partial_bytes(M, K, N),
                    "tgis_dense_gemm_partial: slab buffer too small");
     hipStream_t st = (hipStream_t)stream;
-    DensePlan pl = plan_dense(K, N, M);
+    const DensePlan pl = choose_dense(1, M, K, N, act);
     if (num_slabs) *num_slabs = pl.S;
     if (slab_ld) *slab_ld = cdiv64(N, 32) * 32;
     TgisTimedScope timed(TGIS_OP_DENSE_GEMM, st);
@@ -320,3 +335,21 @@ extern "C" int tgis_dense_gemm_partial(const void* x, int64_t ldx, const void* p
     return dtype == TGIS_F16 ? launch_dense<f16>(a, pl, act, cdiv64(M, 32), st)
                              : launch_dense<bf16>(a, pl, act, cdiv64(M, 32), st);
 }
+
+// tgis_debug_gemm_plan (gptq.hip) for the dense entry points: info as documented there
+namespace dense {
+int debug_plan(int entry, int64_t M, int64_t K, int64_t N, int act, int dtype, int* info) {
+    TGIS_CHECK_ARG(entry >= 0 && entry <= 2 && (dtype == TGIS_F16 || dtype == TGIS_BF16), "tgis_debug_gemm_plan: bad arguments");
+    const DensePlan pl = choose_dense(entry, M, K, N, act);
+    const int rows = dense_row_class(pl, M);
+    info[0] = entry == 2 ? 6 : 4;
+    info[1] = pl.TN, info[2] = pl.WK, info[3] = pl.KR, info[4] = pl.S;
+    info[5] = rows == 2 ? 2 : 1;
+    info[7] = rows == 0;
+    info[8] = entry == 2 ? 3 : (act == 4 || act == 5) ? 0 : act;
+    info[12] = entry == 0 && pl.S > 1;
+    info[13] = dtype == TGIS_BF16;
+    info[14] = act == 4 ? 1 : act == 5 ? 2 : 0;
+    return TGIS_OK;
+}
+}  // namespace dense

@@ -21,6 +21,10 @@
 #include "gptq_gemm_body.h"
 #include "gptq_wide_body.h"
 
+namespace dense {
+int debug_plan(int entry, int64_t M, int64_t K, int64_t N, int act, int dtype, int* info);  // gemm_dense.hip
+}
+
 namespace {
 
 using gptq::PrepLayout;
@@ -483,10 +487,14 @@ static int64_t tall_max_m() {
     static const int64_t v = getenv("TGIS_TALL_MAX_M") ? atoll(getenv("TGIS_TALL_MAX_M")) : 3072;
     return v;
 }
-static bool tall_ok(int64_t M, int64_t K, int64_t groups, const int32_t* perm, int act) {
-    if (M < tall_min_m() || perm != nullptr || act == 1 || K % 64 != 0) return false;
+// groups of 64 * 2^n rows (one {scale, zero} per k64-step); a single group needs whole k64-steps too, or the half-valid last
+// step of K % 64 == 32 would drop with the zero scale that masks steps past the k range
+static bool gptq_group64(int64_t K, int64_t groups) {
     const int64_t gs = K / groups, spg = gs / 64;
-    return groups == 1 || (gs % 64 == 0 && (spg & (spg - 1)) == 0);
+    return K % 64 == 0 && (groups == 1 || (gs % 64 == 0 && (spg & (spg - 1)) == 0));
+}
+static bool tall_ok(int64_t M, int64_t K, int64_t groups, const int32_t* perm, int act) {
+    return M >= tall_min_m() && perm == nullptr && act != 1 && gptq_group64(K, groups);
 }
 struct TallPlan {
     int BMR, S, KR, TW;
@@ -645,7 +653,7 @@ static int launch_gptq(const void* x, int64_t ldx, const void* prepared, const v
     const int64_t mslabs = cdiv64(M, 32 * pl.MR);  // passes over the weights
     const int64_t gs = K / groups;
     const int64_t spg = gs / 64;  // k64-steps per group
-    const bool group64 = groups == 1 || (gs % 64 == 0 && (spg & (spg - 1)) == 0);
+    const bool group64 = gptq_group64(K, groups);
     GemmArgs a;
     a.x = (const f16*)x;
     a.ldx = ldx;
@@ -788,6 +796,54 @@ static GemmPlan wide_plan_as_gemm_plan(int64_t K, int64_t N, int act, int64_t M,
     return {0, w.S, gptq::WIDE_WK, w.CT, 1};
 }
 
+// ---- launch choice: which kernel instance an entry point runs ----------------------------------------------------------
+// The one place that turns (entry point, shape, act, act-order, layouts) into a kernel family and plan: the entry points
+// below launch what it returns, and tgis_debug_gemm_plan reports it.
+enum GemmEntry { ENTRY_GEMM = 0, ENTRY_PARTIAL = 1, ENTRY_ROPE = 2 };
+enum GemmFamily { FAM_STREAM = 0, FAM_SPLIT_SILU = 1, FAM_WIDE = 2, FAM_TALL = 3, FAM_DENSE = 4, FAM_GPTQ_ROPE = 5,
+                  FAM_DENSE_ROPE = 6 };
+struct GptqLaunch {
+    int family;
+    GemmPlan pl;  // FAM_STREAM / FAM_SPLIT_SILU / FAM_GPTQ_ROPE: the streaming plan; FAM_WIDE: TN = CT, S
+    TallPlan tp;  // FAM_TALL
+};
+static GptqLaunch choose_gptq(int entry, int64_t M, int64_t K, int64_t N, int64_t groups, int act, bool perm,
+                              bool frag_in) {
+    static const int32_t some_perm = 0;
+    GptqLaunch c{};
+    if (entry == ENTRY_ROPE) {
+        c.family = frag_in ? FAM_WIDE : FAM_GPTQ_ROPE;
+        c.pl = frag_in ? wide_plan_as_gemm_plan(K, N, 3, M) : plan_gemm(K, N, 2, M);  // whole k range in one block
+        return c;
+    }
+    if (frag_in) {
+        c.family = FAM_WIDE;
+        // the f16 entry point finishes its output; the partial form leaves slabs
+        c.pl = wide_plan_as_gemm_plan(K, N, entry == ENTRY_PARTIAL ? 0 : act, M, entry == ENTRY_GEMM);
+        return c;
+    }
+    if (tall_ok(M, K, groups, perm ? &some_perm : nullptr, act)) {
+        c.family = FAM_TALL;
+        c.tp = plan_tall(M, K, N, act);
+        return c;
+    }
+    c.family = FAM_STREAM;
+    c.pl = plan_gemm(K, N, entry == ENTRY_PARTIAL ? 0 : act, M);
+    // SiLU * up whose unsplit plan has few blocks (TP shards): every block would take in its whole M x K activation
+    // through one CU (2-8 x its weights: a 70B gate_up shard at TP = 8 and 64 rows, 112 blocks, 34.6 us).  The projection
+    // then runs with the split plan of a plain GEMM and the activation moves into the split-K reduce (us, fused -> split:
+    // 64 rows 8192x7168 34.2 -> 24.0, 4096x2752 18.7 -> 11.3; 32 rows 8192x7168 19.0 -> 15.5, 4096x2752 10.8 -> 8.6,
+    // 4096x5504 (86 blocks) 11.2 -> 10.3; from 172 blocks on the epilogue wins: 4096x11008 11.8 vs 17.5).
+    if (entry == ENTRY_GEMM && act == 2 && cdiv64(cdiv64(N, 32), c.pl.TN) < silu_split_below()) {
+        const GemmPlan ps = plan_gemm(K, N, 0, M);
+        if (ps.S > 1) {
+            c.pl = ps;
+            c.family = FAM_SPLIT_SILU;
+        }
+    }
+    return c;
+}
+
 extern "C" int tgis_gptq_gemm_f16(const void* x, int64_t ldx, const void* prepared, const void* bias,
                                   const int32_t* perm, void* out, int64_t ldo, int64_t M, int64_t K,
                                   int64_t N, int64_t groups, int act, void* workspace,
@@ -797,60 +853,39 @@ extern "C" int tgis_gptq_gemm_f16(const void* x, int64_t ldx, const void* prepar
     TGIS_CHECK_ARG(out, "tgis_gptq_gemm_f16: null out");
     if (M == 0) return TGIS_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (ldx == TGIS_LD_FRAGMENTS) {
+    const bool frag_in = ldx == TGIS_LD_FRAGMENTS;
+    if (frag_in) {
         TGIS_CHECK_ARG(!perm, "tgis_gptq_gemm_f16: act-order matrices take a row-major activation");
         TGIS_CHECK_ARG(ldo != TGIS_LD_FRAGMENTS || (act == 2 && (N / 2) % 64 == 0),
                        "tgis_gptq_gemm_f16: only the act = 2 output (N / 2 a multiple of 64) can leave in fragment order");
-        const GemmPlan wp = wide_plan_as_gemm_plan(K, N, act, M, /*finished=*/true);  // this entry point returns f16
-        const int64_t need_w = 4096 + slab_bytes(M, N, wp.S);
-        TGIS_CHECK_ARG(workspace && workspace_bytes >= need_w, "tgis_gptq_gemm_f16: workspace too small (%ld < %ld)",
-                       (long)workspace_bytes, (long)need_w);
-        TgisTimedScope timed(TGIS_OP_GPTQ_GEMM, st);
-        return launch_gptq(x, ldx, prepared, bias, nullptr, out, ldo, M, K, N, groups, act,
-                           (float*)((uint8_t*)workspace + 4096), 0, wp, st);
+    } else {
+        TGIS_CHECK_ARG(ldo != TGIS_LD_FRAGMENTS, "tgis_gptq_gemm_f16: a fragment-order output needs a fragment-order activation");
     }
-    TGIS_CHECK_ARG(ldo != TGIS_LD_FRAGMENTS, "tgis_gptq_gemm_f16: a fragment-order output needs a fragment-order activation");
-    if (tall_ok(M, K, groups, perm, act)) {
-        const TallPlan tp = plan_tall(M, K, N, act);
-        const int64_t need_t = 4096 + (tp.S > 1 ? tall_slab_bytes(M, N, tp.S) : 0);
+    const GptqLaunch c = choose_gptq(ENTRY_GEMM, M, K, N, groups, act, perm != nullptr, frag_in);
+    float* slabs = (float*)((uint8_t*)workspace + 4096);
+    if (c.family == FAM_TALL) {
+        const int64_t need_t = 4096 + (c.tp.S > 1 ? tall_slab_bytes(M, N, c.tp.S) : 0);
         TGIS_CHECK_ARG(workspace && workspace_bytes >= need_t, "tgis_gptq_gemm_f16: workspace too small (%ld < %ld)",
                        (long)workspace_bytes, (long)need_t);
         TgisTimedScope timed(TGIS_OP_GPTQ_GEMM, st);
-        return launch_tall(x, ldx, prepared, bias, out, ldo, M, K, N, groups, act, (float*)((uint8_t*)workspace + 4096), 0,
-                           tp, st);
+        return launch_tall(x, ldx, prepared, bias, out, ldo, M, K, N, groups, act, slabs, 0, c.tp, st);
     }
-    GemmPlan pl = plan_gemm(K, N, act, M);
-    TGIS_CHECK_ARG(cdiv64(M, 32) <= 65535, "tgis_gptq_gemm_f16: M too large for one launch");
-    // SiLU * up whose unsplit plan has few blocks (TP shards): every block would take in its whole M x K activation
-    // through one CU (2-8 x its weights: a 70B gate_up shard at TP = 8 and 64 rows, 112 blocks, 34.6 us).  The projection
-    // then runs with the split plan of a plain GEMM and the activation moves into the split-K reduce (us, fused -> split:
-    // 64 rows 8192x7168 34.2 -> 24.0, 4096x2752 18.7 -> 11.3; 32 rows 8192x7168 19.0 -> 15.5, 4096x2752 10.8 -> 8.6,
-    // 4096x5504 (86 blocks) 11.2 -> 10.3; from 172 blocks on the epilogue wins: 4096x11008 11.8 vs 17.5).
-    bool split_silu = false;
-    if (act == 2 && cdiv64(cdiv64(N, 32), pl.TN) < silu_split_below()) {
-        const GemmPlan ps = plan_gemm(K, N, 0, M);
-        if (ps.S > 1) {
-            pl = ps;
-            split_silu = true;
-        }
-    }
-    int64_t need = 4096 + slab_bytes(M, N, pl.S);
+    TGIS_CHECK_ARG(frag_in || cdiv64(M, 32) <= 65535, "tgis_gptq_gemm_f16: M too large for one launch");
+    const int64_t need = 4096 + slab_bytes(M, N, c.pl.S);
     TGIS_CHECK_ARG(workspace && workspace_bytes >= need, "tgis_gptq_gemm_f16: workspace too small (%ld < %ld)",
                    (long)workspace_bytes, (long)need);
     TgisTimedScope timed(TGIS_OP_GPTQ_GEMM, st);
-    if (split_silu) {
-        float* slabs = (float*)((uint8_t*)workspace + 4096);
-        rc = launch_gptq(x, ldx, prepared, nullptr, perm, out, ldo, M, K, N, groups, 0, slabs, 1, pl, st);
+    if (c.family == FAM_SPLIT_SILU) {
+        rc = launch_gptq(x, ldx, prepared, nullptr, perm, out, ldo, M, K, N, groups, 0, slabs, 1, c.pl, st);
         if (rc != TGIS_OK) return rc;
         const int NP = (int)cdiv64(N, 32) * 32;
         dim3 rgrid((unsigned)cdiv64((int64_t)32 * (NP / 32) * 4, 256), (unsigned)cdiv64(M, 32));
         hipLaunchKernelGGL(splitk_reduce_silu_kernel, rgrid, dim3(256), 0, st, slabs, (const f16*)bias, (f16*)out, ldo, (int)M,
-                           (int)N, NP, pl.S);
+                           (int)N, NP, c.pl.S);
         TGIS_CHECK_LAUNCH();
         return TGIS_OK;
     }
-    return launch_gptq(x, ldx, prepared, bias, perm, out, ldo, M, K, N, groups, act,
-                       (float*)((uint8_t*)workspace + 4096), 0, pl, st);
+    return launch_gptq(x, ldx, prepared, bias, perm, out, ldo, M, K, N, groups, act, slabs, 0, c.pl, st);
 }
 
 // ---- qkv projection with the rotary embedding and the cache write in its epilogue ------------------------------------
@@ -861,8 +896,7 @@ static int64_t rope_min_blocks(int64_t M) {
 
 extern "C" int tgis_gptq_rope_ok(int64_t M, int64_t K, int64_t N, int64_t groups, int act_order, int64_t D) {
     if (M < 1 || M > 64 || act_order || groups <= 0 || K % groups || D < 32 || D % 32 || N <= 0 || N % D) return 0;
-    const int64_t gs = K / groups, spg = gs / 64;
-    if (!(groups == 1 || (gs % 64 == 0 && (spg & (spg - 1)) == 0))) return 0;
+    if (!gptq_group64(K, groups)) return 0;
     // The epilogue needs the whole k range in one block (no split-K): worth it only while that plan still covers the chip
     // (measured: 7B qkv at 32 rows, 192 blocks: 14.9 vs 17.2 us for the pair; 70B qkv at 64 rows, 80 blocks of 42 MB: +5 % on
     // the step; a TP = 8 shard of the 7B qkv, 24 blocks: +2 % on the rank-step; TinyLlama dense, 40 blocks: +-0).
@@ -883,21 +917,16 @@ extern "C" int tgis_gptq_gemm_rope_f16(const void* x, int64_t ldx, const void* p
     int rc = check_gemm_args(x, ldx, prepared, M, K, N, groups, 0);
     if (rc != TGIS_OK) return rc;
     TGIS_CHECK_ARG(positions && slots && cos && sin && q_out && k_pool && v_pool, "tgis_gptq_gemm_rope_f16: null tensor");
-    {
-        const int64_t gs = groups > 0 && K % groups == 0 ? K / groups : 0, spg = gs / 64;
-        TGIS_CHECK_ARG(M >= 1 && M <= 64 && D >= 32 && D % 32 == 0 &&
-                           (groups == 1 || (gs > 0 && gs % 64 == 0 && (spg & (spg - 1)) == 0)),
-                       "tgis_gptq_gemm_rope_f16: needs 1 <= M <= 64, groups of 64 * 2^n rows and a head size that is a "
-                       "multiple of 32 (M=%ld K=%ld groups=%ld D=%ld)", (long)M, (long)K, (long)groups, (long)D);
-    }
+    TGIS_CHECK_ARG(M >= 1 && M <= 64 && D >= 32 && D % 32 == 0 && gptq_group64(K, groups),
+                   "tgis_gptq_gemm_rope_f16: needs 1 <= M <= 64, K %% 64 == 0, groups of 64 * 2^n rows and a head size "
+                   "that is a multiple of 32 (M=%ld K=%ld groups=%ld D=%ld)", (long)M, (long)K, (long)groups, (long)D);
     TGIS_CHECK_ARG(H >= 1 && Hkv >= 1 && (H + 2 * Hkv) * D == N && ldq >= H * D,
                    "tgis_gptq_gemm_rope_f16: N must be (H + 2 Hkv) * D and q rows must hold H * D elements");
-    GemmPlan pl = plan_gemm(K, N, 2, M);  // as the SiLU epilogue: the whole k range in one block (S == 1)
-    if (ldx == TGIS_LD_FRAGMENTS) pl = wide_plan_as_gemm_plan(K, N, 3, M);
+    const GptqLaunch c = choose_gptq(ENTRY_ROPE, M, K, N, groups, 3, false, ldx == TGIS_LD_FRAGMENTS);
     RopeEpi rope{positions, slots, (const f16*)cos, (const f16*)sin, (f16*)k_pool, (f16*)v_pool, (int)H, (int)Hkv, (int)D};
     hipStream_t st = (hipStream_t)stream;
     TgisTimedScope timed(TGIS_OP_GPTQ_GEMM, st);
-    return launch_gptq(x, ldx, prepared, bias, nullptr, q_out, ldq, M, K, N, groups, 3, nullptr, 0, pl, st, &rope);
+    return launch_gptq(x, ldx, prepared, bias, nullptr, q_out, ldq, M, K, N, groups, 3, nullptr, 0, c.pl, st, &rope);
 }
 
 
@@ -934,27 +963,60 @@ extern "C" int tgis_gptq_gemm_f16_partial(const void* x, int64_t ldx, const void
     if (rc != TGIS_OK) return rc;
     TGIS_CHECK_ARG(M >= 1 && cdiv64(M, 32) <= 65535, "tgis_gptq_gemm_f16_partial: bad M");
     TGIS_CHECK_ARG(act != 2, "tgis_gptq_gemm_f16_partial: act=2 cannot be deferred");
-    if (tall_ok(M, K, groups, perm, act)) {
-        const TallPlan tp = plan_tall(M, K, N, act);
-        TGIS_CHECK_ARG(slabs && slabs_bytes >= tall_slab_bytes(M, N, tp.S),
+    const bool frag_in = ldx == TGIS_LD_FRAGMENTS;
+    TGIS_CHECK_ARG(!frag_in || (!perm && act == 0),
+                   "tgis_gptq_gemm_f16_partial: fragment-order activations: act 0, no act-order");
+    const GptqLaunch c = choose_gptq(ENTRY_PARTIAL, M, K, N, groups, act, perm != nullptr, frag_in);
+    hipStream_t st = (hipStream_t)stream;
+    if (slab_ld) *slab_ld = cdiv64(N, 32) * 32;
+    if (c.family == FAM_TALL) {
+        TGIS_CHECK_ARG(slabs && slabs_bytes >= tall_slab_bytes(M, N, c.tp.S),
                        "tgis_gptq_gemm_f16_partial: slab buffer too small");
-        if (num_slabs) *num_slabs = tp.S;
-        if (slab_ld) *slab_ld = cdiv64(N, 32) * 32;
-        TgisTimedScope timed(TGIS_OP_GPTQ_GEMM, (hipStream_t)stream);
-        return launch_tall(x, ldx, prepared, nullptr, nullptr, 0, M, K, N, groups, act, slabs, 1, tp, (hipStream_t)stream);
-    }
-    GemmPlan pl = plan_gemm(K, N, 0, M);
-    if (ldx == TGIS_LD_FRAGMENTS) {
-        TGIS_CHECK_ARG(!perm && act == 0, "tgis_gptq_gemm_f16_partial: fragment-order activations: act 0, no act-order");
-        pl = wide_plan_as_gemm_plan(K, N, 0, M);
+        if (num_slabs) *num_slabs = c.tp.S;
+        TgisTimedScope timed(TGIS_OP_GPTQ_GEMM, st);
+        return launch_tall(x, ldx, prepared, nullptr, nullptr, 0, M, K, N, groups, act, slabs, 1, c.tp, st);
     }
     TGIS_CHECK_ARG(slabs && slabs_bytes >= tgis_gptq_gemm_partial_bytes(M, K, N),
                    "tgis_gptq_gemm_f16_partial: slab buffer too small");
-    hipStream_t st = (hipStream_t)stream;
-    if (num_slabs) *num_slabs = pl.S;
-    if (slab_ld) *slab_ld = cdiv64(N, 32) * 32;
+    if (num_slabs) *num_slabs = c.pl.S;
     TgisTimedScope timed(TGIS_OP_GPTQ_GEMM, st);
-    return launch_gptq(x, ldx, prepared, nullptr, perm, nullptr, 0, M, K, N, groups, act, slabs, 1, pl, st);
+    return launch_gptq(x, ldx, prepared, nullptr, perm, nullptr, 0, M, K, N, groups, act, slabs, 1, c.pl, st);
+}
+
+// debug aid (not part of the documented ABI): the launch an entry point would make, without launching.  entry: 0
+// tgis_gptq_gemm_f16, 1 _f16_partial, 2 _gemm_rope_f16, 3 tgis_dense_gemm, 4 _partial, 5 _gemm_rope.  info[16] =
+// {family (GemmFamily), TN or CT, WK, KR, S, MR or BMR, TW, R16, kernel ACT, G64, PERM, OUTF, reduce (0 none, 1 sum, 2 sum +
+// SiLU * up), dense dtype (0 f16, 1 bf16), GELU (1 erf, 2 tanh), 0}.
+extern "C" int tgis_debug_gemm_plan(int entry, int64_t M, int64_t K, int64_t N, int64_t groups, int act, int act_order,
+                                    int frag_in, int frag_out, int dtype, int* info) {
+    TGIS_CHECK_ARG(info && M >= 1 && K > 0 && N > 0, "tgis_debug_gemm_plan: bad arguments");
+    for (int i = 0; i < 16; ++i) info[i] = 0;
+    if (entry >= 3) return dense::debug_plan(entry - 3, M, K, N, act, dtype, info);
+    TGIS_CHECK_ARG(entry >= 0 && groups > 0 && K % groups == 0, "tgis_debug_gemm_plan: bad arguments");
+    const GptqLaunch c = choose_gptq(entry, M, K, N, groups, entry == ENTRY_ROPE ? 3 : act, act_order != 0, frag_in != 0);
+    info[0] = c.family;
+    const bool finished = entry == ENTRY_GEMM;
+    if (c.family == FAM_TALL) {
+        info[3] = c.tp.KR, info[4] = c.tp.S, info[5] = c.tp.BMR, info[6] = c.tp.TW;
+        info[8] = act == 2 ? 2 : 0, info[9] = 1;
+        info[12] = finished && c.tp.S > 1;
+        return TGIS_OK;
+    }
+    info[1] = c.pl.TN, info[2] = c.pl.WK, info[3] = c.pl.KR, info[4] = c.pl.S;
+    if (c.family == FAM_WIDE) {
+        info[5] = M > 32 ? 2 : 1;
+        info[8] = entry == ENTRY_ROPE ? 3 : entry == ENTRY_PARTIAL ? 0 : act;
+        info[9] = 1;
+        info[11] = frag_out && info[8] == 2;
+        info[12] = finished && c.pl.S > 1;
+        return TGIS_OK;
+    }
+    info[5] = c.pl.WK == 2 ? c.pl.MR : 1;  // launch_variant: 64-row passes for two-k-part blocks only
+    info[8] = c.family == FAM_GPTQ_ROPE ? 3 : c.family == FAM_SPLIT_SILU ? 0 : act;
+    info[9] = c.family == FAM_GPTQ_ROPE || gptq_group64(K, groups);
+    info[10] = act_order != 0 && c.family != FAM_GPTQ_ROPE;
+    info[12] = c.family == FAM_SPLIT_SILU ? 2 : (finished && c.pl.S > 1 && !getenv("TGIS_GPTQ_NOREDUCE"));
+    return TGIS_OK;
 }
 
 // debug aid (not part of the documented ABI): resident blocks per CU the runtime reports for the main kernel
