@@ -1,6 +1,7 @@
 // Small bandwidth-bound helpers of the decode step: SiLU*mul / GELU, embedding gather, decode slot
 // bookkeeping and greedy argmax + logprob.  All use 16-byte vector accesses.
 #include "common.h"
+#include "rowwise_plan.h"
 
 namespace {
 
@@ -319,6 +320,14 @@ extern "C" int tgis_decode_advance(const int64_t* ids, int64_t* ids_copy, int64_
     return TGIS_OK;
 }
 
+// rows are split over workgroups while the batch leaves most of the chip idle and the caller lent the scratch
+ArgmaxPlan choose_argmax(int64_t B, int64_t V, const void* scratch, int64_t scratch_bytes) {
+    int nseg = (int)std::min<int64_t>(16, 256 / std::max<int64_t>(B, 1));
+    while (nseg > 1 && cdiv64(V, nseg) < 1024) --nseg;
+    const bool split = scratch && nseg > 1 && scratch_bytes >= (int64_t)sizeof(ArgmaxPart) * B * nseg;
+    return {nseg, split, split ? (int)cdiv64(V, nseg) : 0};
+}
+
 extern "C" int64_t tgis_argmax_scratch_bytes(int64_t B) { return B > 0 ? (int64_t)sizeof(ArgmaxPart) * B * 16 : 0; }
 
 extern "C" int tgis_argmax_logprob(const void* logits, int64_t ld, int64_t B, int64_t V, int logits_f32,
@@ -329,11 +338,9 @@ extern "C" int tgis_argmax_logprob(const void* logits, int64_t ld, int64_t B, in
     hipStream_t st = (hipStream_t)stream;
     TgisTimedScope timed(TGIS_OP_SAMPLE, st);
     TGIS_CHECK_ARG(logits_f32 || dtype == TGIS_F16 || dtype == TGIS_BF16, "tgis_argmax_logprob: bad dtype");
-    // rows are split over workgroups while the batch leaves most of the chip idle and the caller lent the scratch
-    int nseg = (int)std::min<int64_t>(16, 256 / std::max<int64_t>(B, 1));
-    while (nseg > 1 && cdiv64(V, nseg) < 1024) --nseg;
-    if (scratch && nseg > 1 && scratch_bytes >= (int64_t)sizeof(ArgmaxPart) * B * nseg) {
-        const int seg_len = (int)cdiv64(V, nseg);
+    const ArgmaxPlan plan = choose_argmax(B, V, scratch, scratch_bytes);
+    if (plan.split) {
+        const int nseg = plan.nseg, seg_len = plan.seg_len;
         ArgmaxPart* parts = (ArgmaxPart*)scratch;
         dim3 grid((unsigned)nseg, (unsigned)B);
         if (logits_f32)
@@ -362,4 +369,54 @@ extern "C" int tgis_argmax_logprob(const void* logits, int64_t ld, int64_t B, in
     }
     TGIS_CHECK_LAUNCH();
     return TGIS_OK;
+}
+
+// debug aid (not part of the documented ABI): the launch form a row-wise entry point would take, without launching.
+//   op 0 norm (tgis_rmsnorm_* / tgis_layernorm_* / tgis_layernorm2_*): args {rows, hidden}; info {nt, iters}
+//   op 1 rope (tgis_rope_kv_write[_partial]): args {T, H, Hkv, D, rot_dim, rope}; info {gy, gen, strided, items}
+//   op 2 rope prefill (tgis_rope_kv_write_prefill, its k / v pages): args {max_len, rot_dim, rope}; info {pps, gen}
+//   op 3 argmax (tgis_argmax_logprob): args {B, V, scratch_bytes, or -1 for no scratch}; info {nseg, split, seg_len}
+//   op 4 sampler (tgis_warp_sample): args {V}; info {reg}
+// info[8] is zeroed first; shapes the entry point refuses are refused here too (TGIS_EINVAL).
+extern "C" int tgis_debug_rowwise_plan(int op, const int64_t* args, int64_t* info) {
+    TGIS_CHECK_ARG(args && info, "tgis_debug_rowwise_plan: null arguments");
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    const int64_t* a = args;
+    switch (op) {
+        case 0: {
+            TGIS_CHECK_ARG(a[0] >= 0 && a[1] > 0 && a[1] % 8 == 0 && a[1] <= 16384,
+                           "tgis_debug_rowwise_plan: norm hidden (%ld) must be a multiple of 8 and <= 16384", (long)a[1]);
+            const NormPlan p = choose_norm(a[0], a[1]);
+            info[0] = p.nt, info[1] = p.iters;
+            return TGIS_OK;
+        }
+        case 1: {
+            TGIS_CHECK_ARG(a[0] >= 0 && a[1] > 0 && a[2] >= 0 && a[3] > 0 && a[3] % 16 == 0 &&
+                               (!a[5] || (a[4] > 0 && a[4] <= a[3] && a[4] % 2 == 0)),
+                           "tgis_debug_rowwise_plan: bad rope shape");
+            const RopePlan p = choose_rope(a[0], (int)a[1], (int)a[2], (int)a[3], (int)a[4], a[5] != 0);
+            info[0] = p.gy, info[1] = p.gen, info[2] = p.strided, info[3] = p.items;
+            return TGIS_OK;
+        }
+        case 2: {
+            TGIS_CHECK_ARG(a[0] >= 0 && (!a[2] || (a[1] > 0 && a[1] % 2 == 0)), "tgis_debug_rowwise_plan: bad rope prefill");
+            const RopePrefillPlan p = choose_rope_prefill(a[0], (int)a[1], a[2] != 0);
+            info[0] = p.pps, info[1] = p.gen;
+            return TGIS_OK;
+        }
+        case 3: {
+            TGIS_CHECK_ARG(a[0] > 0 && a[1] > 0, "tgis_debug_rowwise_plan: bad argmax shape");
+            static const char lent = 0;  // stands for a scratch pointer: only its presence matters
+            const ArgmaxPlan p = choose_argmax(a[0], a[1], a[2] >= 0 ? &lent : nullptr, a[2] >= 0 ? a[2] : 0);
+            info[0] = p.nseg, info[1] = p.split, info[2] = p.seg_len;
+            return TGIS_OK;
+        }
+        case 4: {
+            TGIS_CHECK_ARG(a[0] > 0 && a[0] < (1ll << 31), "tgis_debug_rowwise_plan: bad sampler V");
+            info[0] = choose_sampler(a[0]).reg;
+            return TGIS_OK;
+        }
+    }
+    TGIS_CHECK_ARG(false, "tgis_debug_rowwise_plan: unknown op %d", op);
+    return TGIS_EINVAL;
 }

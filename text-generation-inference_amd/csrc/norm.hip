@@ -5,6 +5,7 @@
 //   y   = norm(res) * weight (+ bias)   [statistics in fp32 from the fp32 sum, one rounding at the end]
 // One 256-thread workgroup per row, 16-byte loads, row cached in registers (hidden <= 16384).
 #include "common.h"
+#include "rowwise_plan.h"
 
 namespace {
 
@@ -151,7 +152,7 @@ static int launch_norm(const void* x, const void* residual, const void* weight, 
     if (rows == 0) return TGIS_OK;
     hipStream_t st = (hipStream_t)stream;
     TgisTimedScope timed(TGIS_OP_NORM, st);
-    const bool wide = rows <= 64 && hidden >= 2048;
+    const bool wide = choose_norm(rows, hidden).nt == 512;
 #define TGIS_NORM_LAUNCH(T, P)                                                                                   \
     do {                                                                                                         \
         if (wide)                                                                                                \
@@ -303,7 +304,7 @@ static int launch_layernorm2(const void* h, const Addend& A, const Addend& B, co
     if (rows == 0) return TGIS_OK;
     hipStream_t st = (hipStream_t)stream;
     TgisTimedScope timed(TGIS_OP_NORM, st);
-    const bool wide = rows <= 64 && hidden >= 2048;
+    const bool wide = choose_norm(rows, hidden).nt == 512;
 #define TGIS_LN2_LAUNCH(T, NT)                                                                                       \
     hipLaunchKernelGGL((layernorm2_kernel<T, NT>), dim3((unsigned)rows), dim3(NT), 0, st, (const T*)h, A, B,         \
                        (const T*)w1, (const T*)b1, (const T*)w2, (const T*)b2, (T*)y1, (T*)y2, (T*)res_out,          \
@@ -319,6 +320,12 @@ static int launch_layernorm2(const void* h, const Addend& A, const Addend& B, co
 }
 
 }  // namespace
+
+// 512 threads for decode-sized batches (few rows: latency matters, not occupancy), 256 otherwise
+NormPlan choose_norm(int64_t rows, int64_t hidden) {
+    const int nt = rows <= 64 && hidden >= 2048 ? 512 : 256;
+    return {nt, (int)cdiv64(hidden / 8, nt)};
+}
 
 extern "C" int tgis_rmsnorm_residual(const void* x, const void* residual, const void* weight, void* y, int64_t ldy,
                                      void* res_out, int64_t rows, int64_t hidden, float eps, int dtype,

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include "common.h"
 #include "kv_layout.h"
+#include "rowwise_plan.h"
 
 namespace {
 
@@ -225,6 +226,17 @@ __global__ __launch_bounds__(256) void rope_kv_prefill_kernel(const T* __restric
 
 }  // namespace
 
+// decode-sized T: spread one token's (H + 2 Hkv) * D/8 work items over several workgroups
+RopePlan choose_rope(int64_t T, int H, int Hkv, int D, int rot_dim, bool rope) {
+    const int items = (H + 2 * Hkv) * (D >> 3);
+    const int gy = T <= 64 ? std::min(16, (items + 255) / 256) : 1;
+    return {gy, rope && rot_dim % 16 != 0, gy * 256 < items, items};  // gen: partial span off the 16-element grid
+}
+
+RopePrefillPlan choose_rope_prefill(int64_t max_len, int rot_dim, bool rope) {
+    return {(int)cdiv64(max_len, 32), rope && rot_dim % 16 != 0};
+}
+
 static int rope_launch(void* qkv, int64_t ld_qkv, const void* cos, const void* sin, const int32_t* positions,
                        const int32_t* slots, void* k_pool, void* v_pool, int64_t T, int H, int Hkv, int D, int rot_dim,
                        int dtype, void* stream, const float* slabs, int S, int64_t slab_ld, const void* bias) {
@@ -241,11 +253,9 @@ static int rope_launch(void* qkv, int64_t ld_qkv, const void* cos, const void* s
     if (T == 0) return TGIS_OK;
     hipStream_t st = (hipStream_t)stream;
     TgisTimedScope timed(TGIS_OP_ROPE_KV, st);
-    // decode-sized T: spread one token's (H + 2 Hkv) * D/8 work items over several workgroups
-    const int items = (H + 2 * Hkv) * (D >> 3);
-    const unsigned gy = T <= 64 ? (unsigned)std::min(16, (items + 255) / 256) : 1u;
-    const dim3 grid((unsigned)T, gy);
-    const bool gen = cos && rot_dim % 16 != 0;  // partial span off the 16-element grid (rope_kv_kernel GEN)
+    const RopePlan plan = choose_rope(T, H, Hkv, D, rot_dim, cos != nullptr);
+    const dim3 grid((unsigned)T, (unsigned)plan.gy);
+    const bool gen = plan.gen;
 #define TGIS_ROPE_LAUNCH(T, G)                                                                                         \
     do {                                                                                                               \
         PartialIn<T> pin{slabs, S, slab_ld, (const T*)bias};                                                           \
@@ -296,12 +306,13 @@ extern "C" int tgis_rope_kv_write_prefill(void* qkv, int64_t ld_qkv, const void*
                          nullptr, 0, 0, nullptr);
     if (rc != TGIS_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int pps = (int)cdiv64(max_len, 32);
+    const RopePrefillPlan plan = choose_rope_prefill(max_len, rot_dim, cos != nullptr);
+    const int pps = plan.pps;
     TGIS_CHECK_ARG(pps <= max_pages && B * pps <= 2147483647LL && Hkv <= 65535, "tgis_rope_kv_write_prefill: grid too large");
     TgisTimedScope timed(TGIS_OP_ROPE_KV, st);
     const dim3 grid((unsigned)(B * pps), (unsigned)Hkv);
     const size_t lds = (size_t)32 * (D + 8) * 2;
-    const bool gen = cos && rot_dim % 16 != 0;
+    const bool gen = plan.gen;
 #define TGIS_ROPE_PREFILL_LAUNCH(T, G)                                                                                  \
     hipLaunchKernelGGL((rope_kv_prefill_kernel<T, G>), grid, dim3(256), lds, st, (const T*)qkv, ld_qkv, (const T*)cos,  \
                        (const T*)sin, positions, cu_seqlens, block_tables, max_pages, (T*)k_pool, (T*)v_pool, H, Hkv, D, \

@@ -25,6 +25,7 @@
 // generator: E_i = -log(u_i), u_i from Philox4x32-10 keyed by the request's seed with counter (i, draw offset).
 // A request's stream is (seed, offset): it survives concatenate / prune by copying two integers.
 #include "common.h"
+#include "rowwise_plan.h"
 
 namespace {
 
@@ -556,6 +557,12 @@ __global__ __launch_bounds__(NT) void warp_sample_reg_kernel(SampleArgs a) {
 
 }  // namespace
 
+// the register kernel holds up to 32 elements per thread; TGIS_SAMPLER_GLOBAL_ROWS forces the global-row kernel
+SamplerPlan choose_sampler(int64_t V) {
+    static const bool no_reg = getenv("TGIS_SAMPLER_GLOBAL_ROWS") != nullptr;  // A / B and test hook
+    return {V <= 32 * NT && !no_reg};
+}
+
 extern "C" int tgis_warp_sample(const float* logits, int64_t ld_logits, float* scores, int64_t ld_scores, int64_t B,
                                 int64_t V, const float* temperature, const int* top_k, const float* top_p_cut,
                                 const float* typical_p, const float* rep_penalty, const int64_t* input_ids,
@@ -574,8 +581,7 @@ extern "C" int tgis_warp_sample(const float* logits, int64_t ld_logits, float* s
     SampleArgs a{logits, ld_logits, scores, ld_scores, (int)V, temperature, top_k, top_p_cut, typical_p, rep_penalty,
                  input_ids, ld_ids, (int)L, (int)exclude_id, eos_adjust, (int)eos_id, do_sample, rng, next_ids,
                  next_logprob, lse};
-    static const bool no_reg = getenv("TGIS_SAMPLER_GLOBAL_ROWS") != nullptr;  // A / B and test hook
-    if (V <= 32 * NT && !no_reg)
+    if (choose_sampler(V).reg)
         hipLaunchKernelGGL(warp_sample_reg_kernel<32>, dim3((unsigned)B), dim3(NT), 0, st, a);
     else
         hipLaunchKernelGGL(warp_sample_kernel, dim3((unsigned)B), dim3(NT), 0, st, a);
