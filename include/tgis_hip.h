@@ -37,6 +37,14 @@ extern "C" {
  * 32*head_dim element block in an MFMA-fragment-ready order. */
 #define TGIS_KV_PAGE_TOKENS 32
 
+/* KV cache element codes of the *_kv8 entry points (csrc/kv_layout.h).  TGIS_KV_MODEL: the pools hold the
+ * model dtype (the entry point then behaves exactly like the one it extends; the scales are ignored).  TGIS_KV_FP8_E4M3:
+ * the pools hold one byte per element, OCP float8_e4m3fn, in the same page layout: stored = e4m3(sat(x / s)) with sat the
+ * clamp to +-448 and round-to-nearest-even, s = k_scale for k and v_scale for v (one positive float each per layer).  The
+ * NaN codes 0x7F / 0xFF are never written. */
+#define TGIS_KV_MODEL 0
+#define TGIS_KV_FP8_E4M3 1
+
 /* ---- library info ------------------------------------------------------------------------- */
 const char* tgis_version(void);          /* "tgis_hip x.y (gfx950)" */
 const char* tgis_arch(void);             /* offload arch the kernels were compiled for */
@@ -145,6 +153,12 @@ int tgis_gptq_gemm_rope_f16(const void* x, int64_t ldx, const void* prepared, co
                             const int32_t* slots, const void* cos, const void* sin, void* q_out, int64_t ldq,
                             void* k_pool, void* v_pool, int64_t M, int64_t K, int64_t N, int64_t groups, int64_t H,
                             int64_t Hkv, int64_t D, void* stream);
+/* tgis_gptq_gemm_rope_f16 with a KV cache of element kv_dtype (TGIS_KV_*): k / v go into their pages quantised with
+ * k_scale / v_scale; q_out is as above.  Same call site (flash_llama_modeling.py:251-268,282). */
+int tgis_gptq_gemm_rope_f16_kv8(const void* x, int64_t ldx, const void* prepared, const void* bias,
+                                const int32_t* positions, const int32_t* slots, const void* cos, const void* sin, void* q_out,
+                                int64_t ldq, void* k_pool, void* v_pool, int64_t M, int64_t K, int64_t N, int64_t groups,
+                                int64_t H, int64_t Hkv, int64_t D, void* stream, int kv_dtype, float k_scale, float v_scale);
 
 /* The same launch for dense (f16 / bf16) qkv weights: `prepared` from tgis_dense_prepare with
  * flags = TGIS_GPTQ_ROPE_IMAGE(D, H + Hkv); cos / sin in the model dtype; 1 <= M <= 64. */
@@ -153,6 +167,12 @@ int tgis_dense_gemm_rope(const void* x, int64_t ldx, const void* prepared, const
                          const int32_t* slots, const void* cos, const void* sin, void* q_out, int64_t ldq, void* k_pool,
                          void* v_pool, int64_t M, int64_t K, int64_t N, int64_t H, int64_t Hkv, int64_t D, int dtype,
                          void* stream);
+/* tgis_dense_gemm_rope with a KV cache of element kv_dtype (TGIS_KV_*) and its per-layer scales (as
+ * tgis_gptq_gemm_rope_f16_kv8; flash_llama_modeling.py:251-268,282). */
+int tgis_dense_gemm_rope_kv8(const void* x, int64_t ldx, const void* prepared, const void* bias, const int32_t* positions,
+                             const int32_t* slots, const void* cos, const void* sin, void* q_out, int64_t ldq, void* k_pool,
+                             void* v_pool, int64_t M, int64_t K, int64_t N, int64_t H, int64_t Hkv, int64_t D, int dtype,
+                             void* stream, int kv_dtype, float k_scale, float v_scale);
 
 /* Full dequantisation to a dense f16 [K,N] matrix (row-major), the "temp_dq" path the reference
  * uses for M > 50 before a library GEMM (exllamav2.py:65-66,87). */
@@ -258,6 +278,22 @@ int tgis_rope_kv_write_prefill(void* qkv, int64_t ld_qkv, const void* cos, const
                                void* v_pool, int64_t B, int64_t T, int64_t max_len, int H, int Hkv, int D, int rot_dim,
                                int dtype, void* stream);
 
+/* The three cache writers above for a KV cache of element kv_dtype (TGIS_KV_*): k and v are stored as
+ * e4m3(sat(x / k_scale)) / e4m3(sat(x / v_scale)) of the value the 16-bit pool would receive (k after rotary, rounded to
+ * the model dtype); q, qkv_out and the unrotated dims are exactly those of the 16-bit call; the prefill form zeroes the
+ * slots of a last partial page as well.  Same call sites (flash_llama_modeling.py:262-268,282). */
+int tgis_rope_kv_write_kv8(void* qkv, int64_t ld_qkv, const void* cos, const void* sin, const int32_t* positions,
+                           const int32_t* slots, void* k_pool, void* v_pool, int64_t T, int H, int Hkv, int D, int rot_dim,
+                           int dtype, void* stream, int kv_dtype, float k_scale, float v_scale);
+int tgis_rope_kv_write_partial_kv8(const float* slabs, int num_slabs, int64_t slab_ld, const void* bias, void* qkv_out,
+                                   int64_t ld_qkv, const void* cos, const void* sin, const int32_t* positions,
+                                   const int32_t* slots, void* k_pool, void* v_pool, int64_t T, int H, int Hkv, int D,
+                                   int rot_dim, int dtype, void* stream, int kv_dtype, float k_scale, float v_scale);
+int tgis_rope_kv_write_prefill_kv8(void* qkv, int64_t ld_qkv, const void* cos, const void* sin, const int32_t* positions,
+                                   const int32_t* cu_seqlens, const int32_t* block_tables, int64_t max_pages, void* k_pool,
+                                   void* v_pool, int64_t B, int64_t T, int64_t max_len, int H, int Hkv, int D, int rot_dim,
+                                   int dtype, void* stream, int kv_dtype, float k_scale, float v_scale);
+
 /* ---- paged attention, prefill and decode (replaces flash_attn_2_cuda.varlen_fwd,
  *      utils/flash_attn.py:43-78) ---------------------------------------------------------------- */
 /* Number of key-range splits the launcher will use for this shape (so callers can size workspace). */
@@ -277,6 +313,14 @@ int tgis_attn_paged(const void* q, int64_t ld_q, const void* k_pool, const void*
                     const int32_t* cu_seqlens_q, void* out, int64_t ld_out, int64_t B, int H, int Hkv, int D,
                     int64_t max_q_len, int64_t max_ctx, float scale, int dtype, int num_splits,
                     void* workspace, int64_t workspace_bytes, void* stream);
+/* tgis_attn_paged over pools of element kv_dtype (TGIS_KV_*; utils/flash_attn.py:43-78).  A one-byte cache is read as
+ * k_scale * e4m3(k) and v_scale * e4m3(v): k_scale is folded into the softmax scale and 1 / v_scale into its normaliser
+ * (no per-element multiply).  Same launch forms, splits and workspace as tgis_attn_paged. */
+int tgis_attn_paged_kv8(const void* q, int64_t ld_q, const void* k_pool, const void* v_pool, const int32_t* block_tables,
+                        int64_t max_pages, const int32_t* ctx_lens, const int32_t* cu_seqlens_q, void* out, int64_t ld_out,
+                        int64_t B, int H, int Hkv, int D, int64_t max_q_len, int64_t max_ctx, float scale, int dtype,
+                        int num_splits, void* workspace, int64_t workspace_bytes, void* stream, int kv_dtype,
+                        float k_scale, float v_scale);
 
 /* ---- elementwise --------------------------------------------------------------------------------- */
 /* out[T,I] = act(gate_up[T,0:I]) * gate_up[T,I:2I]; act 1 = SiLU (flash_llama_modeling.py:332-335). */

@@ -40,7 +40,9 @@ namespace {
 
 // NW = waves per workgroup (the key range of a block is dealt page-by-page to its waves)
 // PIPE: two pages of K/V loads in flight per wave (twice the fragment registers)
-template <typename T, int D, int NW, int CH, bool PIPE>
+// KV: the pool's element, T (16-bit cache) or uint8_t (e4m3 codes, kv_layout.h): a one-byte fragment is an 8-byte nontemporal
+// load widened to T in registers; the MFMAs, Q and P stay in T
+template <typename T, typename KV, int D, int NW, int CH, bool PIPE>
 __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(AttnArgs a) {
     using V8 = typename VecT<T>::x8;
     constexpr int KS = D / 32;  // k-steps of the QK^T MFMA
@@ -137,15 +139,14 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(AttnArgs a) {
 
     // one page of K (two 16-token halves x KS k-steps) and V^T (NB 16-row blocks): 16 KiB per wave at D = 128
     auto load_page = [&](const int pg, V8 (&kf)[2][KS], V8 (&vf)[NB]) {
-        const T* kb = reinterpret_cast<const T*>(a.kpool) + ((int64_t)pg * a.Hkv + hk) * (32 * D) + lane * 8;
-        const T* vb = reinterpret_cast<const T*>(a.vpool) + ((int64_t)pg * a.Hkv + hk) * (32 * D) + c * (D * 8) + col * 8;
+        const KV* kb = reinterpret_cast<const KV*>(a.kpool) + ((int64_t)pg * a.Hkv + hk) * (32 * D) + lane * 8;
+        const KV* vb = reinterpret_cast<const KV*>(a.vpool) + ((int64_t)pg * a.Hkv + hk) * (32 * D) + c * (D * 8) + col * 8;
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) kf[t][ks] = __builtin_nontemporal_load(
-                reinterpret_cast<const V8*>(kb + t * (16 * D) + ks * 512));
+            for (int ks = 0; ks < KS; ++ks) kf[t][ks] = kv_get8_nt<T, KV>(kb + t * (16 * D) + ks * 512);
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) vf[nb] = __builtin_nontemporal_load(reinterpret_cast<const V8*>(vb + nb * 128));
+        for (int nb = 0; nb < NB; ++nb) vf[nb] = kv_get8_nt<T, KV>(vb + nb * 128);
     };
     // The page a sequence is still filling: only the part its nv written tokens occupy is requested (round 5: the launch
     // cost one whole page per started page — bench.py's steps got 0.1 ms slower the moment the batch crossed a page
@@ -157,17 +158,17 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(AttnArgs a) {
     // is being filled as well costs 6 - 9 more VGPRs — two instead of three waves per SIMD, which the many-block shapes need;
     // tests/test_ops_gpu.py::test_attention_decode_every_fill_of_the_last_page poisons what must not be requested.)
     auto load_page_part = [&](const int pg, const int nv, V8 (&kf)[2][KS], V8 (&vf)[NB]) {
-        const T* kp = reinterpret_cast<const T*>(a.kpool) + ((int64_t)pg * a.Hkv + hk) * (32 * D);
-        const T* kp1 = kp + (nv > 16 ? 16 * D : 0);  // wave-uniform: a scalar base, the lanes' offsets stay what they are
-        const T* vb = reinterpret_cast<const T*>(a.vpool) + ((int64_t)pg * a.Hkv + hk) * (32 * D) + col * 8 +
-                      ((4 * c < nv) ? c * (D * 8) : 0);
+        const KV* kp = reinterpret_cast<const KV*>(a.kpool) + ((int64_t)pg * a.Hkv + hk) * (32 * D);
+        const KV* kp1 = kp + (nv > 16 ? 16 * D : 0);  // wave-uniform: a scalar base, the lanes' offsets stay what they are
+        const KV* vb = reinterpret_cast<const KV*>(a.vpool) + ((int64_t)pg * a.Hkv + hk) * (32 * D) + col * 8 +
+                       ((4 * c < nv) ? c * (D * 8) : 0);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            kf[0][ks] = __builtin_nontemporal_load(reinterpret_cast<const V8*>(kp + lane * 8 + ks * 512));
-            kf[1][ks] = __builtin_nontemporal_load(reinterpret_cast<const V8*>(kp1 + lane * 8 + ks * 512));
+            kf[0][ks] = kv_get8_nt<T, KV>(kp + lane * 8 + ks * 512);
+            kf[1][ks] = kv_get8_nt<T, KV>(kp1 + lane * 8 + ks * 512);
         }
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) vf[nb] = __builtin_nontemporal_load(reinterpret_cast<const V8*>(vb + nb * 128));
+        for (int nb = 0; nb < NB; ++nb) vf[nb] = kv_get8_nt<T, KV>(vb + nb * 128);
     };
     // FULL: every key of the page is visible to every valid column (all but the last page of a decode step) — no
     // masks.  The softmax reference m[ch] is only moved when a tile maximum exceeds it by more than 2^RESCALE_LOG2
@@ -335,6 +336,9 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(AttnArgs a) {
                 acc[e] += soc[(k * D + ((d & ~15) | ((d & 3) << 2) | ((d >> 2) & 3))) * 16 + j] * f;
             }
         }
+        // one-byte cache: V was read as v / v_scale, so the normaliser becomes l / v_scale (every output form and both merges
+        // then divide by it as they are)
+        if constexpr (kv_is8<T, KV>()) l *= a.inv_v_scale;
         const int64_t tokidx = q0 + t0 + tqj;
         const int headj = hk * a.G + hc * 16 + gj;
         if (a.NS == 1) {
@@ -553,52 +557,52 @@ static int chunks_per_block(int HC, int64_t max_q_len) {
     return (max_q_len == 1 && HC > 1) ? std::min(HC, 3) : 1;
 }
 
-template <typename T, int D, int NW, int CH, bool PIPE>
+template <typename T, typename KV, int D, int NW, int CH, bool PIPE>
 static void launch_attn_pipe(const AttnArgs& a, dim3 grid, hipStream_t st) {
     const size_t lds = (size_t)CH * (NW * D * 16 + NW * 2 * 16) * sizeof(float);
     static bool attr = false;  // e.g. CH = 3, D = 128, NW = 4: 98 KB of combine scratch
     if (!attr && lds > 48 * 1024) {
-        (void)hipFuncSetAttribute((const void*)attn_paged_kernel<T, D, NW, CH, PIPE>,
+        (void)hipFuncSetAttribute((const void*)attn_paged_kernel<T, KV, D, NW, CH, PIPE>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr = true;
     }
-    hipLaunchKernelGGL((attn_paged_kernel<T, D, NW, CH, PIPE>), grid, dim3(64 * NW), lds, st, a);
+    hipLaunchKernelGGL((attn_paged_kernel<T, KV, D, NW, CH, PIPE>), grid, dim3(64 * NW), lds, st, a);
 }
 
 // Two pages in flight where a block is alone on its CU anyway (multi-chunk blocks: nothing else there hides the load
 // latency; MQA 48:1, B=32, ctx 4096: 30.3 -> 25.8 us).  The 8-wave blocks of few-group shapes measured no different,
 // and the many-block shapes keep the small-register variant.
-template <typename T, int D, int NW, int CH>
+template <typename T, typename KV, int D, int NW, int CH>
 static void launch_attn_one(const AttnArgs& a, dim3 grid, hipStream_t st) {
     static const int pipe_env = getenv("TGIS_ATTN_PIPE") ? atoi(getenv("TGIS_ATTN_PIPE")) : -1;  // A/B hook
     if constexpr (CH > 1 && NW == 4) {
-        if (pipe_env != 0) return launch_attn_pipe<T, D, NW, CH, true>(a, grid, st);
+        if (pipe_env != 0) return launch_attn_pipe<T, KV, D, NW, CH, true>(a, grid, st);
     }
     if constexpr (CH == 1 && (NW == 2 || NW == 4)) {
-        if (pipe_env == 2) return launch_attn_pipe<T, D, NW, CH, true>(a, grid, st);
+        if (pipe_env == 2) return launch_attn_pipe<T, KV, D, NW, CH, true>(a, grid, st);
     }
-    launch_attn_pipe<T, D, NW, CH, false>(a, grid, st);
+    launch_attn_pipe<T, KV, D, NW, CH, false>(a, grid, st);
 }
 
-template <typename T, int D, int CH>
+template <typename T, typename KV, int D, int CH>
 static void launch_attn_nw(const AttnArgs& a, dim3 grid, hipStream_t st, int nw) {
-    if (nw == 1) return launch_attn_one<T, D, 1, CH>(a, grid, st);
-    if (nw == 2) return launch_attn_one<T, D, 2, CH>(a, grid, st);
+    if (nw == 1) return launch_attn_one<T, KV, D, 1, CH>(a, grid, st);
+    if (nw == 2) return launch_attn_one<T, KV, D, 2, CH>(a, grid, st);
     if constexpr (CH == 1) {  // wide blocks: few (sequence, kv head) groups, the waves of one block share the keys
-        if (nw == 8) return launch_attn_one<T, D, 8, CH>(a, grid, st);
-        if (nw == 3) return launch_attn_one<T, D, 3, CH>(a, grid, st);  // three waves per SIMD at 1024 blocks (A/B hook)
+        if (nw == 8) return launch_attn_one<T, KV, D, 8, CH>(a, grid, st);
+        if (nw == 3) return launch_attn_one<T, KV, D, 3, CH>(a, grid, st);  // three waves per SIMD at 1024 blocks (A/B hook)
     }
-    launch_attn_one<T, D, 4, CH>(a, grid, st);
+    launch_attn_one<T, KV, D, 4, CH>(a, grid, st);
 }
 
-template <typename T, int D>
+template <typename T, typename KV, int D>
 static int launch_attn(const AttnArgs& a, dim3 grid, int64_t total_q, hipStream_t st, int nw, int ch) {
     if (ch == 3)
-        launch_attn_nw<T, D, 3>(a, grid, st, nw);
+        launch_attn_nw<T, KV, D, 3>(a, grid, st, nw);
     else if (ch == 2)
-        launch_attn_nw<T, D, 2>(a, grid, st, nw);
+        launch_attn_nw<T, KV, D, 2>(a, grid, st, nw);
     else
-        launch_attn_nw<T, D, 1>(a, grid, st, nw);
+        launch_attn_nw<T, KV, D, 1>(a, grid, st, nw);
     TGIS_CHECK_LAUNCH();
     if (a.NS > 1 && !a.counters) {
         const int64_t rows = total_q * a.H;
@@ -789,12 +793,17 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
                            const int32_t* block_tables, int64_t max_pages, const int32_t* ctx_lens,
                            const int32_t* cu_seqlens_q, void* out, int64_t ld_out, int64_t B, int H, int Hkv, int D,
                            int64_t max_q_len, int64_t max_ctx, float scale, int dtype, int num_splits,
-                           void* workspace, int64_t workspace_bytes, void* stream) {
+                           void* workspace, int64_t workspace_bytes, void* stream, int kv_dtype, float k_scale,
+                           float v_scale) {
     TGIS_CHECK_ARG(q && k_pool && v_pool && block_tables && ctx_lens && cu_seqlens_q && out,
                    "tgis_attn_paged: null tensor");
     TGIS_CHECK_ARG(H > 0 && Hkv > 0 && H % Hkv == 0, "tgis_attn_paged: H (%d) must be a multiple of Hkv (%d)", H, Hkv);
     TGIS_CHECK_ARG(D == 64 || D == 96 || D == 128, "tgis_attn_paged: head_dim %d not supported (64, 96, 128)", D);
     TGIS_CHECK_ARG(dtype == TGIS_F16 || dtype == TGIS_BF16, "tgis_attn_paged: bad dtype");
+    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || kv_dtype == TGIS_KV_FP8_E4M3, "tgis_attn_paged_kv8: bad kv_dtype %d", kv_dtype);
+    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || (k_scale > 0.f && v_scale > 0.f && k_scale < INFINITY && v_scale < INFINITY),
+                   "tgis_attn_paged_kv8: k_scale and v_scale must be positive and finite");
+    const bool kv8 = kv_dtype == TGIS_KV_FP8_E4M3;
     TGIS_CHECK_ARG(ld_q % 8 == 0 && ((uintptr_t)q % 16) == 0, "tgis_attn_paged: q must be 16-byte aligned");
     TGIS_CHECK_ARG(max_q_len > 0 && max_pages > 0 && num_splits >= 1, "tgis_attn_paged: bad launch bounds");
     TGIS_CHECK_ARG(num_splits == 1 || max_q_len == 1, "tgis_attn_paged: key splits are for decode (max_q_len == 1)");
@@ -829,7 +838,8 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
     const int ch = chunks_per_block(g.HC, max_q_len);
     a.HCB = (g.HC + ch - 1) / ch;
     a.NS = num_splits;
-    a.scale_log2 = scale * 1.4426950408889634f;
+    a.scale_log2 = kv8 ? scale * k_scale * 1.4426950408889634f : scale * 1.4426950408889634f;
+    a.inv_v_scale = kv8 ? 1.f / v_scale : 1.f;
     a.ws_o = nullptr;
     a.ws_ml = nullptr;
     a.counters = nullptr;
@@ -854,7 +864,7 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
     // long q (prefill): blocks of 128 columns that stage each K/V page once in LDS (attention_prefill.hip)
     if (num_splits == 1 && max_q_len * g.Gp > 64 && !getenv("TGIS_ATTN_NO_PREFILL_KERNEL")) {
         TgisTimedScope timed(TGIS_OP_ATTN, st);
-        return tgis_launch_attn_prefill(a, B, Hkv, D, max_q_len, dtype, st);
+        return tgis_launch_attn_prefill(a, B, Hkv, D, max_q_len, dtype, kv8, st);
     }
     int64_t q_tiles = cdiv64(max_q_len, g.TQ);
     TGIS_CHECK_ARG(q_tiles <= 2147483647LL && (int64_t)Hkv * a.HCB <= 65535 && B * num_splits <= 65535,
@@ -876,14 +886,25 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
         if (ch > 1 && (nw > 4 || nw == 3)) nw = 4;
     }
     TgisTimedScope timed(TGIS_OP_ATTN, st);
+    if (kv8) {  // one-byte cache: the same launch shapes over e4m3 pools
+        if (dtype == TGIS_F16) {
+            if (D == 128) return launch_attn<f16, uint8_t, 128>(a, grid, total_q, st, nw, ch);
+            if (D == 96) return launch_attn<f16, uint8_t, 96>(a, grid, total_q, st, nw, ch);
+            return launch_attn<f16, uint8_t, 64>(a, grid, total_q, st, nw, ch);
+        } else {
+            if (D == 128) return launch_attn<bf16, uint8_t, 128>(a, grid, total_q, st, nw, ch);
+            if (D == 96) return launch_attn<bf16, uint8_t, 96>(a, grid, total_q, st, nw, ch);
+            return launch_attn<bf16, uint8_t, 64>(a, grid, total_q, st, nw, ch);
+        }
+    }
     if (dtype == TGIS_F16) {
-        if (D == 128) return launch_attn<f16, 128>(a, grid, total_q, st, nw, ch);
-        if (D == 96) return launch_attn<f16, 96>(a, grid, total_q, st, nw, ch);  // KS = 3, NB = 6 (gpt-neox-20b)
-        return launch_attn<f16, 64>(a, grid, total_q, st, nw, ch);
+        if (D == 128) return launch_attn<f16, f16, 128>(a, grid, total_q, st, nw, ch);
+        if (D == 96) return launch_attn<f16, f16, 96>(a, grid, total_q, st, nw, ch);  // KS = 3, NB = 6 (gpt-neox-20b)
+        return launch_attn<f16, f16, 64>(a, grid, total_q, st, nw, ch);
     } else {
-        if (D == 128) return launch_attn<bf16, 128>(a, grid, total_q, st, nw, ch);
-        if (D == 96) return launch_attn<bf16, 96>(a, grid, total_q, st, nw, ch);
-        return launch_attn<bf16, 64>(a, grid, total_q, st, nw, ch);
+        if (D == 128) return launch_attn<bf16, bf16, 128>(a, grid, total_q, st, nw, ch);
+        if (D == 96) return launch_attn<bf16, bf16, 96>(a, grid, total_q, st, nw, ch);
+        return launch_attn<bf16, bf16, 64>(a, grid, total_q, st, nw, ch);
     }
 }
 
@@ -893,6 +914,18 @@ extern "C" int tgis_attn_paged(const void* q, int64_t ld_q, const void* k_pool, 
                                int64_t max_q_len, int64_t max_ctx, float scale, int dtype, int num_splits,
                                void* workspace, int64_t workspace_bytes, void* stream) {
     return attn_paged_impl(q, ld_q, k_pool, v_pool, block_tables, max_pages, ctx_lens, cu_seqlens_q, out, ld_out, B, H, Hkv, D,
-                           max_q_len, max_ctx, scale, dtype, num_splits, workspace, workspace_bytes, stream);
+                           max_q_len, max_ctx, scale, dtype, num_splits, workspace, workspace_bytes, stream, TGIS_KV_MODEL,
+                           1.f, 1.f);
+}
+
+extern "C" int tgis_attn_paged_kv8(const void* q, int64_t ld_q, const void* k_pool, const void* v_pool,
+                                   const int32_t* block_tables, int64_t max_pages, const int32_t* ctx_lens,
+                                   const int32_t* cu_seqlens_q, void* out, int64_t ld_out, int64_t B, int H, int Hkv, int D,
+                                   int64_t max_q_len, int64_t max_ctx, float scale, int dtype, int num_splits,
+                                   void* workspace, int64_t workspace_bytes, void* stream, int kv_dtype, float k_scale,
+                                   float v_scale) {
+    return attn_paged_impl(q, ld_q, k_pool, v_pool, block_tables, max_pages, ctx_lens, cu_seqlens_q, out, ld_out, B, H, Hkv, D,
+                           max_q_len, max_ctx, scale, dtype, num_splits, workspace, workspace_bytes, stream, kv_dtype,
+                           k_scale, v_scale);
 }
 

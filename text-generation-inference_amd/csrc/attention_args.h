@@ -21,9 +21,12 @@ struct AttnArgs {
     float* ws_o;   // [total_q][H][NS][D]        (fused combine: [group][chunk][16 columns][NS][D])
     float* ws_ml;  // [total_q][H][NS][2]        (fused combine: [group][chunk][16 columns][NS][4], {m, l, -, -})
     unsigned* counters;  // fused combine: per-group arrival counters (zero between launches), or nullptr
+    float inv_v_scale;   // one-byte cache: 1 / v_scale, folded into the softmax normaliser (kv_layout.h)
 };
 
 constexpr float NEG_BIG = -1.0e30f;
 
 // prefill kernel launcher (attention_prefill.hip); `a` carries the geometry filled in by tgis_attn_paged
-int tgis_launch_attn_prefill(const AttnArgs& a, int64_t B, int Hkv, int D, int64_t max_q_len, int dtype, hipStream_t st);
+// (kv8: the pools hold e4m3 codes, kv_layout.h)
+int tgis_launch_attn_prefill(const AttnArgs& a, int64_t B, int Hkv, int D, int64_t max_q_len, int dtype, bool kv8,
+                             hipStream_t st);

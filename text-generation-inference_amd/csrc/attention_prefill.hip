@@ -15,10 +15,13 @@
 #include <type_traits>
 #include "common.h"
 #include "attention_args.h"
+#include "kv_layout.h"
 
 namespace {
 
-template <typename T, int D>
+// KV: the pool's element, T or uint8_t (e4m3 codes, kv_layout.h): a one-byte page is widened to T in the staging registers, so
+// the LDS images and everything behind them are those of the 16-bit cache
+template <typename T, typename KV, int D>
 __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs a) {
     using V8 = typename VecT<T>::x8;
     constexpr int KS = D / 32;  // k-steps of the QK^T MFMA
@@ -95,13 +98,13 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs a) {
     V8 stage[NP];
     auto page_load = [&](int p) {
         const int pg = btrow[p];
-        const T* kp = reinterpret_cast<const T*>(a.kpool) + ((int64_t)pg * a.Hkv + hk) * PAGE_ELEMS;
-        const T* vp = reinterpret_cast<const T*>(a.vpool) + ((int64_t)pg * a.Hkv + hk) * PAGE_ELEMS;
+        const KV* kp = reinterpret_cast<const KV*>(a.kpool) + ((int64_t)pg * a.Hkv + hk) * PAGE_ELEMS;
+        const KV* vp = reinterpret_cast<const KV*>(a.vpool) + ((int64_t)pg * a.Hkv + hk) * PAGE_ELEMS;
 #pragma unroll
         for (int i = 0; i < KP; ++i) {
             if (!piece_ok(i)) continue;
-            stage[i] = ld16<V8>(kp + (i * 256 + tid) * 8);
-            stage[KP + i] = ld16<V8>(vp + (i * 256 + tid) * 8);
+            stage[i] = kv_get8<T, KV>(kp + (i * 256 + tid) * 8);
+            stage[KP + i] = kv_get8<T, KV>(vp + (i * 256 + tid) * 8);
         }
     };
     auto page_store = [&](int buf) {
@@ -210,6 +213,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs a) {
         float ls = lsum[cg];
         ls += __shfl_xor(ls, 16, 64);
         ls += __shfl_xor(ls, 32, 64);  // every lane of a column now holds the column's normaliser
+        if constexpr (kv_is8<T, KV>()) ls *= a.inv_v_scale;  // V was read as v / v_scale (kv_layout.h)
         const float inv = ls > 0.f ? 1.f / ls : 0.f;
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
@@ -231,13 +235,20 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs a) {
 
 }  // namespace
 
-int tgis_launch_attn_prefill(const AttnArgs& a, int64_t B, int Hkv, int D, int64_t max_q_len, int dtype, hipStream_t st) {
+int tgis_launch_attn_prefill(const AttnArgs& a, int64_t B, int Hkv, int D, int64_t max_q_len, int dtype, bool kv8,
+                             hipStream_t st) {
     const int TQB = a.TQ * 8;
     const int64_t q_tiles = cdiv64(max_q_len, TQB);
     TGIS_CHECK_ARG(q_tiles <= 2147483647LL && (int64_t)Hkv * a.HC <= 65535 && B <= 65535, "tgis_attn_paged: grid too large");
     dim3 grid((unsigned)q_tiles, (unsigned)(Hkv * a.HC), (unsigned)B);
     const size_t lds = (size_t)2 * 2 * 32 * D * 2;  // two buffers of (K page + V page); >= 4 wave slices of D*16 floats
-#define TGIS_PREFILL_LAUNCH(T, DD) hipLaunchKernelGGL((attn_prefill_kernel<T, DD>), grid, dim3(256), lds, st, a)
+#define TGIS_PREFILL_LAUNCH(T, DD)                                                                         \
+    do {                                                                                                   \
+        if (kv8)                                                                                           \
+            hipLaunchKernelGGL((attn_prefill_kernel<T, uint8_t, DD>), grid, dim3(256), lds, st, a);        \
+        else                                                                                               \
+            hipLaunchKernelGGL((attn_prefill_kernel<T, T, DD>), grid, dim3(256), lds, st, a);              \
+    } while (0)
     // every head size by name: a size the caller lets through without a kernel here is an error, not the 64 path
     if (dtype == TGIS_F16) {
         if (D == 128) TGIS_PREFILL_LAUNCH(f16, 128);

@@ -32,6 +32,7 @@ struct DenseArgs {
     void* kpool;               // [pages][rHkv][32 * rD] in the K page layout of kv_layout.h
     void* vpool;
     int rH, rHkv, rD;
+    float k_scale, v_scale;    // ACT == 4: the pools hold e4m3 codes of k / k_scale and v / v_scale (kv_layout.h)
 };
 
 constexpr int DKC = 256;      // k per LDS chunk (4 k64-steps)
@@ -66,6 +67,7 @@ __device__ __forceinline__ T finish_out(float v, int gelu) {
 template <typename T, int TN, int WK, int ACT, int MR, bool R16 = false>
 __device__ __forceinline__ void dense_gemm_unit(const DenseArgs& a, const int ntg, const int split, const int mslab,
                                                 unsigned char* smem) {
+    constexpr bool ROPE = ACT == 3 || ACT == 4;  // rope image epilogue; 4: k / v into a one-byte (e4m3) cache
     static_assert(MR == 1 || WK == 2, "64-row passes need the LDS of two k-parts");
     static_assert(WK > 1, "the finish below exchanges k-parts");
     using V8 = typename VecT<T>::x8;
@@ -101,8 +103,8 @@ __device__ __forceinline__ void dense_gemm_unit(const DenseArgs& a, const int nt
     };
 
     // ACT 3: cache slot and rotary position of the rows this wave will finish (distributed finish below)
-    int32_t rpos[ACT == 3 ? MR : 1][ACT == 3 ? 16 / WK : 1], rslot[ACT == 3 ? MR : 1][ACT == 3 ? 16 / WK : 1];
-    if (ACT == 3) {
+    int32_t rpos[ROPE ? MR : 1][ROPE ? 16 / WK : 1], rslot[ROPE ? MR : 1][ROPE ? 16 / WK : 1];
+    if (ROPE) {
 #pragma unroll
         for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
@@ -221,8 +223,8 @@ __device__ __forceinline__ void dense_gemm_unit(const DenseArgs& a, const int nt
     chunk_body(nchunks - 1, std::true_type{});
     // ACT 3: the cos / sin entries of the rows this wave will finish, asked for before the exchange
     constexpr int NR = 16 / WK;
-    T rcos[ACT == 3 ? MR : 1][ACT == 3 ? NR : 1], rsin[ACT == 3 ? MR : 1][ACT == 3 ? NR : 1];
-    if (ACT == 3) {
+    T rcos[ROPE ? MR : 1][ROPE ? NR : 1], rsin[ROPE ? MR : 1][ROPE ? NR : 1];
+    if (ROPE) {
         const int per = a.rD >> 5;
         const int tt = nt - (nt / per) * per;
         const int dr = 16 * tt + (lane & 15);
@@ -276,7 +278,7 @@ __device__ __forceinline__ void dense_gemm_unit(const DenseArgs& a, const int nt
             const int r = wk * NR + j;
             return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         };
-        if (ACT == 3) {
+        if (ROPE) {
             // rope image: a tile of a q / k head holds dims [16 t, 16 t + 16) in lanes c < 16 and their rotation partners
             // rD/2 + [16 t, ..) in lanes c + 16; v heads keep 32 consecutive dims.  Sum (+ bias) rounded to T, rotated in
             // fp32 (the arithmetic of rope_kv_kernel), q to `out`, k / v into their cache pages.  Host guarantees S == 1.
@@ -306,10 +308,16 @@ __device__ __forceinline__ void dense_gemm_unit(const DenseArgs& a, const int nt
                             reinterpret_cast<T*>(a.out)[(int64_t)(m0 + m) * a.ldo + col] = oh;
                         } else {
                             const int page = rslot[mr][j] >> 5, tok = rslot[mr][j] & 31;
-                            if (roth)
+                            if (ACT == 4) {  // one-byte cache: the e4m3 code of the same rounded value (kv_layout.h)
+                                uint8_t* pool = reinterpret_cast<uint8_t*>(roth ? a.kpool : a.vpool);
+                                kv_put<T, uint8_t>(pool + (roth ? ((int64_t)page * a.rHkv + (head - a.rH)) * 32 * a.rD + k_off(tok, d, a.rD)
+                                                             : ((int64_t)page * a.rHkv + (head - a.rH - a.rHkv)) * 32 * a.rD + v_off(tok, d, a.rD)),
+                                                   oh, roth ? a.k_scale : a.v_scale);
+                            } else if (roth) {
                                 kpool[((int64_t)page * a.rHkv + (head - a.rH)) * 32 * a.rD + k_off(tok, d, a.rD)] = oh;
-                            else
+                            } else {
                                 vpool[((int64_t)page * a.rHkv + (head - a.rH - a.rHkv)) * 32 * a.rD + v_off(tok, d, a.rD)] = oh;
+                            }
                         }
                     }
                 }

@@ -129,12 +129,14 @@ static int launch_dense(const DenseArgs& a, const DensePlan& pl, int act, int64_
     int rc = TGIS_EINVAL;
 #define TGIS_DENSE_CASE(T_, W_)                                                        \
     if (pl.TN == T_ && pl.WK == W_)                                                    \
-        rc = act == 3   ? launch_dense_variant<T, T_, W_, 3>(rows, grid, lds, st, a)                                             \
+        rc = act == 4   ? launch_dense_variant<T, T_, W_, 4>(rows, grid, lds, st, a)                                             \
+             : act == 3 ? launch_dense_variant<T, T_, W_, 3>(rows, grid, lds, st, a)                                             \
              : act == 2 ? launch_dense_variant<T, T_, W_, 2>(rows, grid, lds, st, a)                                             \
              : act == 1 ? launch_dense_variant<T, T_, W_, 1>(rows, grid, lds, st, a)                                             \
                         : launch_dense_variant<T, T_, W_, 0>(rows, grid, lds, st, a)
     // one tile per k-part group: the fused qkv + rotary launch of a narrow projection (TinyLlama: 80 tiles, unsplit)
     if (pl.TN == 1 && pl.WK == 4 && act == 3) rc = launch_dense_variant<T, 1, 4, 3>(rows, grid, lds, st, a);
+    if (pl.TN == 1 && pl.WK == 4 && act == 4) rc = launch_dense_variant<T, 1, 4, 4>(rows, grid, lds, st, a);
     TGIS_DENSE_CASE(2, 2);
     TGIS_DENSE_CASE(2, 4);
     TGIS_DENSE_CASE(3, 4);
@@ -246,6 +248,7 @@ static void dense_fill(DenseArgs& a, const void* x, int64_t ldx, const void* pre
     a.cosb = a.sinb = nullptr;
     a.kpool = a.vpool = nullptr;
     a.rH = a.rHkv = a.rD = 0;
+    a.k_scale = a.v_scale = 1.f;
 }
 
 extern "C" int tgis_dense_gemm(const void* x, int64_t ldx, const void* prepared, const void* bias, void* out,
@@ -283,10 +286,10 @@ extern "C" int tgis_dense_rope_ok(int64_t M, int64_t K, int64_t N, int64_t D) {
     return blocks >= (pl.TN == 1 ? std::min<int64_t>(min_blocks, 64) : min_blocks) ? 1 : 0;
 }
 
-extern "C" int tgis_dense_gemm_rope(const void* x, int64_t ldx, const void* prepared, const void* bias,
-                                    const int32_t* positions, const int32_t* slots, const void* cos, const void* sin,
-                                    void* q_out, int64_t ldq, void* k_pool, void* v_pool, int64_t M, int64_t K, int64_t N,
-                                    int64_t H, int64_t Hkv, int64_t D, int dtype, void* stream) {
+static int dense_gemm_rope_impl(const void* x, int64_t ldx, const void* prepared, const void* bias, const int32_t* positions,
+                                const int32_t* slots, const void* cos, const void* sin, void* q_out, int64_t ldq, void* k_pool,
+                                void* v_pool, int64_t M, int64_t K, int64_t N, int64_t H, int64_t Hkv, int64_t D, int dtype,
+                                void* stream, int kv_dtype, float k_scale, float v_scale) {
     int rc = dense_check(x, ldx, prepared, M, K, N, dtype, 0);
     if (rc != TGIS_OK) return rc;
     TGIS_CHECK_ARG(positions && slots && cos && sin && q_out && k_pool && v_pool, "tgis_dense_gemm_rope: null tensor");
@@ -294,6 +297,11 @@ extern "C" int tgis_dense_gemm_rope(const void* x, int64_t ldx, const void* prep
                    "that is a multiple of 32 (M=%ld D=%ld)", (long)M, (long)D);
     TGIS_CHECK_ARG(H >= 1 && Hkv >= 1 && (H + 2 * Hkv) * D == N && ldq >= H * D,
                    "tgis_dense_gemm_rope: N must be (H + 2 Hkv) * D and q rows must hold H * D elements");
+    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || kv_dtype == TGIS_KV_FP8_E4M3, "tgis_dense_gemm_rope_kv8: bad kv_dtype %d",
+                   kv_dtype);
+    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || (k_scale > 0.f && v_scale > 0.f && k_scale < INFINITY && v_scale < INFINITY),
+                   "tgis_dense_gemm_rope_kv8: k_scale and v_scale must be positive and finite");
+    const bool kv8 = kv_dtype == TGIS_KV_FP8_E4M3;
     hipStream_t st = (hipStream_t)stream;
     const DensePlan pl = choose_dense(2, M, K, N, 3);  // as the SiLU epilogue: the whole k range in one block (S == 1)
     TgisTimedScope timed(TGIS_OP_DENSE_GEMM, st);
@@ -308,7 +316,30 @@ extern "C" int tgis_dense_gemm_rope(const void* x, int64_t ldx, const void* prep
     a.rH = (int)H;
     a.rHkv = (int)Hkv;
     a.rD = (int)D;
-    return dtype == TGIS_F16 ? launch_dense<f16>(a, pl, 3, cdiv64(M, 32), st) : launch_dense<bf16>(a, pl, 3, cdiv64(M, 32), st);
+    const int act = kv8 ? 4 : 3;  // 4: k / v into a one-byte (e4m3) cache
+    if (kv8) {
+        a.k_scale = k_scale;
+        a.v_scale = v_scale;
+    }
+    return dtype == TGIS_F16 ? launch_dense<f16>(a, pl, act, cdiv64(M, 32), st)
+                             : launch_dense<bf16>(a, pl, act, cdiv64(M, 32), st);
+}
+
+extern "C" int tgis_dense_gemm_rope(const void* x, int64_t ldx, const void* prepared, const void* bias,
+                                    const int32_t* positions, const int32_t* slots, const void* cos, const void* sin,
+                                    void* q_out, int64_t ldq, void* k_pool, void* v_pool, int64_t M, int64_t K, int64_t N,
+                                    int64_t H, int64_t Hkv, int64_t D, int dtype, void* stream) {
+    return dense_gemm_rope_impl(x, ldx, prepared, bias, positions, slots, cos, sin, q_out, ldq, k_pool, v_pool, M, K, N, H, Hkv,
+                                D, dtype, stream, TGIS_KV_MODEL, 1.f, 1.f);
+}
+
+extern "C" int tgis_dense_gemm_rope_kv8(const void* x, int64_t ldx, const void* prepared, const void* bias,
+                                        const int32_t* positions, const int32_t* slots, const void* cos, const void* sin,
+                                        void* q_out, int64_t ldq, void* k_pool, void* v_pool, int64_t M, int64_t K, int64_t N,
+                                        int64_t H, int64_t Hkv, int64_t D, int dtype, void* stream, int kv_dtype,
+                                        float k_scale, float v_scale) {
+    return dense_gemm_rope_impl(x, ldx, prepared, bias, positions, slots, cos, sin, q_out, ldq, k_pool, v_pool, M, K, N, H, Hkv,
+                                D, dtype, stream, kv_dtype, k_scale, v_scale);
 }
 
 extern "C" int64_t tgis_dense_gemm_partial_bytes(int64_t M, int64_t K, int64_t N) {

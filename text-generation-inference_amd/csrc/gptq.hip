@@ -627,6 +627,7 @@ struct RopeEpi {
     const f16 *cosb, *sinb;
     f16 *kpool, *vpool;
     int H, Hkv, D;
+    float k_scale = 1.f, v_scale = 1.f;  // one-byte cache (launch_gptq act 4)
 };
 
 template <int CT, int ACT, bool OUTF, int MR>
@@ -679,6 +680,7 @@ static int launch_gptq(const void* x, int64_t ldx, const void* prepared, const v
     a.cosb = a.sinb = nullptr;
     a.kpool = a.vpool = nullptr;
     a.rH = a.rHkv = a.rD = 0;
+    a.k_scale = a.v_scale = 1.f;
     if (rope) {
         a.positions = rope->positions;
         a.slots = rope->slots;
@@ -689,6 +691,8 @@ static int launch_gptq(const void* x, int64_t ldx, const void* prepared, const v
         a.rH = rope->H;
         a.rHkv = rope->Hkv;
         a.rD = rope->D;
+        a.k_scale = rope->k_scale;
+        a.v_scale = rope->v_scale;
     }
     if (groups > 1 && group64)
         for (a.spg_shift = 0; (1 << a.spg_shift) < spg; ++a.spg_shift) {}
@@ -700,6 +704,7 @@ static int launch_gptq(const void* x, int64_t ldx, const void* prepared, const v
 #define TGIS_WIDE(CT)                                                                                   \
     do {                                                                                                \
         int rc_ = act == 3   ? launch_wide_one<CT, 3, false>(wgrid, st, a)                              \
+                  : act == 4 ? launch_wide_one<CT, 4, false>(wgrid, st, a)                              \
                   : act == 2 ? (outf ? launch_wide_one<CT, 2, true>(wgrid, st, a)                       \
                                      : launch_wide_one<CT, 2, false>(wgrid, st, a))                     \
                              : launch_wide_one<CT, 0, false>(wgrid, st, a);                             \
@@ -742,6 +747,11 @@ static int launch_gptq(const void* x, int64_t ldx, const void* prepared, const v
     } while (0)
     if (act == 3) {  // rope epilogue: 64 * 2^n groups, no act-order (checked by the caller)
         TGIS_LAUNCH_GEMM_W(3, true, false);
+        TGIS_CHECK_LAUNCH();
+        return TGIS_OK;
+    }
+    if (act == 4) {  // the rope epilogue into a one-byte (e4m3) cache
+        TGIS_LAUNCH_GEMM_W(4, true, false);
         TGIS_CHECK_LAUNCH();
         return TGIS_OK;
     }
@@ -910,10 +920,10 @@ extern "C" int tgis_gptq_rope_ok(int64_t M, int64_t K, int64_t N, int64_t groups
     return blocks >= rope_min_blocks(M) ? 1 : 0;
 }
 
-extern "C" int tgis_gptq_gemm_rope_f16(const void* x, int64_t ldx, const void* prepared, const void* bias,
-                                       const int32_t* positions, const int32_t* slots, const void* cos, const void* sin,
-                                       void* q_out, int64_t ldq, void* k_pool, void* v_pool, int64_t M, int64_t K, int64_t N,
-                                       int64_t groups, int64_t H, int64_t Hkv, int64_t D, void* stream) {
+static int gptq_gemm_rope_impl(const void* x, int64_t ldx, const void* prepared, const void* bias, const int32_t* positions,
+                               const int32_t* slots, const void* cos, const void* sin, void* q_out, int64_t ldq, void* k_pool,
+                               void* v_pool, int64_t M, int64_t K, int64_t N, int64_t groups, int64_t H, int64_t Hkv, int64_t D,
+                               void* stream, int kv_dtype, float k_scale, float v_scale) {
     int rc = check_gemm_args(x, ldx, prepared, M, K, N, groups, 0);
     if (rc != TGIS_OK) return rc;
     TGIS_CHECK_ARG(positions && slots && cos && sin && q_out && k_pool && v_pool, "tgis_gptq_gemm_rope_f16: null tensor");
@@ -922,11 +932,35 @@ extern "C" int tgis_gptq_gemm_rope_f16(const void* x, int64_t ldx, const void* p
                    "that is a multiple of 32 (M=%ld K=%ld groups=%ld D=%ld)", (long)M, (long)K, (long)groups, (long)D);
     TGIS_CHECK_ARG(H >= 1 && Hkv >= 1 && (H + 2 * Hkv) * D == N && ldq >= H * D,
                    "tgis_gptq_gemm_rope_f16: N must be (H + 2 Hkv) * D and q rows must hold H * D elements");
+    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || kv_dtype == TGIS_KV_FP8_E4M3, "tgis_gptq_gemm_rope_f16_kv8: bad kv_dtype %d",
+                   kv_dtype);
+    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || (k_scale > 0.f && v_scale > 0.f && k_scale < INFINITY && v_scale < INFINITY),
+                   "tgis_gptq_gemm_rope_f16_kv8: k_scale and v_scale must be positive and finite");
+    const bool kv8 = kv_dtype == TGIS_KV_FP8_E4M3;
     const GptqLaunch c = choose_gptq(ENTRY_ROPE, M, K, N, groups, 3, false, ldx == TGIS_LD_FRAGMENTS);
-    RopeEpi rope{positions, slots, (const f16*)cos, (const f16*)sin, (f16*)k_pool, (f16*)v_pool, (int)H, (int)Hkv, (int)D};
+    RopeEpi rope{positions, slots, (const f16*)cos, (const f16*)sin, (f16*)k_pool, (f16*)v_pool, (int)H, (int)Hkv, (int)D,
+                 kv8 ? k_scale : 1.f, kv8 ? v_scale : 1.f};
     hipStream_t st = (hipStream_t)stream;
     TgisTimedScope timed(TGIS_OP_GPTQ_GEMM, st);
-    return launch_gptq(x, ldx, prepared, bias, nullptr, q_out, ldq, M, K, N, groups, 3, nullptr, 0, c.pl, st, &rope);
+    return launch_gptq(x, ldx, prepared, bias, nullptr, q_out, ldq, M, K, N, groups, kv8 ? 4 : 3, nullptr, 0, c.pl, st,
+                       &rope);
+}
+
+extern "C" int tgis_gptq_gemm_rope_f16(const void* x, int64_t ldx, const void* prepared, const void* bias,
+                                       const int32_t* positions, const int32_t* slots, const void* cos, const void* sin,
+                                       void* q_out, int64_t ldq, void* k_pool, void* v_pool, int64_t M, int64_t K, int64_t N,
+                                       int64_t groups, int64_t H, int64_t Hkv, int64_t D, void* stream) {
+    return gptq_gemm_rope_impl(x, ldx, prepared, bias, positions, slots, cos, sin, q_out, ldq, k_pool, v_pool, M, K, N, groups,
+                               H, Hkv, D, stream, TGIS_KV_MODEL, 1.f, 1.f);
+}
+
+extern "C" int tgis_gptq_gemm_rope_f16_kv8(const void* x, int64_t ldx, const void* prepared, const void* bias,
+                                           const int32_t* positions, const int32_t* slots, const void* cos, const void* sin,
+                                           void* q_out, int64_t ldq, void* k_pool, void* v_pool, int64_t M, int64_t K,
+                                           int64_t N, int64_t groups, int64_t H, int64_t Hkv, int64_t D, void* stream,
+                                           int kv_dtype, float k_scale, float v_scale) {
+    return gptq_gemm_rope_impl(x, ldx, prepared, bias, positions, slots, cos, sin, q_out, ldq, k_pool, v_pool, M, K, N, groups,
+                               H, Hkv, D, stream, kv_dtype, k_scale, v_scale);
 }
 
 

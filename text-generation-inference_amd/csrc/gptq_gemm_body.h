@@ -78,6 +78,7 @@ struct GemmArgs {
     f16* kpool;                // [pages][rHkv][32 * rD] in the K page layout of kv_layout.h
     f16* vpool;
     int rH, rHkv, rD;
+    float k_scale, v_scale;    // ACT == 4: the pools hold e4m3 codes of k / k_scale and v / v_scale (kv_layout.h)
 };
 
 #ifdef TGIS_TRACE
@@ -127,9 +128,10 @@ typedef __attribute__((address_space(3))) int lds_int;  // explicit LDS pointer:
 template <int TN, int WK, int ACT, bool GROUP64, bool PERM, int MR>
 __device__ __forceinline__ void gptq_gemm_unit(const GemmArgs& a, const int ntg, const int split, const int mslab,
                                                unsigned char* smem) {
+    constexpr bool ROPE = ACT == 3 || ACT == 4;  // rope image epilogue; 4: k / v into a one-byte (e4m3) cache
     static_assert(MR == 1 || WK == 2, "64-row passes need the LDS of two k-parts");
     static_assert(WK > 1, "the finish below exchanges k-parts");
-    static_assert(ACT != 3 || !PERM, "the rope epilogue is a decode form (<= 64 rows, no act-order)");
+    static_assert(!ROPE || !PERM, "the rope epilogue is a decode form (<= 64 rows, no act-order)");
     constexpr int RING = 4;
     constexpr int XR = 32 * MR;                 // x rows per pass
     constexpr int GT = 64 * TN;                 // threads of one k-part group
@@ -182,8 +184,8 @@ __device__ __forceinline__ void gptq_gemm_unit(const GemmArgs& a, const int ntg,
     uint32_t szr[RING];
 
     // ACT 3: cache slot and rotary position of the rows this wave will finish (see the distributed epilogue)
-    int32_t rpos[ACT == 3 ? MR : 1][ACT == 3 ? 16 / WK : 1], rslot[ACT == 3 ? MR : 1][ACT == 3 ? 16 / WK : 1];
-    if (ACT == 3) {
+    int32_t rpos[ROPE ? MR : 1][ROPE ? 16 / WK : 1], rslot[ROPE ? MR : 1][ROPE ? 16 / WK : 1];
+    if (ROPE) {
 #pragma unroll
         for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
@@ -375,8 +377,8 @@ __device__ __forceinline__ void gptq_gemm_unit(const GemmArgs& a, const int ntg,
     // its tile, i.e. NR of the 16 row groups.  ACT 3: it asks for those rows' cos / sin entries now (the positions were
     // loaded at entry), so that the round trip runs under the k-part exchange.
     constexpr int NR = 16 / WK;
-    f16 rcos[ACT == 3 ? MR : 1][ACT == 3 ? NR : 1], rsin[ACT == 3 ? MR : 1][ACT == 3 ? NR : 1];
-    if (ACT == 3) {
+    f16 rcos[ROPE ? MR : 1][ROPE ? NR : 1], rsin[ROPE ? MR : 1][ROPE ? NR : 1];
+    if (ROPE) {
         const int per = a.rD >> 5;
         const int tt = nt - (nt / per) * per;
         const int dr = 16 * tt + (lane & 15);
@@ -436,7 +438,7 @@ __device__ __forceinline__ void gptq_gemm_unit(const GemmArgs& a, const int ntg,
             const int r = wk * NR + j;
             return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         };
-        if (ACT == 3) {
+        if (ROPE) {
             // Rope image (col_src flags bit 1): a tile of a q or k head holds dims [16 t, 16 t + 16) in lanes c < 16 and
             // their rotation partners rD/2 + [16 t, 16 t + 16) in lanes c + 16; v heads keep 32 consecutive dims.  The sum
             // (+ bias) is rounded to f16 first, then rotated in fp32 — the arithmetic of rope_kv_kernel on the reduced
@@ -466,10 +468,16 @@ __device__ __forceinline__ void gptq_gemm_unit(const GemmArgs& a, const int ntg,
                         a.out[(int64_t)(m0 + m) * a.ldo + col] = oh;
                     } else {
                         const int page = rslot[mr][j] >> 5, tok = rslot[mr][j] & 31;
-                        if (roth)
+                        if (ACT == 4) {  // one-byte cache: the e4m3 code of the same rounded value (kv_layout.h)
+                            uint8_t* pool = reinterpret_cast<uint8_t*>(roth ? a.kpool : a.vpool);
+                            kv_put<f16, uint8_t>(pool + (roth ? ((int64_t)page * a.rHkv + (head - a.rH)) * 32 * a.rD + k_off(tok, d, a.rD)
+                                                         : ((int64_t)page * a.rHkv + (head - a.rH - a.rHkv)) * 32 * a.rD + v_off(tok, d, a.rD)),
+                                               oh, roth ? a.k_scale : a.v_scale);
+                        } else if (roth) {
                             a.kpool[((int64_t)page * a.rHkv + (head - a.rH)) * 32 * a.rD + k_off(tok, d, a.rD)] = oh;
-                        else
+                        } else {
                             a.vpool[((int64_t)page * a.rHkv + (head - a.rH - a.rHkv)) * 32 * a.rD + v_off(tok, d, a.rD)] = oh;
+                        }
                     }
                 }
             }

@@ -100,6 +100,7 @@ static inline int wide_max_splits(int64_t K, int64_t N) {
 // "two tiles per wave on one activation" of the 64-row passes, with the activation in registers instead of LDS).
 template <int CT, int ACT, bool OUTF, int MR>
 __device__ __forceinline__ void gptq_wide_unit(const GemmArgs& a, unsigned char* smem) {
+    constexpr bool ROPE = ACT == 3 || ACT == 4;  // rope image epilogue; 4: k / v into a one-byte (e4m3) cache
     constexpr int WK = WIDE_WK, DEPTH = WIDE_DEPTH, NR = 16 / WK;
     {   // every cache line of the argument block is requested at entry: one scalar round trip instead of three dependent
         // ones before the first weight request (tools/floor/wide.hip `pre`: 0.1 - 0.25 us per launch)
@@ -167,8 +168,8 @@ __device__ __forceinline__ void gptq_wide_unit(const GemmArgs& a, unsigned char*
         return mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
     };
     // ACT 3: their cache slots and rotary positions
-    int32_t rpos[ACT == 3 ? MR : 1][ACT == 3 ? NR : 1], rslot[ACT == 3 ? MR : 1][ACT == 3 ? NR : 1];
-    if (ACT == 3) {
+    int32_t rpos[ROPE ? MR : 1][ROPE ? NR : 1], rslot[ROPE ? MR : 1][ROPE ? NR : 1];
+    if (ROPE) {
 #pragma unroll
         for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
@@ -227,8 +228,8 @@ __device__ __forceinline__ void gptq_wide_unit(const GemmArgs& a, unsigned char*
     WIDE_STAMP(3);
 
     // ACT 3: the finishing rows' cos / sin entries are requested before the exchange (their positions came in at entry)
-    f16 rcos[ACT == 3 ? MR : 1][ACT == 3 ? CT : 1][ACT == 3 ? NR : 1], rsin[ACT == 3 ? MR : 1][ACT == 3 ? CT : 1][ACT == 3 ? NR : 1];
-    if (ACT == 3) {
+    f16 rcos[ROPE ? MR : 1][ROPE ? CT : 1][ROPE ? NR : 1], rsin[ROPE ? MR : 1][ROPE ? CT : 1][ROPE ? NR : 1];
+    if (ROPE) {
         const int per = a.rD >> 5;
 #pragma unroll
         for (int t = 0; t < CT; ++t) {
@@ -283,7 +284,7 @@ __device__ __forceinline__ void gptq_wide_unit(const GemmArgs& a, unsigned char*
         for (int t = tg0; t < tg0 + TG && t < CT; ++t) {
             const int nt = cg * CT + t;
             if (nt >= a.NT) break;
-            if (ACT == 3) {
+            if (ROPE) {
                 // rope image: see gptq_gemm_body.h (the same epilogue on the same image)
                 const int per = a.rD >> 5;
                 const int head = nt / per, tt = nt - head * per;
@@ -307,10 +308,16 @@ __device__ __forceinline__ void gptq_wide_unit(const GemmArgs& a, unsigned char*
                             a.out[(int64_t)m * a.ldo + col] = oh;
                         } else {
                             const int page = rslot[mr][j] >> 5, tok = rslot[mr][j] & 31;
-                            if (roth)
+                            if (ACT == 4) {  // one-byte cache: the e4m3 code of the same rounded value (kv_layout.h)
+                                uint8_t* pool = reinterpret_cast<uint8_t*>(roth ? a.kpool : a.vpool);
+                                kv_put<f16, uint8_t>(pool + (roth ? ((int64_t)page * a.rHkv + (head - a.rH)) * 32 * a.rD + k_off(tok, d, a.rD)
+                                                             : ((int64_t)page * a.rHkv + (head - a.rH - a.rHkv)) * 32 * a.rD + v_off(tok, d, a.rD)),
+                                                   oh, roth ? a.k_scale : a.v_scale);
+                            } else if (roth) {
                                 a.kpool[((int64_t)page * a.rHkv + (head - a.rH)) * 32 * a.rD + k_off(tok, d, a.rD)] = oh;
-                            else
+                            } else {
                                 a.vpool[((int64_t)page * a.rHkv + (head - a.rH - a.rHkv)) * 32 * a.rD + v_off(tok, d, a.rD)] = oh;
+                            }
                         }
                     }
                 }

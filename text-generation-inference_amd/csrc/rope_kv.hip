@@ -29,13 +29,14 @@ __device__ __forceinline__ float load_elem(const T* hp, int64_t t, int col, cons
 // dims, so a half-span is 12 elements).  The work items of the first rc8 = ceil(rot / 8) chunks of a head then share the
 // span's rot / 2 pairs, rotated element by element (same fp32 expressions as the chunk path), and the copies of the dims in
 // [rot, 8 rc8); the chunks behind take the chunk path.  GEN = false is the rot % 16 == 0 kernel.
-template <typename T, bool GEN>
+// KV: the pool's element, T or uint8_t (e4m3 codes of x / k_scale, x / v_scale: kv_layout.h); q and qkv are the same either way.
+template <typename T, typename KV, bool GEN>
 __global__ __launch_bounds__(256) void rope_kv_kernel(T* qkv, int64_t ld, const T* __restrict__ cosb,
                                                       const T* __restrict__ sinb,
                                                       const int32_t* __restrict__ positions,
-                                                      const int32_t* __restrict__ slots, T* __restrict__ kpool,
-                                                      T* __restrict__ vpool, int H, int Hkv, int D, int rot,
-                                                      PartialIn<T> pin) {
+                                                      const int32_t* __restrict__ slots, KV* __restrict__ kpool,
+                                                      KV* __restrict__ vpool, int H, int Hkv, int D, int rot,
+                                                      PartialIn<T> pin, float k_scale, float v_scale) {
     using V8 = typename VecT<T>::x8;
     const int64_t t = blockIdx.x;
     T* row = qkv + t * ld;
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(T* qkv, int64_t ld, const 
         if (GEN && roped && j < rc8) {
             // the rc8 items of the span share its pairs: item j takes pairs j, j + rc8, j + 2 rc8, ... in batches of 4 whose
             // loads are all in flight together, and the copies rot + j, rot + j + rc8, ... (every pair and dim has one owner)
-            T* kb = is_k && kpool ? kpool + ((int64_t)page * Hkv + (head - H)) * 32 * D : nullptr;
+            KV* kb = is_k && kpool ? kpool + ((int64_t)page * Hkv + (head - H)) * 32 * D : nullptr;
             const int half = rot >> 1;
             for (int i0 = j; i0 < half; i0 += 4 * rc8) {
                 float x1[4], x2[4], cf[4], sf[4];
@@ -76,15 +77,15 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(T* qkv, int64_t ld, const 
                     hp[i] = o1;
                     hp[i + half] = o2;
                     if (kb) {
-                        kb[k_off(tok, i, D)] = o1;
-                        kb[k_off(tok, i + half, D)] = o2;
+                        kv_put<T, KV>(kb + k_off(tok, i, D), o1, k_scale);
+                        kv_put<T, KV>(kb + k_off(tok, i + half, D), o2, k_scale);
                     }
                 }
             }
             for (int d = rot + j; d < rc8 * 8; d += rc8) {
                 const T x = from_f32<T>(load_elem<T>(hp + d, t, head * D + d, pin));
                 if (pin.slabs) hp[d] = x;
-                if (kb) kb[k_off(tok, d, D)] = x;
+                if (kb) kv_put<T, KV>(kb + k_off(tok, d, D), x, k_scale);
             }
             continue;
         }
@@ -103,22 +104,22 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(T* qkv, int64_t ld, const 
             st16(hp + j * 8, o1);
             st16(hp + (j + rh8) * 8, o2);
             if (is_k && kpool) {
-                T* kb = kpool + ((int64_t)page * Hkv + (head - H)) * 32 * D;
-                st16(kb + k_off(tok, j * 8, D), o1);
-                st16(kb + k_off(tok, (j + rh8) * 8, D), o2);
+                KV* kb = kpool + ((int64_t)page * Hkv + (head - H)) * 32 * D;
+                kv_put8<T, KV>(kb + k_off(tok, j * 8, D), o1, k_scale);
+                kv_put8<T, KV>(kb + k_off(tok, (j + rh8) * 8, D), o2, k_scale);
             }
         } else if (is_k) {
             if (pin.slabs) st16(hp + j * 8, a);
             if (kpool) {
-                T* kb = kpool + ((int64_t)page * Hkv + (head - H)) * 32 * D;
-                st16(kb + k_off(tok, j * 8, D), a);
+                KV* kb = kpool + ((int64_t)page * Hkv + (head - H)) * 32 * D;
+                kv_put8<T, KV>(kb + k_off(tok, j * 8, D), a, k_scale);
             }
         } else if (is_v) {
             if (pin.slabs) st16(hp + j * 8, a);
             if (!vpool) continue;
-            T* vb = vpool + ((int64_t)page * Hkv + (head - H - Hkv)) * 32 * D + v_off(tok, j * 8, D);
+            KV* vb = vpool + ((int64_t)page * Hkv + (head - H - Hkv)) * 32 * D + v_off(tok, j * 8, D);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) vb[e * 8] = a[e];
+            for (int e = 0; e < 8; ++e) kv_put<T, KV>(vb + e * 8, a[e], v_scale);
         } else if (pin.slabs) {
             st16(hp + j * 8, a);  // un-rotated q chunk (no rope / beyond the rotary span)
         }
@@ -131,14 +132,15 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(T* qkv, int64_t ld, const 
 // (k) and 2-byte (v) stores scattered over the page: fine for the 32 tokens of a decode step, ~4x slower than this on a
 // 32k-token prefill.  Precondition: token i of sequence b sits at cache position i (a fresh prefill; its rotary
 // position comes from `positions` like everywhere else).  Slots of the last page past the sequence end get zeros.
-template <typename T, bool GEN>
+// KV as in rope_kv_kernel.
+template <typename T, typename KV, bool GEN>
 __global__ __launch_bounds__(256) void rope_kv_prefill_kernel(const T* __restrict__ qkv, int64_t ld,
                                                               const T* __restrict__ cosb, const T* __restrict__ sinb,
                                                               const int32_t* __restrict__ positions,
                                                               const int32_t* __restrict__ cu, const int32_t* __restrict__ bt,
-                                                              int64_t max_pages, T* __restrict__ kpool,
-                                                              T* __restrict__ vpool, int H, int Hkv, int D, int rot,
-                                                              int pages_per_seq) {
+                                                              int64_t max_pages, KV* __restrict__ kpool,
+                                                              KV* __restrict__ vpool, int H, int Hkv, int D, int rot,
+                                                              int pages_per_seq, float k_scale, float v_scale) {
     using V8 = typename VecT<T>::x8;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     T* vs = reinterpret_cast<T*>(smem);  // [32 tokens][D + 8]
@@ -150,8 +152,8 @@ __global__ __launch_bounds__(256) void rope_kv_prefill_kernel(const T* __restric
     const int page = bt[(int64_t)b * max_pages + p];
     const int tid = threadIdx.x;
     const int c8 = D >> 3, rh8 = rot >> 4;
-    T* kb = kpool + ((int64_t)page * Hkv + hk) * 32 * D;
-    T* vb = vpool + ((int64_t)page * Hkv + hk) * 32 * D;
+    KV* kb = kpool + ((int64_t)page * Hkv + hk) * 32 * D;
+    KV* vb = vpool + ((int64_t)page * Hkv + hk) * 32 * D;
     V8 zero;
 #pragma unroll
     for (int e = 0; e < 8; ++e) zero[e] = (T)0.f;
@@ -173,10 +175,10 @@ __global__ __launch_bounds__(256) void rope_kv_prefill_kernel(const T* __restric
                     o1 = from_f32<T>(x1 * cf - x2 * sf);
                     o2 = from_f32<T>(x1 * sf + x2 * cf);
                 }
-                kb[k_off(tok, i, D)] = o1;
-                kb[k_off(tok, i + half, D)] = o2;
+                kv_put<T, KV>(kb + k_off(tok, i, D), o1, k_scale);
+                kv_put<T, KV>(kb + k_off(tok, i + half, D), o2, k_scale);
             }
-            for (int d = rot + j; d < rc8 * 8; d += rc8) kb[k_off(tok, d, D)] = kp ? kp[d] : (T)0.f;
+            for (int d = rot + j; d < rc8 * 8; d += rc8) kv_put<T, KV>(kb + k_off(tok, d, D), kp ? kp[d] : (T)0.f, k_scale);
             continue;
         }
         if (!GEN && roped && j >= rh8 && j < 2 * rh8) continue;
@@ -199,8 +201,8 @@ __global__ __launch_bounds__(256) void rope_kv_prefill_kernel(const T* __restric
                 }
             }
         }
-        st16(kb + k_off(tok, j * 8, D), o1);
-        if (pair) st16(kb + k_off(tok, (j + rh8) * 8, D), o2);
+        kv_put8<T, KV>(kb + k_off(tok, j * 8, D), o1, k_scale);
+        if (pair) kv_put8<T, KV>(kb + k_off(tok, (j + rh8) * 8, D), o2, k_scale);
     }
 
     // ---- V: stage [token][d] rows, store [column group][d][8 token columns] runs ----------------------------------------------
@@ -220,7 +222,7 @@ __global__ __launch_bounds__(256) void rope_kv_prefill_kernel(const T* __restric
             o[e] = vs[(c * 4 + e) * rs + d];
             o[e + 4] = vs[(16 + c * 4 + e) * rs + d];
         }
-        st16(vb + ((int64_t)c * D + d) * 8, o);
+        kv_put8<T, KV>(vb + ((int64_t)c * D + d) * 8, o, v_scale);
     }
 }
 
@@ -239,7 +241,8 @@ RopePrefillPlan choose_rope_prefill(int64_t max_len, int rot_dim, bool rope) {
 
 static int rope_launch(void* qkv, int64_t ld_qkv, const void* cos, const void* sin, const int32_t* positions,
                        const int32_t* slots, void* k_pool, void* v_pool, int64_t T, int H, int Hkv, int D, int rot_dim,
-                       int dtype, void* stream, const float* slabs, int S, int64_t slab_ld, const void* bias) {
+                       int dtype, void* stream, const float* slabs, int S, int64_t slab_ld, const void* bias,
+                       int kv_dtype = TGIS_KV_MODEL, float k_scale = 1.f, float v_scale = 1.f) {
     TGIS_CHECK_ARG(qkv, "tgis_rope_kv_write: null qkv");
     TGIS_CHECK_ARG(H > 0 && Hkv >= 0 && D > 0 && D % 16 == 0, "tgis_rope_kv_write: head_dim must be a multiple of 16");
     TGIS_CHECK_ARG(ld_qkv % 8 == 0 && ld_qkv >= (int64_t)(H + 2 * Hkv) * D, "tgis_rope_kv_write: bad row stride");
@@ -248,6 +251,10 @@ static int rope_launch(void* qkv, int64_t ld_qkv, const void* cos, const void* s
                    "tgis_rope_kv_write: rot_dim must be even and <= head_dim");
     TGIS_CHECK_ARG((!k_pool && !v_pool) || slots, "tgis_rope_kv_write: cache write needs slots");
     TGIS_CHECK_ARG(dtype == TGIS_F16 || dtype == TGIS_BF16, "tgis_rope_kv_write: bad dtype");
+    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || kv_dtype == TGIS_KV_FP8_E4M3, "tgis_rope_kv_write_kv8: bad kv_dtype %d",
+                   kv_dtype);
+    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || (k_scale > 0.f && v_scale > 0.f && k_scale < INFINITY && v_scale < INFINITY),
+                   "tgis_rope_kv_write_kv8: k_scale and v_scale must be positive and finite");
     TGIS_CHECK_ARG(!slabs || (S >= 1 && slab_ld >= (int64_t)(H + 2 * Hkv) * D && slab_ld % 4 == 0),
                    "tgis_rope_kv_write_partial: needs a slab row stride >= (H + 2 Hkv) D");
     if (T == 0) return TGIS_OK;
@@ -256,11 +263,16 @@ static int rope_launch(void* qkv, int64_t ld_qkv, const void* cos, const void* s
     const RopePlan plan = choose_rope(T, H, Hkv, D, rot_dim, cos != nullptr);
     const dim3 grid((unsigned)T, (unsigned)plan.gy);
     const bool gen = plan.gen;
-#define TGIS_ROPE_LAUNCH(T, G)                                                                                         \
+#define TGIS_ROPE_LAUNCH_KV(T, KV, G)                                                                                  \
     do {                                                                                                               \
         PartialIn<T> pin{slabs, S, slab_ld, (const T*)bias};                                                           \
-        hipLaunchKernelGGL((rope_kv_kernel<T, G>), grid, dim3(256), 0, st, (T*)qkv, ld_qkv, (const T*)cos,             \
-                           (const T*)sin, positions, slots, (T*)k_pool, (T*)v_pool, H, Hkv, D, rot_dim, pin);          \
+        hipLaunchKernelGGL((rope_kv_kernel<T, KV, G>), grid, dim3(256), 0, st, (T*)qkv, ld_qkv, (const T*)cos,         \
+                           (const T*)sin, positions, slots, (KV*)k_pool, (KV*)v_pool, H, Hkv, D, rot_dim, pin,         \
+                           k_scale, v_scale);                                                                          \
+    } while (0)
+#define TGIS_ROPE_LAUNCH(T, G)                                                                                         \
+    do {                                                                                                               \
+        if (kv_dtype == TGIS_KV_FP8_E4M3) TGIS_ROPE_LAUNCH_KV(T, uint8_t, G); else TGIS_ROPE_LAUNCH_KV(T, T, G);       \
     } while (0)
     if (dtype == TGIS_F16) {
         if (gen) TGIS_ROPE_LAUNCH(f16, true); else TGIS_ROPE_LAUNCH(f16, false);
@@ -268,6 +280,7 @@ static int rope_launch(void* qkv, int64_t ld_qkv, const void* cos, const void* s
         if (gen) TGIS_ROPE_LAUNCH(bf16, true); else TGIS_ROPE_LAUNCH(bf16, false);
     }
 #undef TGIS_ROPE_LAUNCH
+#undef TGIS_ROPE_LAUNCH_KV
     TGIS_CHECK_LAUNCH();
     return TGIS_OK;
 }
@@ -279,6 +292,14 @@ extern "C" int tgis_rope_kv_write(void* qkv, int64_t ld_qkv, const void* cos, co
                        nullptr, 0, 0, nullptr);
 }
 
+extern "C" int tgis_rope_kv_write_kv8(void* qkv, int64_t ld_qkv, const void* cos, const void* sin,
+                                      const int32_t* positions, const int32_t* slots, void* k_pool, void* v_pool,
+                                      int64_t T, int H, int Hkv, int D, int rot_dim, int dtype, void* stream, int kv_dtype,
+                                      float k_scale, float v_scale) {
+    return rope_launch(qkv, ld_qkv, cos, sin, positions, slots, k_pool, v_pool, T, H, Hkv, D, rot_dim, dtype, stream,
+                       nullptr, 0, 0, nullptr, kv_dtype, k_scale, v_scale);
+}
+
 extern "C" int tgis_rope_kv_write_partial(const float* slabs, int num_slabs, int64_t slab_ld, const void* bias,
                                           void* qkv_out, int64_t ld_qkv, const void* cos, const void* sin,
                                           const int32_t* positions, const int32_t* slots, void* k_pool, void* v_pool,
@@ -288,11 +309,20 @@ extern "C" int tgis_rope_kv_write_partial(const float* slabs, int num_slabs, int
                        stream, slabs, num_slabs, slab_ld, bias);
 }
 
-extern "C" int tgis_rope_kv_write_prefill(void* qkv, int64_t ld_qkv, const void* cos, const void* sin,
-                                          const int32_t* positions, const int32_t* cu_seqlens,
-                                          const int32_t* block_tables, int64_t max_pages, void* k_pool, void* v_pool,
-                                          int64_t B, int64_t T, int64_t max_len, int H, int Hkv, int D, int rot_dim,
-                                          int dtype, void* stream) {
+extern "C" int tgis_rope_kv_write_partial_kv8(const float* slabs, int num_slabs, int64_t slab_ld, const void* bias,
+                                              void* qkv_out, int64_t ld_qkv, const void* cos, const void* sin,
+                                              const int32_t* positions, const int32_t* slots, void* k_pool, void* v_pool,
+                                              int64_t T, int H, int Hkv, int D, int rot_dim, int dtype, void* stream,
+                                              int kv_dtype, float k_scale, float v_scale) {
+    TGIS_CHECK_ARG(slabs, "tgis_rope_kv_write_partial_kv8: null slabs");
+    return rope_launch(qkv_out, ld_qkv, cos, sin, positions, slots, k_pool, v_pool, T, H, Hkv, D, rot_dim, dtype,
+                       stream, slabs, num_slabs, slab_ld, bias, kv_dtype, k_scale, v_scale);
+}
+
+static int rope_prefill_launch(void* qkv, int64_t ld_qkv, const void* cos, const void* sin, const int32_t* positions,
+                               const int32_t* cu_seqlens, const int32_t* block_tables, int64_t max_pages, void* k_pool,
+                               void* v_pool, int64_t B, int64_t T, int64_t max_len, int H, int Hkv, int D, int rot_dim,
+                               int dtype, void* stream, int kv_dtype, float k_scale, float v_scale) {
     TGIS_CHECK_ARG(qkv && cu_seqlens && block_tables && k_pool && v_pool, "tgis_rope_kv_write_prefill: null tensor");
     TGIS_CHECK_ARG(B >= 0 && T >= 0 && max_len >= 0 && max_pages > 0, "tgis_rope_kv_write_prefill: bad sizes");
     TGIS_CHECK_ARG(H > 0 && Hkv > 0 && D > 0 && D % 16 == 0, "tgis_rope_kv_write_prefill: head_dim must be a multiple of 16");
@@ -300,6 +330,10 @@ extern "C" int tgis_rope_kv_write_prefill(void* qkv, int64_t ld_qkv, const void*
     TGIS_CHECK_ARG(!cos || (positions && rot_dim > 0 && rot_dim <= D && rot_dim % 2 == 0),
                    "tgis_rope_kv_write_prefill: rot_dim must be even and <= head_dim");
     TGIS_CHECK_ARG(dtype == TGIS_F16 || dtype == TGIS_BF16, "tgis_rope_kv_write_prefill: bad dtype");
+    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || kv_dtype == TGIS_KV_FP8_E4M3, "tgis_rope_kv_write_prefill_kv8: bad kv_dtype %d",
+                   kv_dtype);
+    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || (k_scale > 0.f && v_scale > 0.f && k_scale < INFINITY && v_scale < INFINITY),
+                   "tgis_rope_kv_write_prefill_kv8: k_scale and v_scale must be positive and finite");
     if (B == 0 || T == 0) return TGIS_OK;
     // q heads: rotated in place by the per-token kernel (no cache traffic: Hkv = 0, no pools)
     int rc = rope_launch(qkv, ld_qkv, cos, sin, positions, nullptr, nullptr, nullptr, T, H, 0, D, rot_dim, dtype, stream,
@@ -313,16 +347,40 @@ extern "C" int tgis_rope_kv_write_prefill(void* qkv, int64_t ld_qkv, const void*
     const dim3 grid((unsigned)(B * pps), (unsigned)Hkv);
     const size_t lds = (size_t)32 * (D + 8) * 2;
     const bool gen = plan.gen;
+#define TGIS_ROPE_PREFILL_LAUNCH_KV(T, KV, G)                                                                           \
+    hipLaunchKernelGGL((rope_kv_prefill_kernel<T, KV, G>), grid, dim3(256), lds, st, (const T*)qkv, ld_qkv,             \
+                       (const T*)cos, (const T*)sin, positions, cu_seqlens, block_tables, max_pages, (KV*)k_pool,       \
+                       (KV*)v_pool, H, Hkv, D, rot_dim, pps, k_scale, v_scale)
 #define TGIS_ROPE_PREFILL_LAUNCH(T, G)                                                                                  \
-    hipLaunchKernelGGL((rope_kv_prefill_kernel<T, G>), grid, dim3(256), lds, st, (const T*)qkv, ld_qkv, (const T*)cos,  \
-                       (const T*)sin, positions, cu_seqlens, block_tables, max_pages, (T*)k_pool, (T*)v_pool, H, Hkv, D, \
-                       rot_dim, pps)
+    do {                                                                                                                \
+        if (kv_dtype == TGIS_KV_FP8_E4M3) TGIS_ROPE_PREFILL_LAUNCH_KV(T, uint8_t, G);                                   \
+        else TGIS_ROPE_PREFILL_LAUNCH_KV(T, T, G);                                                                      \
+    } while (0)
     if (dtype == TGIS_F16) {
         if (gen) TGIS_ROPE_PREFILL_LAUNCH(f16, true); else TGIS_ROPE_PREFILL_LAUNCH(f16, false);
     } else {
         if (gen) TGIS_ROPE_PREFILL_LAUNCH(bf16, true); else TGIS_ROPE_PREFILL_LAUNCH(bf16, false);
     }
 #undef TGIS_ROPE_PREFILL_LAUNCH
+#undef TGIS_ROPE_PREFILL_LAUNCH_KV
     TGIS_CHECK_LAUNCH();
     return TGIS_OK;
+}
+
+extern "C" int tgis_rope_kv_write_prefill(void* qkv, int64_t ld_qkv, const void* cos, const void* sin,
+                                          const int32_t* positions, const int32_t* cu_seqlens,
+                                          const int32_t* block_tables, int64_t max_pages, void* k_pool, void* v_pool,
+                                          int64_t B, int64_t T, int64_t max_len, int H, int Hkv, int D, int rot_dim,
+                                          int dtype, void* stream) {
+    return rope_prefill_launch(qkv, ld_qkv, cos, sin, positions, cu_seqlens, block_tables, max_pages, k_pool, v_pool, B, T,
+                               max_len, H, Hkv, D, rot_dim, dtype, stream, TGIS_KV_MODEL, 1.f, 1.f);
+}
+
+extern "C" int tgis_rope_kv_write_prefill_kv8(void* qkv, int64_t ld_qkv, const void* cos, const void* sin,
+                                              const int32_t* positions, const int32_t* cu_seqlens,
+                                              const int32_t* block_tables, int64_t max_pages, void* k_pool, void* v_pool,
+                                              int64_t B, int64_t T, int64_t max_len, int H, int Hkv, int D, int rot_dim,
+                                              int dtype, void* stream, int kv_dtype, float k_scale, float v_scale) {
+    return rope_prefill_launch(qkv, ld_qkv, cos, sin, positions, cu_seqlens, block_tables, max_pages, k_pool, v_pool, B, T,
+                               max_len, H, Hkv, D, rot_dim, dtype, stream, kv_dtype, k_scale, v_scale);
 }

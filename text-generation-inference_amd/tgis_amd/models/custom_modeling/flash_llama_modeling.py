@@ -151,13 +151,15 @@ class FlashLlamaAttention:
                 and native.rope_gemm_ok(hidden_states.shape[0], rope_w, D)):
             # one launch: GEMM + rotary embedding + cache write (native.gptq_gemm_rope / native.dense_gemm_rope)
             fused = native.gptq_gemm_rope if isinstance(rope_w, native.GptqWeight) else native.dense_gemm_rope
-            return fused(hidden_states, rope_w, lin.bias, cos, sin, position_ids, kv.slots, k_pool, v_pool, H, Hkv, D)
+            return fused(hidden_states, rope_w, lin.bias, cos, sin, position_ids, kv.slots, k_pool, v_pool, H, Hkv, D,
+                         **kv.cache.kv8_kwargs(layer_id))
         # [T, (H + 2 Hkv) D]; at decode sizes the split-K sum of the GPTQ GEMM is finished inside the rope kernel
         qkv = self.query_key_value(hidden_states, partial=True)
         if kv.fresh_prefill and not isinstance(qkv, native.Partial):
             return native.rope_kv_write_prefill(qkv, cos, sin, position_ids, cu_seqlens_q, kv.block_tables, k_pool, v_pool,
-                                                kv.max_q_len, H, Hkv, D, D)
-        return native.rope_kv_write(qkv, cos, sin, position_ids, kv.slots, k_pool, v_pool, H, Hkv, D, D)
+                                                kv.max_q_len, H, Hkv, D, D, **kv.cache.kv8_kwargs(layer_id))
+        return native.rope_kv_write(qkv, cos, sin, position_ids, kv.slots, k_pool, v_pool, H, Hkv, D, D,
+                                    **kv.cache.kv8_kwargs(layer_id))
 
     def attend(self, qkv, cu_seqlens_q, layer_id: int, kv: KVArgs):
         """Attention of the rotated q over the layer's cache pages (reference :271-295): [T, H D]."""
@@ -175,7 +177,8 @@ class FlashLlamaAttention:
             ws = workspace(qkv.device)
             ws.ensure(native.attn_workspace_bytes(T, H, Hkv, D, kv.num_splits))
         native.attn_paged(qkv, qkv.stride(0), k_pool, v_pool, kv.block_tables, kv.ctx_lens, cu_seqlens_q,
-                          attn_output, B, H, Hkv, D, kv.max_q_len, kv.max_ctx, self.softmax_scale, kv.num_splits, ws)
+                          attn_output, B, H, Hkv, D, kv.max_q_len, kv.max_ctx, self.softmax_scale, kv.num_splits, ws,
+                          **kv.cache.kv8_kwargs(layer_id))
         return attn_output
 
     def forward(self, hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id: int, kv: KVArgs):

@@ -157,13 +157,15 @@ class FlashNeoxAttention:
     def forward(self, hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id: int, kv: KVArgs, partial: bool):
         H, D = self.num_heads, self.head_size
         k_pool, v_pool = kv.cache.k_pool(layer_id), kv.cache.v_pool(layer_id)
+        kv8 = kv.cache.kv8_kwargs(layer_id)  # the scales of a one-byte cache (none for a 16-bit one)
         # [T, 3 H D]; at decode sizes the split-K sum (and the bias) is finished inside the rotary + cache-write kernel
         qkv = self.query_key_value(hidden_states, partial=True)
         if kv.fresh_prefill and not isinstance(qkv, native.Partial):
             qkv = native.rope_kv_write_prefill(qkv, cos, sin, position_ids, cu_seqlens_q, kv.block_tables, k_pool,
-                                               v_pool, kv.max_q_len, H, H, D, self.rot_dim)
+                                               v_pool, kv.max_q_len, H, H, D, self.rot_dim, **kv8)
         else:
-            qkv = native.rope_kv_write(qkv, cos, sin, position_ids, kv.slots, k_pool, v_pool, H, H, D, self.rot_dim)
+            qkv = native.rope_kv_write(qkv, cos, sin, position_ids, kv.slots, k_pool, v_pool, H, H, D, self.rot_dim,
+                                       **kv8)
         T = qkv.shape[0]
         attn_output = torch.empty((T, H * D), dtype=qkv.dtype, device=qkv.device)
         ws = None
@@ -173,7 +175,7 @@ class FlashNeoxAttention:
             ws.ensure(native.attn_workspace_bytes(T, H, H, D, kv.num_splits))
         native.attn_paged(qkv, qkv.stride(0), k_pool, v_pool, kv.block_tables, kv.ctx_lens, cu_seqlens_q, attn_output,
                           kv.block_tables.shape[0], H, H, D, kv.max_q_len, kv.max_ctx, self.softmax_scale, kv.num_splits,
-                          ws)
+                          ws, **kv8)
         return self.dense(attn_output, partial=partial)
 
     __call__ = forward

@@ -128,11 +128,13 @@ class FlashMQAttention:
         # the cache-write kernel below (native.Partial)
         qkv = self.c_attn(hidden_states, partial=True)
         k_pool, v_pool = kv.cache.k_pool(layer_id), kv.cache.v_pool(layer_id)
+        kv8 = kv.cache.kv8_kwargs(layer_id)  # the scales of a one-byte cache (none for a 16-bit one)
         if kv.fresh_prefill and not isinstance(qkv, native.Partial):
             qkv = native.rope_kv_write_prefill(qkv, None, None, None, cu_seqlens_q, kv.block_tables, k_pool, v_pool,
-                                               kv.max_q_len, H, 1, D, D)  # no rotary: page-wise cache write only
+                                               kv.max_q_len, H, 1, D, D, **kv8)  # no rotary: page-wise write only
         else:
-            qkv = native.rope_kv_write(qkv, None, None, None, kv.slots, k_pool, v_pool, H, 1, D, D)  # no rotary
+            qkv = native.rope_kv_write(qkv, None, None, None, kv.slots, k_pool, v_pool, H, 1, D, D,
+                                       **kv8)  # no rotary
         T = qkv.shape[0]
         attn_output = torch.empty((T, H * D), dtype=qkv.dtype, device=qkv.device)
         ws = None
@@ -141,7 +143,7 @@ class FlashMQAttention:
             ws.ensure(native.attn_workspace_bytes(T, H, 1, D, kv.num_splits))
         native.attn_paged(qkv, qkv.stride(0), k_pool, v_pool, kv.block_tables, kv.ctx_lens, cu_seqlens_q,
                           attn_output, kv.block_tables.shape[0], H, 1, D, kv.max_q_len, kv.max_ctx,
-                          self.softmax_scale, kv.num_splits, ws)
+                          self.softmax_scale, kv.num_splits, ws, **kv8)
         return self.c_proj(attn_output, partial=True)  # summed by the following add + LayerNorm
 
     __call__ = forward

@@ -31,7 +31,8 @@ from tgis_amd.models.model import Model
 from tgis_amd.models.types import Batch, GenerateError
 from tgis_amd.pb import generate_pb2
 from tgis_amd.utils.graph_segments import SegmentedGraph, no_gc_during_capture
-from tgis_amd.utils.kv_cache import PAGE, PagedKVCache
+from tgis_amd.utils.kv_cache import (KV_CACHE_DTYPES, PAGE, PagedKVCache, kv_pool_dtype, pages_for_budget,
+                                     parse_kv_cache_dtype)
 from tgis_amd.utils.token_types import InputTokens, TokenInfo
 from tgis_amd.utils.tokens import HeterogeneousNextTokenChooser, get_input_tokens_info, get_token_info
 
@@ -444,7 +445,18 @@ class _DecodeGraph:
 class FlashCausalLM(Model):
     def __init__(self, model_name: str, revision: Optional[str], deployment_framework: str, dtype: torch.dtype,
                  quantize: Optional[str], model_config: Union[Any] = None, auto_model_class=None,
-                 max_sequence_length: Optional[int] = None, engine=None, kv_cache_pages: Optional[int] = None):
+                 max_sequence_length: Optional[int] = None, engine=None, kv_cache_pages: Optional[int] = None,
+                 kv_cache_dtype: Optional[str] = None):
+        # KV cache element: "auto" (the model dtype) or "fp8_e4m3" (one byte, utils/kv_cache.py); None reads
+        # TGIS_KV_CACHE_DTYPE.  Checked before anything is loaded — except on a rank of a tensor-parallel group, which first
+        # tells its peers (_check_same_kv_dtype) so that they fail with it instead of waiting in that collective.
+        self._kv_dtype_error = None
+        try:
+            self.kv_cache_dtype = parse_kv_cache_dtype(kv_cache_dtype)
+        except ValueError as e:
+            if (getattr(engine, "world_size", 1) or 1) == 1:
+                raise
+            self.kv_cache_dtype, self._kv_dtype_error = None, e
         if not torch.cuda.is_available():
             raise NotImplementedError("FlashCausalLM is only available on GPU")
         if engine is None:
@@ -475,6 +487,9 @@ class FlashCausalLM(Model):
         self.num_layers = len(inner.layers)
         if hasattr(self.model, "post_init"):
             self.model.post_init()
+        # Tensor parallel: every rank reads and writes its shard of the same layers' pages with the same kernels — a rank
+        # whose environment asked for another cache dtype is a configuration error, raised here rather than served.
+        self._check_same_kv_dtype(engine)
         if kv_cache_pages is None:
             kv_cache_pages = self._default_kv_pages()
         # Tensor parallel: every rank must hold the SAME number of pages.  Each rank sizes its pool from its own free
@@ -483,7 +498,7 @@ class FlashCausalLM(Model):
         # reports to the router would differ from its peers'.  The smallest pool decides.
         kv_cache_pages = self._agree_on_min(kv_cache_pages, engine)
         self.kv_cache = PagedKVCache(self.num_layers, self.num_kv_heads, self.head_size, kv_cache_pages, dtype,
-                                     self.device)
+                                     self.device, kv_dtype=self.kv_cache_dtype)
         # tp > 1, TGIS_TP_GRAPHS = auto (default) | full | segments | false:
         #   full      one graph per step with the RCCL all-reduces / all-gather inside it (RCCL is capture-aware);
         #   segments  a chain of graphs with the collectives launched between them (utils/graph_segments.py);
@@ -578,11 +593,27 @@ class FlashCausalLM(Model):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MIN, group=pg)
         return int(t.item())
 
+    def _check_same_kv_dtype(self, engine):
+        world = engine.world_size if hasattr(engine, "world_size") else 1
+        if world == 1:
+            return
+        # (-1: this rank's value was not a KV cache dtype at all)
+        code = -1 if self._kv_dtype_error is not None else KV_CACHE_DTYPES.index(self.kv_cache_dtype)
+        lo, hi = self._agree_on_min(code, engine), -self._agree_on_min(-code, engine)
+        if self._kv_dtype_error is not None:
+            raise self._kv_dtype_error
+        if lo < 0:
+            raise ValueError("another tensor-parallel rank was given an unsupported KV cache dtype (TGIS_KV_CACHE_DTYPE)")
+        if lo != hi:
+            raise ValueError(f"tensor-parallel ranks disagree on the KV cache dtype (this rank: {self.kv_cache_dtype}; "
+                             f"ranks use {KV_CACHE_DTYPES[lo]} and {KV_CACHE_DTYPES[hi]}): set TGIS_KV_CACHE_DTYPE alike "
+                             f"on every rank")
+
     def _default_kv_pages(self) -> int:
         free, _total = torch.cuda.mem_get_info(self.device)
         frac = float(os.getenv("TGIS_KV_CACHE_FRACTION", "0.85"))
-        per_page = self.num_layers * 2 * self.num_kv_heads * PAGE * self.head_size * 2
-        return max(64, int(free * frac) // per_page)
+        elem = torch.empty((), dtype=kv_pool_dtype(self.kv_cache_dtype, self.dtype)).element_size()
+        return pages_for_budget(int(free * frac), self.num_layers, self.num_kv_heads, self.head_size, elem)
 
     @property
     def batch_type(self) -> Type[FlashCausalLMBatch]:

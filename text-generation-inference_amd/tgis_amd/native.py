@@ -24,6 +24,7 @@ _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int
 _c_f = ctypes.c_float
 _vp = ctypes.c_void_p
+_KV8_ARGS = [_c_int, _c_f, _c_f]  # kv_dtype, k_scale, v_scale appended by the *_kv8 entry points
 
 
 
@@ -49,11 +50,15 @@ SIGNATURES = {
     "tgis_gptq_dequant_f16": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _vp]),
     "tgis_dense_gemm_rope": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64, _c_i64,
                                       _c_i64, _c_i64, _c_i64, _c_int, _vp]),
+    "tgis_dense_gemm_rope_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64,
+                                          _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp] + _KV8_ARGS),
     "tgis_gptq_rope_ok": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_i64]),
     "tgis_gptq_fragments_ok": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int]),
     "tgis_dense_rope_ok": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64]),
     "tgis_gptq_gemm_rope_f16": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64,
                                          _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _vp]),
+    "tgis_gptq_gemm_rope_f16_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64,
+                                             _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _vp] + _KV8_ARGS),
     "tgis_dense_prepared_bytes": (_c_i64, [_c_i64, _c_i64]),
     "tgis_dense_prepare": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp]),
     "tgis_dense_gemm_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
@@ -78,10 +83,18 @@ SIGNATURES = {
                                             _c_int, _c_int, _c_int, _c_int, _c_int, _vp]),
     "tgis_rope_kv_write_prefill": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64, _c_i64,
                                             _c_int, _c_int, _c_int, _c_int, _c_int, _vp]),
+    "tgis_rope_kv_write_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_int, _c_int, _c_int,
+                                        _c_int, _c_int, _vp] + _KV8_ARGS),
+    "tgis_rope_kv_write_partial_kv8": (_c_int, [_vp, _c_int, _c_i64, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64,
+                                                _c_int, _c_int, _c_int, _c_int, _c_int, _vp] + _KV8_ARGS),
+    "tgis_rope_kv_write_prefill_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64,
+                                                _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _vp] + _KV8_ARGS),
     "tgis_attn_num_splits": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _c_i64]),
     "tgis_attn_workspace_bytes": (_c_i64, [_c_i64, _c_int, _c_int, _c_int, _c_int]),
     "tgis_attn_paged": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int,
                                  _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_int, _vp, _c_i64, _vp]),
+    "tgis_attn_paged_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int,
+                                     _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_int, _vp, _c_i64, _vp] + _KV8_ARGS),
     "tgis_act_mul": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _c_int, _vp]),
     "tgis_gelu": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_int, _vp]),
     "tgis_embedding": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp]),
@@ -124,6 +137,16 @@ def _check(rc: int, what: str):
     if rc != 0:
         msg = load_library().tgis_last_error().decode()
         raise TgisHipError(f"{what} failed (code {rc}): {msg}")
+
+
+# KV cache element codes of the *_kv8 entry points (TGIS_KV_* in tgis_hip.h)
+KV_MODEL, KV_FP8_E4M3 = 0, 1
+KV8_DTYPES = (torch.uint8, torch.float8_e4m3fn)  # a one-byte pool holds e4m3 codes; torch may see them as either
+
+
+def kv_is8(pool: Optional[torch.Tensor]) -> bool:
+    """Whether a KV pool holds one-byte (e4m3) codes: its writers and readers then take the *_kv8 entry points."""
+    return pool is not None and pool.dtype in KV8_DTYPES
 
 
 def dtype_code(dt: torch.dtype) -> int:
@@ -413,10 +436,11 @@ def rope_gemm_ok(M: int, w, D: int) -> bool:
 
 
 def gptq_gemm_rope(x: torch.Tensor, w: GptqWeight, bias, cos, sin, positions, slots, k_pool, v_pool, H: int, Hkv: int,
-                   D: int, out=None) -> torch.Tensor:
+                   D: int, out=None, kv_scales=(1.0, 1.0)) -> torch.Tensor:
     """qkv projection + rotary embedding + cache write in one launch (decode, M <= 64; `w` is the rope image of the fused
     qkv weight).  Returns a [M, (H + 2 Hkv) D] tensor whose first H D columns hold the rotated q (the k / v columns are not
-    written: they went straight into their cache pages)."""
+    written: they went straight into their cache pages).  One-byte pools (kv_is8) take tgis_gptq_gemm_rope_f16_kv8 with
+    kv_scales = (k_scale, v_scale)."""
     if isinstance(x, FragAct):
         assert x.K == w.K
         M, xp, ldx = x.M, _ptr(x.buf), LD_FRAGMENTS
@@ -428,11 +452,13 @@ def gptq_gemm_rope(x: torch.Tensor, w: GptqWeight, bias, cos, sin, positions, sl
     assert cos.shape[1] * 2 == D, "the fused epilogue covers the full rotary span only"
     if out is None:
         out = torch.empty((M, w.N), dtype=torch.float16, device=x.device)
-    _check(
-        load_library().tgis_gptq_gemm_rope_f16(xp, ldx, _ptr(w.image), _ptr(bias), _ptr(positions), _ptr(slots),
-                                               _ptr(cos), _ptr(sin), _ptr(out), out.stride(0), _ptr(k_pool), _ptr(v_pool),
-                                               M, w.K, w.N, w.groups, H, Hkv, D, _stream()),
-        "tgis_gptq_gemm_rope_f16")
+    args = (xp, ldx, _ptr(w.image), _ptr(bias), _ptr(positions), _ptr(slots), _ptr(cos), _ptr(sin), _ptr(out),
+            out.stride(0), _ptr(k_pool), _ptr(v_pool), M, w.K, w.N, w.groups, H, Hkv, D, _stream())
+    if kv_is8(k_pool):
+        _check(load_library().tgis_gptq_gemm_rope_f16_kv8(*args, *_kv8_args(k_pool, v_pool, kv_scales)),
+               "tgis_gptq_gemm_rope_f16_kv8")
+    else:
+        _check(load_library().tgis_gptq_gemm_rope_f16(*args), "tgis_gptq_gemm_rope_f16")
     return out
 
 
@@ -504,20 +530,23 @@ def dense_gemm_partial(x: torch.Tensor, w: DenseWeight, bias=None, act: int = 0)
 
 
 def dense_gemm_rope(x: torch.Tensor, w: DenseWeight, bias, cos, sin, positions, slots, k_pool, v_pool, H: int, Hkv: int,
-                    D: int, out=None) -> torch.Tensor:
+                    D: int, out=None, kv_scales=(1.0, 1.0)) -> torch.Tensor:
     """Dense qkv projection + rotary embedding + cache write in one launch (decode, M <= 64; `w` is the rope image of the
-    fused qkv weight).  Returns [M, (H + 2 Hkv) D] whose first H D columns hold the rotated q."""
+    fused qkv weight).  Returns [M, (H + 2 Hkv) D] whose first H D columns hold the rotated q.  One-byte pools: as
+    gptq_gemm_rope."""
     assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == w.dtype and x.shape[1] == w.K
     assert w.flags & 2 and w.N == (H + 2 * Hkv) * D and cos.dtype == w.dtype and cos.shape[1] * 2 == D
     assert positions.dtype == torch.int32 and slots.dtype == torch.int32
     M = x.shape[0]
     if out is None:
         out = torch.empty((M, w.N), dtype=w.dtype, device=x.device)
-    _check(
-        load_library().tgis_dense_gemm_rope(_ptr(x), x.stride(0), _ptr(w.image), _ptr(bias), _ptr(positions), _ptr(slots),
-                                            _ptr(cos), _ptr(sin), _ptr(out), out.stride(0), _ptr(k_pool), _ptr(v_pool), M,
-                                            w.K, w.N, H, Hkv, D, dtype_code(w.dtype), _stream()),
-        "tgis_dense_gemm_rope")
+    args = (_ptr(x), x.stride(0), _ptr(w.image), _ptr(bias), _ptr(positions), _ptr(slots), _ptr(cos), _ptr(sin),
+            _ptr(out), out.stride(0), _ptr(k_pool), _ptr(v_pool), M, w.K, w.N, H, Hkv, D, dtype_code(w.dtype), _stream())
+    if kv_is8(k_pool):
+        _check(load_library().tgis_dense_gemm_rope_kv8(*args, *_kv8_args(k_pool, v_pool, kv_scales)),
+               "tgis_dense_gemm_rope_kv8")
+    else:
+        _check(load_library().tgis_dense_gemm_rope(*args), "tgis_dense_gemm_rope")
     return out
 
 
@@ -618,38 +647,56 @@ def layernorm2_residual(residual, a, b, w1, b1, eps: float, w2=None, b2=None, re
 
 
 # ---- rope + kv write, attention --------------------------------------------------------------------------
-def rope_kv_write(qkv, cos, sin, positions, slots, k_pool, v_pool, H: int, Hkv: int, D: int, rot_dim: int):
+def _kv8_args(k_pool, v_pool, kv_scales):
+    """(kv_dtype, k_scale, v_scale) of a *_kv8 call on one-byte pools."""
+    assert kv_is8(v_pool) and k_pool.dtype == v_pool.dtype, "k and v pools must both hold e4m3 codes"
+    k_scale, v_scale = (1.0, 1.0) if kv_scales is None else kv_scales
+    return KV_FP8_E4M3, float(k_scale), float(v_scale)
+
+
+def rope_kv_write(qkv, cos, sin, positions, slots, k_pool, v_pool, H: int, Hkv: int, D: int, rot_dim: int,
+                  kv_scales=(1.0, 1.0)):
     """Rotates q,k in place and writes k,v to the cache.  `qkv` may be a Partial: the reduced, rotated activation is
-    then materialised into a fresh [T, (H+2Hkv)D] tensor, which is returned (the plain form returns qkv itself)."""
+    then materialised into a fresh [T, (H+2Hkv)D] tensor, which is returned (the plain form returns qkv itself).
+    One-byte pools (kv_is8) receive e4m3 codes of k / k_scale and v / v_scale, kv_scales = (k_scale, v_scale)."""
+    kv8 = kv_is8(k_pool)
+    lib = load_library()
     if isinstance(qkv, Partial):
         T = qkv.M
         out = torch.empty((T, qkv.N), dtype=qkv.dtype, device=qkv.device)
-        _check(
-            load_library().tgis_rope_kv_write_partial(_ptr(qkv.slabs), qkv.S, qkv.ld, _ptr(qkv.bias), _ptr(out),
-                                                      out.stride(0), _ptr(cos), _ptr(sin), _ptr(positions),
-                                                      _ptr(slots), _ptr(k_pool), _ptr(v_pool), T, H, Hkv, D, rot_dim,
-                                                      dtype_code(out.dtype), _stream()), "tgis_rope_kv_write_partial")
+        args = (_ptr(qkv.slabs), qkv.S, qkv.ld, _ptr(qkv.bias), _ptr(out), out.stride(0), _ptr(cos), _ptr(sin),
+                _ptr(positions), _ptr(slots), _ptr(k_pool), _ptr(v_pool), T, H, Hkv, D, rot_dim, dtype_code(out.dtype),
+                _stream())
+        if kv8:
+            _check(lib.tgis_rope_kv_write_partial_kv8(*args, *_kv8_args(k_pool, v_pool, kv_scales)),
+                   "tgis_rope_kv_write_partial_kv8")
+        else:
+            _check(lib.tgis_rope_kv_write_partial(*args), "tgis_rope_kv_write_partial")
         return out
     assert qkv.dim() == 2 and qkv.stride(1) == 1
     T = qkv.shape[0]
-    _check(
-        load_library().tgis_rope_kv_write(_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(positions),
-                                          _ptr(slots), _ptr(k_pool), _ptr(v_pool), T, H, Hkv, D, rot_dim,
-                                          dtype_code(qkv.dtype), _stream()), "tgis_rope_kv_write")
+    args = (_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(positions), _ptr(slots), _ptr(k_pool), _ptr(v_pool), T,
+            H, Hkv, D, rot_dim, dtype_code(qkv.dtype), _stream())
+    if kv8:
+        _check(lib.tgis_rope_kv_write_kv8(*args, *_kv8_args(k_pool, v_pool, kv_scales)), "tgis_rope_kv_write_kv8")
+    else:
+        _check(lib.tgis_rope_kv_write(*args), "tgis_rope_kv_write")
     return qkv
 
 
 def rope_kv_write_prefill(qkv, cos, sin, positions, cu_seqlens, block_tables, k_pool, v_pool, max_len: int, H: int,
-                          Hkv: int, D: int, rot_dim: int):
+                          Hkv: int, D: int, rot_dim: int, kv_scales=(1.0, 1.0)):
     """rope_kv_write for a fresh prefill (token i of a sequence = cache position i): page-wise cache writes."""
     assert qkv.dim() == 2 and qkv.stride(1) == 1 and block_tables.is_contiguous()
     B = block_tables.shape[0]
-    _check(
-        load_library().tgis_rope_kv_write_prefill(_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(positions),
-                                                  _ptr(cu_seqlens), _ptr(block_tables), block_tables.shape[1],
-                                                  _ptr(k_pool), _ptr(v_pool), B, qkv.shape[0], max_len, H, Hkv, D,
-                                                  rot_dim, dtype_code(qkv.dtype), _stream()),
-        "tgis_rope_kv_write_prefill")
+    args = (_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(positions), _ptr(cu_seqlens), _ptr(block_tables),
+            block_tables.shape[1], _ptr(k_pool), _ptr(v_pool), B, qkv.shape[0], max_len, H, Hkv, D, rot_dim,
+            dtype_code(qkv.dtype), _stream())
+    if kv_is8(k_pool):
+        _check(load_library().tgis_rope_kv_write_prefill_kv8(*args, *_kv8_args(k_pool, v_pool, kv_scales)),
+               "tgis_rope_kv_write_prefill_kv8")
+    else:
+        _check(load_library().tgis_rope_kv_write_prefill(*args), "tgis_rope_kv_write_prefill")
     return qkv
 
 
@@ -662,9 +709,11 @@ def attn_workspace_bytes(total_q: int, H: int, Hkv: int, D: int, num_splits: int
 
 
 def attn_paged(q, ld_q: int, k_pool, v_pool, block_tables, ctx_lens, cu_seqlens_q, out, B: int, H: int, Hkv: int,
-               D: int, max_q_len: int, max_ctx: int, scale: float, num_splits: int, ws: Optional[Workspace]):
+               D: int, max_q_len: int, max_ctx: int, scale: float, num_splits: int, ws: Optional[Workspace],
+               kv_scales=(1.0, 1.0)):
     """q is a (view into a) [T, *] activation whose row stride is ld_q elements; out [T, H*D], or (decode, B <= 32) a
-    FragAct of that shape for the o_proj GEMM."""
+    FragAct of that shape for the o_proj GEMM.  One-byte pools (kv_is8) are read as k_scale * e4m3(k), v_scale * e4m3(v)
+    (tgis_attn_paged_kv8), kv_scales = (k_scale, v_scale)."""
     assert block_tables.dtype == torch.int32 and ctx_lens.dtype == torch.int32 and cu_seqlens_q.dtype == torch.int32
     assert block_tables.is_contiguous()
     if isinstance(out, FragAct):
@@ -674,11 +723,13 @@ def attn_paged(q, ld_q: int, k_pool, v_pool, block_tables, ctx_lens, cu_seqlens_
         assert out.is_contiguous()
         optr, ldo = _ptr(out), H * D
     wptr, wbytes = (ws.ptr, ws.nbytes) if ws is not None else (None, 0)
-    _check(
-        load_library().tgis_attn_paged(_ptr(q), ld_q, _ptr(k_pool), _ptr(v_pool), _ptr(block_tables),
-                                       block_tables.shape[1], _ptr(ctx_lens), _ptr(cu_seqlens_q), optr, ldo, B, H,
-                                       Hkv, D, max_q_len, max_ctx, float(scale), dtype_code(q.dtype), num_splits,
-                                       wptr, wbytes, _stream()), "tgis_attn_paged")
+    args = (_ptr(q), ld_q, _ptr(k_pool), _ptr(v_pool), _ptr(block_tables), block_tables.shape[1], _ptr(ctx_lens),
+            _ptr(cu_seqlens_q), optr, ldo, B, H, Hkv, D, max_q_len, max_ctx, float(scale), dtype_code(q.dtype), num_splits,
+            wptr, wbytes, _stream())
+    if kv_is8(k_pool):
+        _check(load_library().tgis_attn_paged_kv8(*args, *_kv8_args(k_pool, v_pool, kv_scales)), "tgis_attn_paged_kv8")
+    else:
+        _check(load_library().tgis_attn_paged(*args), "tgis_attn_paged")
     return out
 
 

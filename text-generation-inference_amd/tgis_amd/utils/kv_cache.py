@@ -18,13 +18,48 @@ pristine pool — lowest-id-first dealing over the holes of an aged pool is stil
 (one heap per page-id residue class, page p of sequence b from class (b + p) mod C — VERDICT r05 item 2a) was built and
 measured on aged pools for C = 2 .. 128 at five shapes: never better than this one, 1-4 % worse for several C
 (profiles/r06_page_classes.log; the allocator lives on in tools/attn_page_order.py), so it is not here.
+
+KV cache dtype (opt-in, `kv_dtype="fp8_e4m3"` / TGIS_KV_CACHE_DTYPE): the pool holds one byte per element, OCP float8_e4m3fn
+codes of x / k_scale and x / v_scale (csrc/kv_layout.h) in a torch.uint8 tensor of the same shape — half the
+bytes per page, so twice the pages for the same memory.  The scales are one float per layer for k and one for v (1.0 until a
+calibrated checkpoint supplies others); the native calls take them with `kv_scales=cache.scales(layer)`.
 """
 import heapq
-from typing import List
+import os
+from typing import List, Optional, Tuple
 
 import torch
 
 PAGE = 32
+
+# TGIS_KV_CACHE_DTYPE / kv_cache_dtype values: "auto" = the model dtype
+KV_CACHE_DTYPES = ("auto", "fp8_e4m3")
+
+
+def parse_kv_cache_dtype(value: Optional[str] = None) -> str:
+    """The KV cache dtype name: `value`, or TGIS_KV_CACHE_DTYPE when it is None (unset: "auto").  Raises on anything else."""
+    if value is None:
+        value = os.getenv("TGIS_KV_CACHE_DTYPE", "auto")
+    name = str(value).strip().lower()
+    if name not in KV_CACHE_DTYPES:
+        raise ValueError(f"KV cache dtype {value!r} is not supported (one of {', '.join(KV_CACHE_DTYPES)})")
+    return name
+
+
+def kv_pool_dtype(kv_dtype: str, model_dtype: torch.dtype) -> torch.dtype:
+    """Element type of the pool tensor: the model dtype, or uint8 holding e4m3 codes."""
+    return torch.uint8 if parse_kv_cache_dtype(kv_dtype) == "fp8_e4m3" else model_dtype
+
+
+def kv_bytes_per_page(num_layers: int, num_kv_heads: int, head_dim: int, elem_bytes: int) -> int:
+    """Bytes of one page across every layer, k and v."""
+    return num_layers * 2 * num_kv_heads * PAGE * head_dim * elem_bytes
+
+
+def pages_for_budget(budget_bytes: int, num_layers: int, num_kv_heads: int, head_dim: int, elem_bytes: int,
+                     min_pages: int = 64) -> int:
+    """How many pages a pool of `elem_bytes`-byte elements gets out of `budget_bytes` (at least `min_pages`)."""
+    return max(min_pages, int(budget_bytes) // kv_bytes_per_page(num_layers, num_kv_heads, head_dim, elem_bytes))
 
 
 class OutOfPages(RuntimeError):
@@ -32,9 +67,15 @@ class OutOfPages(RuntimeError):
 
 
 class PagedKVCache:
-    def __init__(self, num_layers: int, num_kv_heads: int, head_dim: int, num_pages: int, dtype, device):
+    def __init__(self, num_layers: int, num_kv_heads: int, head_dim: int, num_pages: int, dtype, device,
+                 kv_dtype: str = "auto"):
         self.num_layers, self.num_kv_heads, self.head_dim = num_layers, num_kv_heads, head_dim
         self.num_pages = num_pages
+        self.kv_dtype = parse_kv_cache_dtype(kv_dtype)
+        dtype = kv_pool_dtype(self.kv_dtype, dtype)
+        # per-layer dequantisation scales of a one-byte cache (k, v); 1.0: no calibration yet
+        self.k_scales = [1.0] * num_layers
+        self.v_scales = [1.0] * num_layers
         # zero-initialised, and every value a kernel ever writes into it is finite: masked slots of a page (the unwritten tail
         # of the page a sequence is filling, stale tokens of a page's previous owner) are multiplied by P = 0 and must never
         # hold NaN / Inf patterns (tests/test_ops_gpu.py::test_attention_decode_every_fill_of_the_last_page runs over stale
@@ -50,6 +91,19 @@ class PagedKVCache:
 
     def bytes_per_token(self) -> int:
         return self.num_layers * 2 * self.num_kv_heads * self.head_dim * self.pool.element_size()
+
+    @property
+    def is_fp8(self) -> bool:
+        return self.kv_dtype == "fp8_e4m3"
+
+    def scales(self, layer: int) -> Tuple[float, float]:
+        """(k_scale, v_scale) of a layer: a one-byte pool holds e4m3(k / k_scale), e4m3(v / v_scale)."""
+        return self.k_scales[layer], self.v_scales[layer]
+
+    def kv8_kwargs(self, layer: int) -> dict:
+        """Keyword arguments of the native cache writers / attention for this layer: the scales of a one-byte pool, nothing
+        for a 16-bit one (whose calls stay exactly what they were)."""
+        return {"kv_scales": self.scales(layer)} if self.is_fp8 else {}
 
     def k_pool(self, layer: int) -> torch.Tensor:
         return self.pool[layer, 0]
