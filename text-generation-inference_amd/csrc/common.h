@@ -38,6 +38,14 @@ void tgis_set_error(const char* fmt, ...);
         }                                                                                 \
     } while (0)
 #define TGIS_CHECK_LAUNCH() TGIS_CHECK_HIP(hipGetLastError())
+// The cache dtype and scales of a *_kv8 entry point; `fn` is its name, a string literal.
+#define TGIS_CHECK_KV_ARGS(fn, kv_dtype, k_scale, v_scale)                                                              \
+    do {                                                                                                                \
+        TGIS_CHECK_ARG((kv_dtype) == TGIS_KV_MODEL || (kv_dtype) == TGIS_KV_FP8_E4M3, fn ": bad kv_dtype %d", (kv_dtype)); \
+        TGIS_CHECK_ARG((kv_dtype) == TGIS_KV_MODEL ||                                                                   \
+                           ((k_scale) > 0.f && (v_scale) > 0.f && (k_scale) < INFINITY && (v_scale) < INFINITY),        \
+                       fn ": k_scale and v_scale must be positive and finite");                                         \
+    } while (0)
 
 // Optional event timing around an op's launches (see tgis_timing_* in tgis_hip.h).
 struct TgisTimedScope {

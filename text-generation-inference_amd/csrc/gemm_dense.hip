@@ -297,10 +297,7 @@ static int dense_gemm_rope_impl(const void* x, int64_t ldx, const void* prepared
                    "that is a multiple of 32 (M=%ld D=%ld)", (long)M, (long)D);
     TGIS_CHECK_ARG(H >= 1 && Hkv >= 1 && (H + 2 * Hkv) * D == N && ldq >= H * D,
                    "tgis_dense_gemm_rope: N must be (H + 2 Hkv) * D and q rows must hold H * D elements");
-    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || kv_dtype == TGIS_KV_FP8_E4M3, "tgis_dense_gemm_rope_kv8: bad kv_dtype %d",
-                   kv_dtype);
-    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || (k_scale > 0.f && v_scale > 0.f && k_scale < INFINITY && v_scale < INFINITY),
-                   "tgis_dense_gemm_rope_kv8: k_scale and v_scale must be positive and finite");
+    TGIS_CHECK_KV_ARGS("tgis_dense_gemm_rope_kv8", kv_dtype, k_scale, v_scale);
     const bool kv8 = kv_dtype == TGIS_KV_FP8_E4M3;
     hipStream_t st = (hipStream_t)stream;
     const DensePlan pl = choose_dense(2, M, K, N, 3);  // as the SiLU epilogue: the whole k range in one block (S == 1)

@@ -932,10 +932,7 @@ static int gptq_gemm_rope_impl(const void* x, int64_t ldx, const void* prepared,
                    "that is a multiple of 32 (M=%ld K=%ld groups=%ld D=%ld)", (long)M, (long)K, (long)groups, (long)D);
     TGIS_CHECK_ARG(H >= 1 && Hkv >= 1 && (H + 2 * Hkv) * D == N && ldq >= H * D,
                    "tgis_gptq_gemm_rope_f16: N must be (H + 2 Hkv) * D and q rows must hold H * D elements");
-    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || kv_dtype == TGIS_KV_FP8_E4M3, "tgis_gptq_gemm_rope_f16_kv8: bad kv_dtype %d",
-                   kv_dtype);
-    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || (k_scale > 0.f && v_scale > 0.f && k_scale < INFINITY && v_scale < INFINITY),
-                   "tgis_gptq_gemm_rope_f16_kv8: k_scale and v_scale must be positive and finite");
+    TGIS_CHECK_KV_ARGS("tgis_gptq_gemm_rope_f16_kv8", kv_dtype, k_scale, v_scale);
     const bool kv8 = kv_dtype == TGIS_KV_FP8_E4M3;
     const GptqLaunch c = choose_gptq(ENTRY_ROPE, M, K, N, groups, 3, false, ldx == TGIS_LD_FRAGMENTS);
     RopeEpi rope{positions, slots, (const f16*)cos, (const f16*)sin, (f16*)k_pool, (f16*)v_pool, (int)H, (int)Hkv, (int)D,

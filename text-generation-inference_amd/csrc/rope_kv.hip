@@ -251,10 +251,7 @@ static int rope_launch(void* qkv, int64_t ld_qkv, const void* cos, const void* s
                    "tgis_rope_kv_write: rot_dim must be even and <= head_dim");
     TGIS_CHECK_ARG((!k_pool && !v_pool) || slots, "tgis_rope_kv_write: cache write needs slots");
     TGIS_CHECK_ARG(dtype == TGIS_F16 || dtype == TGIS_BF16, "tgis_rope_kv_write: bad dtype");
-    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || kv_dtype == TGIS_KV_FP8_E4M3, "tgis_rope_kv_write_kv8: bad kv_dtype %d",
-                   kv_dtype);
-    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || (k_scale > 0.f && v_scale > 0.f && k_scale < INFINITY && v_scale < INFINITY),
-                   "tgis_rope_kv_write_kv8: k_scale and v_scale must be positive and finite");
+    TGIS_CHECK_KV_ARGS("tgis_rope_kv_write_kv8", kv_dtype, k_scale, v_scale);
     TGIS_CHECK_ARG(!slabs || (S >= 1 && slab_ld >= (int64_t)(H + 2 * Hkv) * D && slab_ld % 4 == 0),
                    "tgis_rope_kv_write_partial: needs a slab row stride >= (H + 2 Hkv) D");
     if (T == 0) return TGIS_OK;
@@ -330,10 +327,7 @@ static int rope_prefill_launch(void* qkv, int64_t ld_qkv, const void* cos, const
     TGIS_CHECK_ARG(!cos || (positions && rot_dim > 0 && rot_dim <= D && rot_dim % 2 == 0),
                    "tgis_rope_kv_write_prefill: rot_dim must be even and <= head_dim");
     TGIS_CHECK_ARG(dtype == TGIS_F16 || dtype == TGIS_BF16, "tgis_rope_kv_write_prefill: bad dtype");
-    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || kv_dtype == TGIS_KV_FP8_E4M3, "tgis_rope_kv_write_prefill_kv8: bad kv_dtype %d",
-                   kv_dtype);
-    TGIS_CHECK_ARG(kv_dtype == TGIS_KV_MODEL || (k_scale > 0.f && v_scale > 0.f && k_scale < INFINITY && v_scale < INFINITY),
-                   "tgis_rope_kv_write_prefill_kv8: k_scale and v_scale must be positive and finite");
+    TGIS_CHECK_KV_ARGS("tgis_rope_kv_write_prefill_kv8", kv_dtype, k_scale, v_scale);
     if (B == 0 || T == 0) return TGIS_OK;
     // q heads: rotated in place by the per-token kernel (no cache traffic: Hkv = 0, no pools)
     int rc = rope_launch(qkv, ld_qkv, cos, sin, positions, nullptr, nullptr, nullptr, T, H, 0, D, rot_dim, dtype, stream,

@@ -32,10 +32,8 @@ def model_class_for(config):
 
         return FlashLlamaForCausalLM, aliases
     if model_type == "gpt_bigcode":
-        try:
-            from tgis_amd.models.custom_modeling.flash_santacoder_modeling import FlashSantacoderForCausalLM
-        except ImportError as e:
-            raise NotImplementedError("gpt_bigcode (Santacoder/Starcoder) is not built yet in this round") from e
+        from tgis_amd.models.custom_modeling.flash_santacoder_modeling import FlashSantacoderForCausalLM
+
         config.transpose = config.architectures[0].startswith("GPT2")
         return FlashSantacoderForCausalLM, {"transformer.wte.weight": ["lm_head.weight"]}
     if model_type == "gpt_neox":

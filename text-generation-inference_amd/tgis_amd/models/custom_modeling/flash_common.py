@@ -1,0 +1,113 @@
+"""What the Llama, GPT-NeoX and Santacoder forwards share: how a layer writes its keys and values into the paged cache and
+attends over it, the fused add + LayerNorm, the growth rule of the rotary tables and the tail of the `*ForCausalLM` classes.
+
+A change to the cache (another element type, per-head scales, a clamp on write) is made here once; the model files differ
+only in `(H, Hkv, D, rot_dim)` and in whether they rotate at all.  Every `native` function is looked up when it is called:
+tests replace them on the module."""
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from tgis_amd import native
+from tgis_amd.utils.layers import workspace
+
+
+@dataclass
+class KVArgs:
+    """Where this forward's keys/values live in the paged cache."""
+    cache: "object"                    # utils.kv_cache.PagedKVCache
+    block_tables: torch.Tensor         # [B, max_pages] int32 (device)
+    ctx_lens: Optional[torch.Tensor]   # [B] int32, tokens per sequence incl. this forward's (prefill); decode: filled in
+    slots: Optional[torch.Tensor]      # [T] int32 physical slot per token (prefill); decode: filled in
+    max_q_len: int                     # longest q run in this forward (1 for decode)
+    max_ctx: int                       # upper bound of ctx_lens (launch shaping only)
+    num_splits: int = 1                # attention key splits (decode)
+    fresh_prefill: bool = False        # every sequence starts at cache position 0: page-wise cache writes
+
+
+def layer_pools(kv: KVArgs, layer_id: int):
+    """(k_pool, v_pool, keyword arguments) of the native cache writers and readers for one layer: the scales of a one-byte
+    cache; a 16-bit one's calls carry no `kv_scales` keyword at all."""
+    cache = kv.cache
+    scales = {"kv_scales": cache.scales(layer_id)} if cache.is_fp8 else {}
+    return cache.k_pool(layer_id), cache.v_pool(layer_id), scales
+
+
+def write_kv(qkv, kv: KVArgs, layer_id: int, H: int, Hkv: int, D: int, rot_dim: int, cos, sin, position_ids, cu_seqlens_q):
+    """Rotates q and k of `qkv` [T, (H + 2 Hkv) D] (cos is None: no rotary) and scatters k and v to their page slots;
+    returns the activation whose first H D columns attention reads.  A fresh prefill writes page-wise; everything else per
+    token, which at decode sizes also finishes the split-K sum (and the bias) of a `native.Partial`."""
+    k_pool, v_pool, scales = layer_pools(kv, layer_id)
+    if kv.fresh_prefill and not isinstance(qkv, native.Partial):
+        return native.rope_kv_write_prefill(qkv, cos, sin, position_ids, cu_seqlens_q, kv.block_tables, k_pool, v_pool,
+                                            kv.max_q_len, H, Hkv, D, rot_dim, **scales)
+    return native.rope_kv_write(qkv, cos, sin, position_ids, kv.slots, k_pool, v_pool, H, Hkv, D, rot_dim, **scales)
+
+
+def attend(qkv, kv: KVArgs, layer_id: int, H: int, Hkv: int, D: int, scale: float, cu_seqlens_q, frag_out: bool = False):
+    """Attention of the rotated q over the layer's cache pages: [T, H D], in fragment order (native.FragAct) for the int4
+    GEMM behind it when `frag_out`."""
+    k_pool, v_pool, scales = layer_pools(kv, layer_id)
+    T = qkv.shape[0]
+    if frag_out:
+        attn_output = native.FragAct.empty(T, H * D, qkv.device)
+    else:
+        attn_output = torch.empty((T, H * D), dtype=qkv.dtype, device=qkv.device)
+    ws = None
+    if kv.num_splits > 1:
+        ws = workspace(qkv.device)
+        ws.ensure(native.attn_workspace_bytes(T, H, Hkv, D, kv.num_splits))
+    native.attn_paged(qkv, qkv.stride(0), k_pool, v_pool, kv.block_tables, kv.ctx_lens, cu_seqlens_q, attn_output,
+                      kv.block_tables.shape[0], H, Hkv, D, kv.max_q_len, kv.max_ctx, scale, kv.num_splits, ws, **scales)
+    return attn_output
+
+
+class FastLayerNorm:
+    def __init__(self, prefix, weights, eps):
+        self.weight = weights.get_tensor(f"{prefix}.weight").contiguous()
+        self.bias = weights.get_tensor(f"{prefix}.bias").contiguous()
+        self.eps = eps
+
+    def forward(self, hidden_states, residual=None):
+        return native.layernorm_residual(hidden_states, residual, self.weight, self.bias, self.eps)
+
+    __call__ = forward
+
+
+def grow_max_positions(config, max_positions: int, max_s: int) -> int:
+    """How many positions the cos / sin tables of a model cover once a forward needs `max_s` of them.
+    Sized once for the model's whole position range, so the tables normally never move.  A longer request still works:
+    PositionRotaryEmbedding keeps the replaced tables allocated, because decode graphs captured earlier hold their raw
+    pointers (and only ever index positions inside the table they captured)."""
+    if max_s <= max_positions:
+        return max_positions
+    declared = min(int(getattr(config, "max_position_embeddings", 0) or 0), 1 << 17)
+    return max(max_s, 2 * max_positions, declared, 2048)
+
+
+class FlashForCausalLM:
+    """Tail of the three `*ForCausalLM` classes: `self.model` is the decoder stack, `self.lm_head` the output head and
+    `self.gptq_linears` the linears that are repacked after loading."""
+
+    def post_init(self):
+        """Repack every GPTQ linear for the kernels (the reference does this in serve(), server.py:334-358)."""
+        for lin in self.gptq_linears:
+            if lin.q_handle is None:
+                lin.post_init()
+
+    @property
+    def num_layers(self):
+        return len(self.model.layers)
+
+    def forward(self, input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds=None, kv: KVArgs = None,
+                lm_head_indices: Optional[torch.Tensor] = None):
+        """position_ids int32 [T]; returns fp32 logits [T or len(lm_head_indices), vocab]."""
+        if input_ids is not None and inputs_embeds is not None:
+            raise ValueError("You cannot specify both input_ids and inputs_embeds at the same time")
+        hidden_states = self.model(input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds, kv)
+        if lm_head_indices is not None:
+            hidden_states = hidden_states.index_select(0, lm_head_indices)
+        return self.lm_head(hidden_states)
+
+    __call__ = forward

@@ -11,13 +11,15 @@ Mirrors custom_modeling/flash_llama_modeling.py of the reference — `LlamaConfi
   * logits are produced in fp32.
 Tensor-parallel sharding follows the reference exactly (heads split across ranks, qkv / gate_up
 column-parallel, o_proj / down_proj row-parallel + all-reduce, vocab-parallel embedding and head)."""
-import os
-from dataclasses import dataclass
-from typing import List, Optional
-
-import torch
-
 from tgis_amd import native
+from tgis_amd.models.custom_modeling.flash_common import (  # noqa: F401  (KVArgs is re-exported)
+    FlashForCausalLM,
+    KVArgs,
+    attend,
+    grow_max_positions,
+    layer_pools,
+    write_kv,
+)
 from tgis_amd.utils.layers import (
     PositionRotaryEmbedding,
     TensorParallelColumnLinear,
@@ -59,19 +61,6 @@ class LlamaConfig:
 
     def to_dict(self):
         return dict(vars(self))
-
-
-@dataclass
-class KVArgs:
-    """Where this forward's keys/values live in the paged cache."""
-    cache: "object"                    # utils.kv_cache.PagedKVCache
-    block_tables: torch.Tensor         # [B, max_pages] int32 (device)
-    ctx_lens: Optional[torch.Tensor]   # [B] int32, tokens per sequence incl. this forward's (prefill); decode: filled in
-    slots: Optional[torch.Tensor]      # [T] int32 physical slot per token (prefill); decode: filled in
-    max_q_len: int                     # longest q run in this forward (1 for decode)
-    max_ctx: int                       # upper bound of ctx_lens (launch shaping only)
-    num_splits: int = 1                # attention key splits (decode)
-    fresh_prefill: bool = False        # every sequence starts at cache position 0: page-wise cache writes
 
 
 # (The persistent decode tail, the rope-in-attention launch and the norm-as-a-GEMM-phase launches of rounds 2 and 3 were all
@@ -135,14 +124,13 @@ class FlashLlamaAttention:
             bias=config.attention_bias)
         self.o_proj = TensorParallelRowLinear.load(config, prefix=f"{prefix}.o_proj", weights=weights,
                                                    bias=config.attention_bias)
-        # int4 qkv: decode steps of up to 32 rows rotate q / k and write the cache in the GEMM epilogue
+        # int4 qkv: decode steps of up to 64 rows rotate q / k and write the cache in the GEMM epilogue
         if hasattr(self.query_key_value.linear, "rope_heads"):
             self.query_key_value.linear.rope_heads = (self.num_heads, self.num_key_value_heads, self.head_size)
 
     def project_qkv(self, hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id: int, kv: KVArgs):
         """qkv GEMM, rotation of q and k in place, k and v scattered to their page slots (reference :251-268,282)."""
         H, Hkv, D = self.num_heads, self.num_key_value_heads, self.head_size
-        k_pool, v_pool = kv.cache.k_pool(layer_id), kv.cache.v_pool(layer_id)
         lin = self.query_key_value.linear
         rope_w = getattr(lin, "rope_handle", None)
         if isinstance(hidden_states, native.FragAct) or (
@@ -151,35 +139,18 @@ class FlashLlamaAttention:
                 and native.rope_gemm_ok(hidden_states.shape[0], rope_w, D)):
             # one launch: GEMM + rotary embedding + cache write (native.gptq_gemm_rope / native.dense_gemm_rope)
             fused = native.gptq_gemm_rope if isinstance(rope_w, native.GptqWeight) else native.dense_gemm_rope
+            k_pool, v_pool, scales = layer_pools(kv, layer_id)
             return fused(hidden_states, rope_w, lin.bias, cos, sin, position_ids, kv.slots, k_pool, v_pool, H, Hkv, D,
-                         **kv.cache.kv8_kwargs(layer_id))
+                         **scales)
         # [T, (H + 2 Hkv) D]; at decode sizes the split-K sum of the GPTQ GEMM is finished inside the rope kernel
         qkv = self.query_key_value(hidden_states, partial=True)
-        if kv.fresh_prefill and not isinstance(qkv, native.Partial):
-            return native.rope_kv_write_prefill(qkv, cos, sin, position_ids, cu_seqlens_q, kv.block_tables, k_pool, v_pool,
-                                                kv.max_q_len, H, Hkv, D, D, **kv.cache.kv8_kwargs(layer_id))
-        return native.rope_kv_write(qkv, cos, sin, position_ids, kv.slots, k_pool, v_pool, H, Hkv, D, D,
-                                    **kv.cache.kv8_kwargs(layer_id))
+        return write_kv(qkv, kv, layer_id, H, Hkv, D, D, cos, sin, position_ids, cu_seqlens_q)
 
     def attend(self, qkv, cu_seqlens_q, layer_id: int, kv: KVArgs):
         """Attention of the rotated q over the layer's cache pages (reference :271-295): [T, H D]."""
-        H, Hkv, D = self.num_heads, self.num_key_value_heads, self.head_size
-        k_pool, v_pool = kv.cache.k_pool(layer_id), kv.cache.v_pool(layer_id)
-        T = qkv.shape[0]
-        B = kv.block_tables.shape[0]
-        if frag_rows(self.o_proj.linear, T, kv):  # decode: the o_proj GEMM reads its operand in fragment order
-            attn_output = native.FragAct.empty(T, H * D, qkv.device)
-        else:
-            attn_output = torch.empty((T, H * D), dtype=qkv.dtype, device=qkv.device)
-        ws = None
-        if kv.num_splits > 1:
-            from tgis_amd.utils.layers import workspace
-            ws = workspace(qkv.device)
-            ws.ensure(native.attn_workspace_bytes(T, H, Hkv, D, kv.num_splits))
-        native.attn_paged(qkv, qkv.stride(0), k_pool, v_pool, kv.block_tables, kv.ctx_lens, cu_seqlens_q,
-                          attn_output, B, H, Hkv, D, kv.max_q_len, kv.max_ctx, self.softmax_scale, kv.num_splits, ws,
-                          **kv.cache.kv8_kwargs(layer_id))
-        return attn_output
+        # decode: the o_proj GEMM reads its operand in fragment order
+        return attend(qkv, kv, layer_id, self.num_heads, self.num_key_value_heads, self.head_size, self.softmax_scale,
+                      cu_seqlens_q, frag_out=frag_rows(self.o_proj.linear, qkv.shape[0], kv))
 
     def forward(self, hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id: int, kv: KVArgs):
         qkv = self.project_qkv(hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id, kv)
@@ -234,7 +205,7 @@ class FlashLlamaLayer:
     def forward(self, hidden_states, residual, cos, sin, position_ids, cu_seqlens_q, kv: KVArgs):
         rows = hidden_states.shape[0]
         att = self.self_attn
-        # decode steps of <= 32 rows hand the int4 GEMMs their operands in fragment order (native.FragAct): the qkv + rotary
+        # decode steps of <= 64 rows hand the int4 GEMMs their operands in fragment order (native.FragAct): the qkv + rotary
         # launch when it serves the step, the MLP when the SiLU * up epilogue does
         qkv_frag = (kv.slots is not None and cos.shape[1] * 2 == att.head_size
                     and frag_rows(att.query_key_value.linear, rows, kv, act=3))
@@ -261,18 +232,12 @@ class FlashLlamaModel:
         self.num_heads = self.layers[0].self_attn.num_heads
         self.num_key_value_heads = config.num_key_value_heads // process_group.size()
         self.max_positions = 0
+
     def rope_tables(self, dtype, device, max_s: int):
-        # Sized once for the model's whole position range, so the tables normally never move.  A longer request
-        # still works: PositionRotaryEmbedding keeps the replaced tables allocated, because decode graphs captured
-        # earlier hold their raw pointers (and only ever index positions inside the table they captured).
-        if max_s > self.max_positions:
-            declared = min(int(getattr(self.config, "max_position_embeddings", 0) or 0), 1 << 17)
-            self.max_positions = max(max_s, 2 * self.max_positions, declared, 2048)
+        self.max_positions = grow_max_positions(self.config, self.max_positions, max_s)
         return self.layers[0].self_attn.rotary_emb.tables(dtype, device, self.max_positions)
 
     def forward(self, input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds, kv: KVArgs):
-        if input_ids is not None and inputs_embeds is not None:
-            raise ValueError("You cannot specify both input_ids and inputs_embeds at the same time")
         hidden_states = inputs_embeds if inputs_embeds is not None else self.embed_tokens(input_ids)
         cos, sin = self.rope_tables(hidden_states.dtype, hidden_states.device, max_s)
         residual = None
@@ -284,37 +249,17 @@ class FlashLlamaModel:
     __call__ = forward
 
 
-class FlashLlamaForCausalLM:
+class FlashLlamaForCausalLM(FlashForCausalLM):
     def __init__(self, config, weights):
         self.config = config
         self.model = FlashLlamaModel(config, weights)
         self.lm_head = TensorParallelHead.load(config, prefix="lm_head", weights=weights)
-        self.gptq_linears: List = []
+        self.gptq_linears = []
         for layer in self.model.layers:
             for lin in (layer.self_attn.query_key_value.linear, layer.self_attn.o_proj.linear,
                         layer.mlp.gate_up_proj.linear, layer.mlp.down_proj.linear):
                 if hasattr(lin, "post_init"):
                     self.gptq_linears.append(lin)
 
-    def post_init(self):
-        """Repack every GPTQ linear for the kernels (the reference does this in serve(), server.py:334-358)."""
-        for lin in self.gptq_linears:
-            if lin.q_handle is None:
-                lin.post_init()
-
     def get_input_embeddings(self):
         return self.model.embed_tokens
-
-    @property
-    def num_layers(self):
-        return len(self.model.layers)
-
-    def forward(self, input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds=None, kv: KVArgs = None,
-                lm_head_indices: Optional[torch.Tensor] = None):
-        """position_ids int32 [T]; returns fp32 logits [T or len(lm_head_indices), vocab]."""
-        hidden_states = self.model(input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds, kv)
-        if lm_head_indices is not None:
-            hidden_states = hidden_states.index_select(0, lm_head_indices)
-        return self.lm_head(hidden_states)
-
-    __call__ = forward

@@ -13,7 +13,14 @@ import torch
 import torch.distributed
 
 from tgis_amd import native
-from tgis_amd.models.custom_modeling.flash_llama_modeling import KVArgs
+from tgis_amd.models.custom_modeling.flash_common import (
+    FastLayerNorm,
+    FlashForCausalLM,
+    KVArgs,
+    attend,
+    grow_max_positions,
+    write_kv,
+)
 from tgis_amd.utils.graph_segments import collective
 from tgis_amd.utils.layers import (
     PositionRotaryEmbedding,
@@ -127,18 +134,6 @@ def load_row(config, prefix: str, weights):
     return TensorParallelRowLinear(linear, process_group=weights.process_group)
 
 
-class FastLayerNorm:
-    def __init__(self, prefix, weights, eps):
-        self.weight = weights.get_tensor(f"{prefix}.weight").contiguous()
-        self.bias = weights.get_tensor(f"{prefix}.bias").contiguous()
-        self.eps = eps
-
-    def forward(self, hidden_states, residual=None):
-        return native.layernorm_residual(hidden_states, residual, self.weight, self.bias, self.eps)
-
-    __call__ = forward
-
-
 class FlashNeoxAttention:
     def __init__(self, config, prefix, weights):
         self.hidden_size = config.hidden_size
@@ -156,26 +151,10 @@ class FlashNeoxAttention:
 
     def forward(self, hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id: int, kv: KVArgs, partial: bool):
         H, D = self.num_heads, self.head_size
-        k_pool, v_pool = kv.cache.k_pool(layer_id), kv.cache.v_pool(layer_id)
-        kv8 = kv.cache.kv8_kwargs(layer_id)  # the scales of a one-byte cache (none for a 16-bit one)
         # [T, 3 H D]; at decode sizes the split-K sum (and the bias) is finished inside the rotary + cache-write kernel
         qkv = self.query_key_value(hidden_states, partial=True)
-        if kv.fresh_prefill and not isinstance(qkv, native.Partial):
-            qkv = native.rope_kv_write_prefill(qkv, cos, sin, position_ids, cu_seqlens_q, kv.block_tables, k_pool,
-                                               v_pool, kv.max_q_len, H, H, D, self.rot_dim, **kv8)
-        else:
-            qkv = native.rope_kv_write(qkv, cos, sin, position_ids, kv.slots, k_pool, v_pool, H, H, D, self.rot_dim,
-                                       **kv8)
-        T = qkv.shape[0]
-        attn_output = torch.empty((T, H * D), dtype=qkv.dtype, device=qkv.device)
-        ws = None
-        if kv.num_splits > 1:
-            from tgis_amd.utils.layers import workspace
-            ws = workspace(qkv.device)
-            ws.ensure(native.attn_workspace_bytes(T, H, H, D, kv.num_splits))
-        native.attn_paged(qkv, qkv.stride(0), k_pool, v_pool, kv.block_tables, kv.ctx_lens, cu_seqlens_q, attn_output,
-                          kv.block_tables.shape[0], H, H, D, kv.max_q_len, kv.max_ctx, self.softmax_scale, kv.num_splits,
-                          ws, **kv8)
+        qkv = write_kv(qkv, kv, layer_id, H, H, D, self.rot_dim, cos, sin, position_ids, cu_seqlens_q)
+        attn_output = attend(qkv, kv, layer_id, H, H, D, self.softmax_scale, cu_seqlens_q)
         return self.dense(attn_output, partial=partial)
 
     __call__ = forward
@@ -243,15 +222,11 @@ class FlashGPTNeoXModel:
         self.max_positions = 0
 
     def rope_tables(self, dtype, device, max_s: int):
-        """cos / sin [positions, rot_dim / 2], sized once for the model's position range (see FlashLlamaModel)."""
-        if max_s > self.max_positions:
-            declared = min(int(getattr(self.config, "max_position_embeddings", 0) or 0), 1 << 17)
-            self.max_positions = max(max_s, 2 * self.max_positions, declared, 2048)
+        """cos / sin [positions, rot_dim / 2], sized once for the model's position range (grow_max_positions)."""
+        self.max_positions = grow_max_positions(self.config, self.max_positions, max_s)
         return self.layers[0].attention.rotary_emb.tables(dtype, device, self.max_positions)
 
     def forward(self, input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds, kv: KVArgs):
-        if input_ids is not None and inputs_embeds is not None:
-            raise ValueError("You cannot specify both input_ids and inputs_embeds at the same time")
         hidden_states = inputs_embeds if inputs_embeds is not None else self.embed_in(input_ids)
         cos, sin = self.rope_tables(hidden_states.dtype, hidden_states.device, max_s)
         fln = self.final_layer_norm
@@ -275,7 +250,7 @@ class FlashGPTNeoXModel:
     __call__ = forward
 
 
-class FlashGPTNeoXForCausalLM:
+class FlashGPTNeoXForCausalLM(FlashForCausalLM):
     def __init__(self, config, weights):
         check_neox_config(config)
         self.config = config
@@ -287,22 +262,12 @@ class FlashGPTNeoXForCausalLM:
         return self.gpt_neox
 
     @property
-    def num_layers(self):
-        return len(self.gpt_neox.layers)
+    def lm_head(self):
+        return self.embed_out
 
     def post_init(self):
         pass  # dense weights only: their GEMM images are built at load
 
     def get_input_embeddings(self):
         return self.gpt_neox.embed_in
-
-    def forward(self, input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds=None, kv: KVArgs = None,
-                lm_head_indices: Optional[torch.Tensor] = None):
-        """position_ids int32 [T]; returns fp32 logits [T or len(lm_head_indices), vocab]."""
-        hidden_states = self.gpt_neox(input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds, kv)
-        if lm_head_indices is not None:
-            hidden_states = hidden_states.index_select(0, lm_head_indices)
-        return self.embed_out(hidden_states)
-
-    __call__ = forward
 

@@ -6,16 +6,12 @@ ranks, the single k/v head replicated on every rank), `load_col`/`load_row` (:16
 all-reduce, :408-414) and `FlashSantacoderForCausalLM` (:462-498, lm_head tied to wte).
 Differences are the same as for Llama (paged KV through `KVArgs`, fp32 logits); there is no RoPE, so
 tgis_rope_kv_write runs with cos = NULL and only scatters k/v into their page slots."""
-from typing import List, Optional
-
-import os
-
 import torch
 import torch.distributed
 
 from tgis_amd import native
 from tgis_amd.utils.graph_segments import collective
-from tgis_amd.models.custom_modeling.flash_llama_modeling import KVArgs
+from tgis_amd.models.custom_modeling.flash_common import FastLayerNorm, FlashForCausalLM, KVArgs, attend, write_kv
 from tgis_amd.utils.layers import (
     FastLinear,
     TensorParallelColumnLinear,
@@ -23,7 +19,6 @@ from tgis_amd.utils.layers import (
     TensorParallelHead,
     TensorParallelRowLinear,
     get_linear,
-    workspace,
 )
 
 
@@ -96,18 +91,6 @@ def load_row(config, prefix: str, weights, bias: bool):
     return TensorParallelRowLinear(get_linear(weight, b, config.quantize), process_group=weights.process_group)
 
 
-class FastLayerNorm:
-    def __init__(self, prefix, weights, eps):
-        self.weight = weights.get_tensor(f"{prefix}.weight").contiguous()
-        self.bias = weights.get_tensor(f"{prefix}.bias").contiguous()
-        self.eps = eps
-
-    def forward(self, hidden_states, residual=None):
-        return native.layernorm_residual(hidden_states, residual, self.weight, self.bias, self.eps)
-
-    __call__ = forward
-
-
 class FlashMQAttention:
     def __init__(self, prefix, config, weights):
         self.hidden_size = config.hidden_size
@@ -127,23 +110,8 @@ class FlashMQAttention:
         # [T, (H + 2) D]: H query heads, then the single k and v heads; at decode sizes the split-K sum is left to
         # the cache-write kernel below (native.Partial)
         qkv = self.c_attn(hidden_states, partial=True)
-        k_pool, v_pool = kv.cache.k_pool(layer_id), kv.cache.v_pool(layer_id)
-        kv8 = kv.cache.kv8_kwargs(layer_id)  # the scales of a one-byte cache (none for a 16-bit one)
-        if kv.fresh_prefill and not isinstance(qkv, native.Partial):
-            qkv = native.rope_kv_write_prefill(qkv, None, None, None, cu_seqlens_q, kv.block_tables, k_pool, v_pool,
-                                               kv.max_q_len, H, 1, D, D, **kv8)  # no rotary: page-wise write only
-        else:
-            qkv = native.rope_kv_write(qkv, None, None, None, kv.slots, k_pool, v_pool, H, 1, D, D,
-                                       **kv8)  # no rotary
-        T = qkv.shape[0]
-        attn_output = torch.empty((T, H * D), dtype=qkv.dtype, device=qkv.device)
-        ws = None
-        if kv.num_splits > 1:
-            ws = workspace(qkv.device)
-            ws.ensure(native.attn_workspace_bytes(T, H, 1, D, kv.num_splits))
-        native.attn_paged(qkv, qkv.stride(0), k_pool, v_pool, kv.block_tables, kv.ctx_lens, cu_seqlens_q,
-                          attn_output, kv.block_tables.shape[0], H, 1, D, kv.max_q_len, kv.max_ctx,
-                          self.softmax_scale, kv.num_splits, ws, **kv8)
+        qkv = write_kv(qkv, kv, layer_id, H, 1, D, D, None, None, None, cu_seqlens_q)  # no rotary: cache write only
+        attn_output = attend(qkv, kv, layer_id, H, 1, D, self.softmax_scale, cu_seqlens_q)
         return self.c_proj(attn_output, partial=True)  # summed by the following add + LayerNorm
 
     __call__ = forward
@@ -200,8 +168,6 @@ class FlashSantacoderModel:
         self.num_key_value_heads = 1  # the single kv head is replicated on every rank
 
     def forward(self, input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds, kv: KVArgs):
-        if input_ids is not None and inputs_embeds is not None:
-            raise ValueError("You cannot specify both input_ids and inputs_embeds at the same time")
         pos = self.wpe(position_ids.to(torch.int64))
         tok = inputs_embeds if inputs_embeds is not None else self.wte(input_ids)
         hidden_states = tok + pos  # partial sums of both vocab-sharded tables ...
@@ -218,12 +184,12 @@ class FlashSantacoderModel:
     __call__ = forward
 
 
-class FlashSantacoderForCausalLM:
+class FlashSantacoderForCausalLM(FlashForCausalLM):
     def __init__(self, config, weights):
         self.config = config
         self.transformer = FlashSantacoderModel(config, weights)
         self.lm_head = TensorParallelHead.load(config, prefix="transformer.wte", weights=weights)  # tied
-        self.gptq_linears: List = []
+        self.gptq_linears = []
         for blk in self.transformer.h:
             for lin in (blk.attn.c_attn.linear, blk.attn.c_proj.linear, blk.mlp.c_fc.linear, blk.mlp.c_proj.linear):
                 if hasattr(lin, "post_init"):
@@ -233,19 +199,5 @@ class FlashSantacoderForCausalLM:
     def model(self):
         return self.transformer
 
-    def post_init(self):
-        for lin in self.gptq_linears:
-            if lin.q_handle is None:
-                lin.post_init()
-
     def get_input_embeddings(self):
         return self.transformer.wte
-
-    def forward(self, input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds=None, kv: KVArgs = None,
-                lm_head_indices: Optional[torch.Tensor] = None):
-        hidden_states = self.transformer(input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds, kv)
-        if lm_head_indices is not None:
-            hidden_states = hidden_states.index_select(0, lm_head_indices)
-        return self.lm_head(hidden_states)
-
-    __call__ = forward

@@ -17,7 +17,7 @@ What is different by design:
 import logging
 import os
 import time
-from collections import OrderedDict
+from collections import OrderedDict, deque
 from dataclasses import dataclass
 from operator import itemgetter
 from typing import Any, List, Optional, Tuple, Type, Union
@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from tgis_amd import native
-from tgis_amd.models.custom_modeling.flash_llama_modeling import KVArgs
+from tgis_amd.models.custom_modeling.flash_common import KVArgs
 from tgis_amd.models.model import Model
 from tgis_amd.models.types import Batch, GenerateError
 from tgis_amd.pb import generate_pb2
@@ -530,7 +530,7 @@ class FlashCausalLM(Model):
         # captured decode steps, least recently used first; they share one memory pool (a step's intermediates are dead
         # once it has run, and its outputs are consumed before the next replay), and the number kept is bounded
         self._graphs = OrderedDict()
-        self.graph_captures: List[Tuple[int, int, float]] = []
+        self.graph_captures = deque(maxlen=4096)  # (rows, pages per row, capture ms) of the latest captures
         self.max_graphs = int(os.getenv("TGIS_MAX_DECODE_GRAPHS", "48"))
         self.graph_pool = torch.cuda.graph_pool_handle() if self.use_graphs else None
 

@@ -27,7 +27,6 @@ _vp = ctypes.c_void_p
 _KV8_ARGS = [_c_int, _c_f, _c_f]  # kv_dtype, k_scale, v_scale appended by the *_kv8 entry points
 
 
-
 # name -> (restype, argtypes); must list every symbol declared in include/tgis_hip.h
 SIGNATURES = {
     "tgis_version": (ctypes.c_char_p, []),
@@ -147,6 +146,17 @@ KV8_DTYPES = (torch.uint8, torch.float8_e4m3fn)  # a one-byte pool holds e4m3 co
 def kv_is8(pool: Optional[torch.Tensor]) -> bool:
     """Whether a KV pool holds one-byte (e4m3) codes: its writers and readers then take the *_kv8 entry points."""
     return pool is not None and pool.dtype in KV8_DTYPES
+
+
+def _call_kv(name: str, args: tuple, k_pool, v_pool, kv_scales) -> None:
+    """One launch of the entry point `name` that writes or reads the KV cache: `name` itself on 16-bit pools, its `_kv8`
+    twin with (kv_dtype, k_scale, v_scale) appended on one-byte pools."""
+    if kv_is8(k_pool):
+        assert kv_is8(v_pool) and k_pool.dtype == v_pool.dtype, "k and v pools must both hold e4m3 codes"
+        k_scale, v_scale = (1.0, 1.0) if kv_scales is None else kv_scales
+        name += "_kv8"
+        args += (KV_FP8_E4M3, float(k_scale), float(v_scale))
+    _check(getattr(load_library(), name)(*args), name)
 
 
 def dtype_code(dt: torch.dtype) -> int:
@@ -454,11 +464,7 @@ def gptq_gemm_rope(x: torch.Tensor, w: GptqWeight, bias, cos, sin, positions, sl
         out = torch.empty((M, w.N), dtype=torch.float16, device=x.device)
     args = (xp, ldx, _ptr(w.image), _ptr(bias), _ptr(positions), _ptr(slots), _ptr(cos), _ptr(sin), _ptr(out),
             out.stride(0), _ptr(k_pool), _ptr(v_pool), M, w.K, w.N, w.groups, H, Hkv, D, _stream())
-    if kv_is8(k_pool):
-        _check(load_library().tgis_gptq_gemm_rope_f16_kv8(*args, *_kv8_args(k_pool, v_pool, kv_scales)),
-               "tgis_gptq_gemm_rope_f16_kv8")
-    else:
-        _check(load_library().tgis_gptq_gemm_rope_f16(*args), "tgis_gptq_gemm_rope_f16")
+    _call_kv("tgis_gptq_gemm_rope_f16", args, k_pool, v_pool, kv_scales)
     return out
 
 
@@ -542,11 +548,7 @@ def dense_gemm_rope(x: torch.Tensor, w: DenseWeight, bias, cos, sin, positions, 
         out = torch.empty((M, w.N), dtype=w.dtype, device=x.device)
     args = (_ptr(x), x.stride(0), _ptr(w.image), _ptr(bias), _ptr(positions), _ptr(slots), _ptr(cos), _ptr(sin),
             _ptr(out), out.stride(0), _ptr(k_pool), _ptr(v_pool), M, w.K, w.N, H, Hkv, D, dtype_code(w.dtype), _stream())
-    if kv_is8(k_pool):
-        _check(load_library().tgis_dense_gemm_rope_kv8(*args, *_kv8_args(k_pool, v_pool, kv_scales)),
-               "tgis_dense_gemm_rope_kv8")
-    else:
-        _check(load_library().tgis_dense_gemm_rope(*args), "tgis_dense_gemm_rope")
+    _call_kv("tgis_dense_gemm_rope", args, k_pool, v_pool, kv_scales)
     return out
 
 
@@ -558,7 +560,7 @@ def clear_error() -> None:
 # ---- norms --------------------------------------------------------------------------------------------
 def rmsnorm_residual(x, residual, weight, eps: float, y=None, res_out=None, frag: bool = False):
     """(y, res) = fused add + RMSNorm; mirrors LlamaRMSNorm.forward (flash_llama_modeling.py:113-152).
-    frag (rows <= 32, f16): y is returned as a FragAct, the layout the int4 GEMM behind the norm reads."""
+    frag (rows <= 64, f16): y is returned as a FragAct, the layout the int4 GEMM behind the norm reads."""
     rows, hidden = x.shape
     yf = None
     if frag:
@@ -647,40 +649,24 @@ def layernorm2_residual(residual, a, b, w1, b1, eps: float, w2=None, b2=None, re
 
 
 # ---- rope + kv write, attention --------------------------------------------------------------------------
-def _kv8_args(k_pool, v_pool, kv_scales):
-    """(kv_dtype, k_scale, v_scale) of a *_kv8 call on one-byte pools."""
-    assert kv_is8(v_pool) and k_pool.dtype == v_pool.dtype, "k and v pools must both hold e4m3 codes"
-    k_scale, v_scale = (1.0, 1.0) if kv_scales is None else kv_scales
-    return KV_FP8_E4M3, float(k_scale), float(v_scale)
-
-
 def rope_kv_write(qkv, cos, sin, positions, slots, k_pool, v_pool, H: int, Hkv: int, D: int, rot_dim: int,
                   kv_scales=(1.0, 1.0)):
     """Rotates q,k in place and writes k,v to the cache.  `qkv` may be a Partial: the reduced, rotated activation is
     then materialised into a fresh [T, (H+2Hkv)D] tensor, which is returned (the plain form returns qkv itself).
     One-byte pools (kv_is8) receive e4m3 codes of k / k_scale and v / v_scale, kv_scales = (k_scale, v_scale)."""
-    kv8 = kv_is8(k_pool)
-    lib = load_library()
     if isinstance(qkv, Partial):
         T = qkv.M
         out = torch.empty((T, qkv.N), dtype=qkv.dtype, device=qkv.device)
         args = (_ptr(qkv.slabs), qkv.S, qkv.ld, _ptr(qkv.bias), _ptr(out), out.stride(0), _ptr(cos), _ptr(sin),
                 _ptr(positions), _ptr(slots), _ptr(k_pool), _ptr(v_pool), T, H, Hkv, D, rot_dim, dtype_code(out.dtype),
                 _stream())
-        if kv8:
-            _check(lib.tgis_rope_kv_write_partial_kv8(*args, *_kv8_args(k_pool, v_pool, kv_scales)),
-                   "tgis_rope_kv_write_partial_kv8")
-        else:
-            _check(lib.tgis_rope_kv_write_partial(*args), "tgis_rope_kv_write_partial")
+        _call_kv("tgis_rope_kv_write_partial", args, k_pool, v_pool, kv_scales)
         return out
     assert qkv.dim() == 2 and qkv.stride(1) == 1
     T = qkv.shape[0]
     args = (_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(positions), _ptr(slots), _ptr(k_pool), _ptr(v_pool), T,
             H, Hkv, D, rot_dim, dtype_code(qkv.dtype), _stream())
-    if kv8:
-        _check(lib.tgis_rope_kv_write_kv8(*args, *_kv8_args(k_pool, v_pool, kv_scales)), "tgis_rope_kv_write_kv8")
-    else:
-        _check(lib.tgis_rope_kv_write(*args), "tgis_rope_kv_write")
+    _call_kv("tgis_rope_kv_write", args, k_pool, v_pool, kv_scales)
     return qkv
 
 
@@ -692,11 +678,7 @@ def rope_kv_write_prefill(qkv, cos, sin, positions, cu_seqlens, block_tables, k_
     args = (_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(positions), _ptr(cu_seqlens), _ptr(block_tables),
             block_tables.shape[1], _ptr(k_pool), _ptr(v_pool), B, qkv.shape[0], max_len, H, Hkv, D, rot_dim,
             dtype_code(qkv.dtype), _stream())
-    if kv_is8(k_pool):
-        _check(load_library().tgis_rope_kv_write_prefill_kv8(*args, *_kv8_args(k_pool, v_pool, kv_scales)),
-               "tgis_rope_kv_write_prefill_kv8")
-    else:
-        _check(load_library().tgis_rope_kv_write_prefill(*args), "tgis_rope_kv_write_prefill")
+    _call_kv("tgis_rope_kv_write_prefill", args, k_pool, v_pool, kv_scales)
     return qkv
 
 
@@ -711,7 +693,7 @@ def attn_workspace_bytes(total_q: int, H: int, Hkv: int, D: int, num_splits: int
 def attn_paged(q, ld_q: int, k_pool, v_pool, block_tables, ctx_lens, cu_seqlens_q, out, B: int, H: int, Hkv: int,
                D: int, max_q_len: int, max_ctx: int, scale: float, num_splits: int, ws: Optional[Workspace],
                kv_scales=(1.0, 1.0)):
-    """q is a (view into a) [T, *] activation whose row stride is ld_q elements; out [T, H*D], or (decode, B <= 32) a
+    """q is a (view into a) [T, *] activation whose row stride is ld_q elements; out [T, H*D], or (decode, B <= 64) a
     FragAct of that shape for the o_proj GEMM.  One-byte pools (kv_is8) are read as k_scale * e4m3(k), v_scale * e4m3(v)
     (tgis_attn_paged_kv8), kv_scales = (k_scale, v_scale)."""
     assert block_tables.dtype == torch.int32 and ctx_lens.dtype == torch.int32 and cu_seqlens_q.dtype == torch.int32
@@ -726,10 +708,7 @@ def attn_paged(q, ld_q: int, k_pool, v_pool, block_tables, ctx_lens, cu_seqlens_
     args = (_ptr(q), ld_q, _ptr(k_pool), _ptr(v_pool), _ptr(block_tables), block_tables.shape[1], _ptr(ctx_lens),
             _ptr(cu_seqlens_q), optr, ldo, B, H, Hkv, D, max_q_len, max_ctx, float(scale), dtype_code(q.dtype), num_splits,
             wptr, wbytes, _stream())
-    if kv_is8(k_pool):
-        _check(load_library().tgis_attn_paged_kv8(*args, *_kv8_args(k_pool, v_pool, kv_scales)), "tgis_attn_paged_kv8")
-    else:
-        _check(load_library().tgis_attn_paged(*args), "tgis_attn_paged")
+    _call_kv("tgis_attn_paged", args, k_pool, v_pool, kv_scales)
     return out
 
 

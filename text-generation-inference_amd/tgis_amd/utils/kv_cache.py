@@ -100,11 +100,6 @@ class PagedKVCache:
         """(k_scale, v_scale) of a layer: a one-byte pool holds e4m3(k / k_scale), e4m3(v / v_scale)."""
         return self.k_scales[layer], self.v_scales[layer]
 
-    def kv8_kwargs(self, layer: int) -> dict:
-        """Keyword arguments of the native cache writers / attention for this layer: the scales of a one-byte pool, nothing
-        for a 16-bit one (whose calls stay exactly what they were)."""
-        return {"kv_scales": self.scales(layer)} if self.is_fp8 else {}
-
     def k_pool(self, layer: int) -> torch.Tensor:
         return self.pool[layer, 0]
 
