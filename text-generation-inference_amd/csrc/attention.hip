@@ -22,6 +22,7 @@
 #include <map>
 #include <mutex>
 #include "common.h"
+#include "dispatch.h"
 #include "attention_args.h"
 #include "kv_layout.h"
 
@@ -584,26 +585,21 @@ static void launch_attn_one(const AttnArgs& a, dim3 grid, hipStream_t st) {
     launch_attn_pipe<T, KV, D, NW, CH, false>(a, grid, st);
 }
 
-template <typename T, typename KV, int D, int CH>
-static void launch_attn_nw(const AttnArgs& a, dim3 grid, hipStream_t st, int nw) {
-    if (nw == 1) return launch_attn_one<T, KV, D, 1, CH>(a, grid, st);
-    if (nw == 2) return launch_attn_one<T, KV, D, 2, CH>(a, grid, st);
-    if constexpr (CH == 1) {  // wide blocks: few (sequence, kv head) groups, the waves of one block share the keys
-        if (nw == 8) return launch_attn_one<T, KV, D, 8, CH>(a, grid, st);
-        if (nw == 3) return launch_attn_one<T, KV, D, 3, CH>(a, grid, st);  // three waves per SIMD at 1024 blocks (A/B hook)
-    }
-    launch_attn_one<T, KV, D, 4, CH>(a, grid, st);
-}
-
 template <typename T, typename KV, int D>
 static int launch_attn(const AttnArgs& a, dim3 grid, int64_t total_q, hipStream_t st, int nw, int ch) {
-    if (ch == 3)
-        launch_attn_nw<T, KV, D, 3>(a, grid, st, nw);
-    else if (ch == 2)
-        launch_attn_nw<T, KV, D, 2>(a, grid, st, nw);
-    else
-        launch_attn_nw<T, KV, D, 1>(a, grid, st, nw);
-    TGIS_CHECK_LAUNCH();
+    const int rc = by_int<1, 2, 3>(ch, "tgis_attn_paged: chunks per block", [&](auto chc) {
+        constexpr int CH = decltype(chc)::value;
+        auto one = [&](auto nwc) {
+            launch_attn_one<T, KV, D, decltype(nwc)::value, CH>(a, grid, st);
+            TGIS_CHECK_LAUNCH();
+            return TGIS_OK;
+        };
+        // wide blocks (8 waves): few (sequence, kv head) groups, the waves of one block share the keys; three waves per
+        // SIMD at 1024 blocks is an A/B hook.  Both exist for one-chunk blocks only.
+        if constexpr (CH == 1) return by_int<1, 2, 3, 4, 8>(nw, "tgis_attn_paged: waves per block", one);
+        else return by_int<1, 2, 4>(nw, "tgis_attn_paged: waves per block", one);
+    });
+    if (rc != TGIS_OK) return rc;
     if (a.NS > 1 && !a.counters) {
         const int64_t rows = total_q * a.H;
         if (a.NS <= 8)
@@ -884,26 +880,15 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
         if (ch > 1 && (nw > 4 || nw == 3)) nw = 4;
     }
     TgisTimedScope timed(TGIS_OP_ATTN, st);
-    if (kv8) {  // one-byte cache: the same launch shapes over e4m3 pools
-        if (dtype == TGIS_F16) {
-            if (D == 128) return launch_attn<f16, uint8_t, 128>(a, grid, total_q, st, nw, ch);
-            if (D == 96) return launch_attn<f16, uint8_t, 96>(a, grid, total_q, st, nw, ch);
-            return launch_attn<f16, uint8_t, 64>(a, grid, total_q, st, nw, ch);
-        } else {
-            if (D == 128) return launch_attn<bf16, uint8_t, 128>(a, grid, total_q, st, nw, ch);
-            if (D == 96) return launch_attn<bf16, uint8_t, 96>(a, grid, total_q, st, nw, ch);
-            return launch_attn<bf16, uint8_t, 64>(a, grid, total_q, st, nw, ch);
-        }
-    }
-    if (dtype == TGIS_F16) {
-        if (D == 128) return launch_attn<f16, f16, 128>(a, grid, total_q, st, nw, ch);
-        if (D == 96) return launch_attn<f16, f16, 96>(a, grid, total_q, st, nw, ch);  // KS = 3, NB = 6 (gpt-neox-20b)
-        return launch_attn<f16, f16, 64>(a, grid, total_q, st, nw, ch);
-    } else {
-        if (D == 128) return launch_attn<bf16, bf16, 128>(a, grid, total_q, st, nw, ch);
-        if (D == 96) return launch_attn<bf16, bf16, 96>(a, grid, total_q, st, nw, ch);
-        return launch_attn<bf16, bf16, 64>(a, grid, total_q, st, nw, ch);
-    }
+    return by_dtype(dtype, [&](auto t) {
+        using T = type_of<decltype(t)>;
+        return by_kv<T>(kv8, [&](auto kv) {  // one-byte cache: the same launch shapes over e4m3 pools
+            // D = 96: KS = 3, NB = 6 (gpt-neox-20b)
+            return by_int<128, 96, 64>(D, "tgis_attn_paged: head_dim", [&](auto d) {
+                return launch_attn<T, type_of<decltype(kv)>, decltype(d)::value>(a, grid, total_q, st, nw, ch);
+            });
+        });
+    });
 }
 
 extern "C" int tgis_attn_paged(const void* q, int64_t ld_q, const void* k_pool, const void* v_pool,

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "common.h"
+#include "dispatch.h"
 #include "attention_args.h"
 #include "kv_layout.h"
 
@@ -242,26 +243,16 @@ int tgis_launch_attn_prefill(const AttnArgs& a, int64_t B, int Hkv, int D, int64
     TGIS_CHECK_ARG(q_tiles <= 2147483647LL && (int64_t)Hkv * a.HC <= 65535 && B <= 65535, "tgis_attn_paged: grid too large");
     dim3 grid((unsigned)q_tiles, (unsigned)(Hkv * a.HC), (unsigned)B);
     const size_t lds = (size_t)2 * 2 * 32 * D * 2;  // two buffers of (K page + V page); >= 4 wave slices of D*16 floats
-#define TGIS_PREFILL_LAUNCH(T, DD)                                                                         \
-    do {                                                                                                   \
-        if (kv8)                                                                                           \
-            hipLaunchKernelGGL((attn_prefill_kernel<T, uint8_t, DD>), grid, dim3(256), lds, st, a);        \
-        else                                                                                               \
-            hipLaunchKernelGGL((attn_prefill_kernel<T, T, DD>), grid, dim3(256), lds, st, a);              \
-    } while (0)
-    // every head size by name: a size the caller lets through without a kernel here is an error, not the 64 path
-    if (dtype == TGIS_F16) {
-        if (D == 128) TGIS_PREFILL_LAUNCH(f16, 128);
-        else if (D == 96) TGIS_PREFILL_LAUNCH(f16, 96);
-        else if (D == 64) TGIS_PREFILL_LAUNCH(f16, 64);
-        else TGIS_CHECK_ARG(false, "tgis_attn_paged: no prefill kernel for head_dim %d", D);
-    } else {
-        if (D == 128) TGIS_PREFILL_LAUNCH(bf16, 128);
-        else if (D == 96) TGIS_PREFILL_LAUNCH(bf16, 96);
-        else if (D == 64) TGIS_PREFILL_LAUNCH(bf16, 64);
-        else TGIS_CHECK_ARG(false, "tgis_attn_paged: no prefill kernel for head_dim %d", D);
-    }
-#undef TGIS_PREFILL_LAUNCH
-    TGIS_CHECK_LAUNCH();
-    return TGIS_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = type_of<decltype(t)>;
+        return by_kv<T>(kv8, [&](auto kv) {
+            // every head size by name: a size the caller lets through without a kernel here is an error, not the 64 path
+            return by_int<128, 96, 64>(D, "tgis_attn_paged: prefill head_dim", [&](auto d) {
+                hipLaunchKernelGGL((attn_prefill_kernel<T, type_of<decltype(kv)>, decltype(d)::value>), grid, dim3(256), lds,
+                                   st, a);
+                TGIS_CHECK_LAUNCH();
+                return TGIS_OK;
+            });
+        });
+    });
 }

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "common.h"
+#include "dispatch.h"
 #include "dense_gemm_body.h"
 
 namespace {
@@ -126,27 +127,15 @@ static int launch_dense(const DenseArgs& a, const DensePlan& pl, int act, int64_
     dim3 grid((unsigned)cdiv64(a.NT, pl.TN), (unsigned)pl.S, (unsigned)cdiv64(mslabs32, pl.MR));
     const size_t lds = (size_t)pl.WK * 2 * 32 * pl.MR * DRS * sizeof(T) + 64;
     const int rows = dense_row_class(pl, a.M);
-    int rc = TGIS_EINVAL;
-#define TGIS_DENSE_CASE(T_, W_)                                                        \
-    if (pl.TN == T_ && pl.WK == W_)                                                    \
-        rc = act == 4   ? launch_dense_variant<T, T_, W_, 4>(rows, grid, lds, st, a)                                             \
-             : act == 3 ? launch_dense_variant<T, T_, W_, 3>(rows, grid, lds, st, a)                                             \
-             : act == 2 ? launch_dense_variant<T, T_, W_, 2>(rows, grid, lds, st, a)                                             \
-             : act == 1 ? launch_dense_variant<T, T_, W_, 1>(rows, grid, lds, st, a)                                             \
-                        : launch_dense_variant<T, T_, W_, 0>(rows, grid, lds, st, a)
-    // one tile per k-part group: the fused qkv + rotary launch of a narrow projection (TinyLlama: 80 tiles, unsplit)
-    if (pl.TN == 1 && pl.WK == 4 && act == 3) rc = launch_dense_variant<T, 1, 4, 3>(rows, grid, lds, st, a);
-    if (pl.TN == 1 && pl.WK == 4 && act == 4) rc = launch_dense_variant<T, 1, 4, 4>(rows, grid, lds, st, a);
-    TGIS_DENSE_CASE(2, 2);
-    TGIS_DENSE_CASE(2, 4);
-    TGIS_DENSE_CASE(3, 4);
-    TGIS_DENSE_CASE(4, 2);
-    TGIS_DENSE_CASE(4, 4);
-#undef TGIS_DENSE_CASE
-    if (rc != TGIS_OK) {
-        tgis_set_error("tgis_dense_gemm: no kernel for plan TN=%d WK=%d", pl.TN, pl.WK);
-        return rc;
-    }
+    const int rc = by_pair<pair_c<1, 4>, pair_c<2, 2>, pair_c<2, 4>, pair_c<3, 4>, pair_c<4, 2>, pair_c<4, 4>>(
+        pl.TN, pl.WK, "tgis_dense_gemm: plan (TN, WK)", [&](auto tw) {
+        constexpr int TN = decltype(tw)::first, WK = decltype(tw)::second;
+        auto variant = [&](auto ac) { return launch_dense_variant<T, TN, WK, decltype(ac)::value>(rows, grid, lds, st, a); };
+        // one tile per k-part group: the fused qkv + rotary launch of a narrow projection (TinyLlama: 80 tiles, unsplit)
+        if constexpr (TN == 1) return by_int<3, 4>(act, "tgis_dense_gemm: one-tile plan, act", variant);
+        else return by_int<0, 1, 2, 3, 4>(act, "tgis_dense_gemm: act", variant);
+    });
+    if (rc != TGIS_OK) return rc;
     TGIS_CHECK_LAUNCH();
     if (!a.partial && pl.S > 1) {
         const int NP = a.NT * 32;
@@ -180,14 +169,13 @@ extern "C" int tgis_dense_prepare(const void* w, int64_t N, int64_t K, int dtype
     int64_t NT = cdiv64(N, 32), KS = cdiv64(K, 64);
     int64_t total = NT * KS * 256;
     dim3 grid((unsigned)cdiv64(total, 256));
-    if (dtype == TGIS_F16)
-        hipLaunchKernelGGL(dense_prepare_kernel<f16>, grid, dim3(256), 0, (hipStream_t)stream, (const f16*)w,
-                           (f16*)prepared, N, K, NT, KS, flags);
-    else
-        hipLaunchKernelGGL(dense_prepare_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)w,
-                           (bf16*)prepared, N, K, NT, KS, flags);
-    TGIS_CHECK_LAUNCH();
-    return TGIS_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = type_of<decltype(t)>;
+        hipLaunchKernelGGL(dense_prepare_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)w, (T*)prepared, N,
+                           K, NT, KS, flags);
+        TGIS_CHECK_LAUNCH();
+        return TGIS_OK;
+    });
 }
 
 extern "C" int64_t tgis_dense_gemm_workspace_bytes(int64_t M, int64_t K, int64_t N) {
@@ -271,8 +259,7 @@ extern "C" int tgis_dense_gemm(const void* x, int64_t ldx, const void* prepared,
     DenseArgs a;
     dense_fill(a, x, ldx, prepared, bias, out, ldo, M, K, N, out_f32, (float*)((uint8_t*)workspace + 4096), 0, pl);
     a.gelu = gelu;
-    return dtype == TGIS_F16 ? launch_dense<f16>(a, pl, act, cdiv64(M, 32), st)
-                             : launch_dense<bf16>(a, pl, act, cdiv64(M, 32), st);
+    return by_dtype(dtype, [&](auto t) { return launch_dense<type_of<decltype(t)>>(a, pl, act, cdiv64(M, 32), st); });
 }
 
 // ---- qkv projection with the rotary embedding and the cache write in its epilogue (dense weights) ---------------------
@@ -318,8 +305,7 @@ static int dense_gemm_rope_impl(const void* x, int64_t ldx, const void* prepared
         a.k_scale = k_scale;
         a.v_scale = v_scale;
     }
-    return dtype == TGIS_F16 ? launch_dense<f16>(a, pl, act, cdiv64(M, 32), st)
-                             : launch_dense<bf16>(a, pl, act, cdiv64(M, 32), st);
+    return by_dtype(dtype, [&](auto t) { return launch_dense<type_of<decltype(t)>>(a, pl, act, cdiv64(M, 32), st); });
 }
 
 extern "C" int tgis_dense_gemm_rope(const void* x, int64_t ldx, const void* prepared, const void* bias,
@@ -360,8 +346,7 @@ extern "C" int tgis_dense_gemm_partial(const void* x, int64_t ldx, const void* p
     TgisTimedScope timed(TGIS_OP_DENSE_GEMM, st);
     DenseArgs a;
     dense_fill(a, x, ldx, prepared, nullptr, nullptr, 0, M, K, N, 0, slabs, 1, pl);
-    return dtype == TGIS_F16 ? launch_dense<f16>(a, pl, act, cdiv64(M, 32), st)
-                             : launch_dense<bf16>(a, pl, act, cdiv64(M, 32), st);
+    return by_dtype(dtype, [&](auto t) { return launch_dense<type_of<decltype(t)>>(a, pl, act, cdiv64(M, 32), st); });
 }
 
 // tgis_debug_gemm_plan (gptq.hip) for the dense entry points: info as documented there

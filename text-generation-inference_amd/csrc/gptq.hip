@@ -17,7 +17,7 @@
 #include <vector>
 #include <mutex>
 #include "common.h"
-#include <type_traits>
+#include "dispatch.h"
 #include "gptq_gemm_body.h"
 #include "gptq_wide_body.h"
 
@@ -377,7 +377,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_silu_kernel(const float* __
 
 }  // namespace
 
-// shared with gptq_lean.hip (declared in gptq_gemm_body.h)
+// every split-K sum of this file (declared in gptq_gemm_body.h)
 int gptq::reduce_slabs(const float* slabs, const f16* bias, f16* out, int64_t ldo, int M, int N, int NP, int S,
                        hipStream_t st) {
     dim3 rgrid((unsigned)cdiv64((int64_t)32 * (NP / 4), 256), (unsigned)cdiv64(M, 32));
@@ -519,18 +519,32 @@ static TallPlan plan_tall(int64_t M, int64_t K, int64_t N, int act) {
 }
 static int64_t tall_slab_bytes(int64_t M, int64_t N, int S) { return (int64_t)cdiv64(M, 32) * S * 32 * cdiv64(N, 32) * 32 * 4; }
 
-static int launch_tall(const void* x, int64_t ldx, const void* prepared, const void* bias, void* out, int64_t ldo,
-                       int64_t M, int64_t K, int64_t N, int64_t groups, int act, float* slabs, int partial,
-                       const TallPlan& tp, hipStream_t st) {
-    PrepLayout p = prep_layout(K, N, groups);
-    const int64_t gs = K / groups, spg = gs / 64;
-    GemmArgs a;
+// The rotary epilogue's operands (act 3; act 4: into a one-byte cache, with its scales)
+struct RopeEpi {
+    const int32_t *positions, *slots;
+    const f16 *cosb, *sinb;
+    f16 *kpool, *vpool;
+    int H, Hkv, D;
+    float k_scale = 1.f, v_scale = 1.f;
+};
+
+struct KSplit {
+    int KR, S;  // k range per block and global k splits of the family's plan
+};
+
+// Every field of the launch arguments, for every kernel family
+static void fill_args(GemmArgs& a, const void* x, int64_t ldx, const void* prepared, const PrepLayout& p, const void* bias,
+                      const int32_t* perm, void* out, int64_t ldo, int64_t M, int64_t K, int64_t N, int64_t groups,
+                      KSplit ks, float* slabs, int partial, const RopeEpi* rope = nullptr) {
+    static const RopeEpi no_rope{};
+    const RopeEpi& r = rope ? *rope : no_rope;
+    const int64_t gs = K / groups, spg = gs / 64;  // k64-steps per group
     a.x = (const f16*)x;
     a.ldx = ldx;
     a.prep = (const uint8_t*)prepared;
     a.offB = p.offB;
-    a.bias = partial ? nullptr : (const f16*)bias;
-    a.perm = nullptr;
+    a.bias = (const f16*)bias;
+    a.perm = perm;
     a.out = (f16*)out;
     a.ldo = ldo;
     a.M = (int)M;
@@ -538,49 +552,63 @@ static int launch_tall(const void* x, int64_t ldx, const void* prepared, const v
     a.N = (int)N;
     a.G = (int)groups;
     a.gs = (int)gs;
-    a.KR = tp.KR;
-    a.S = tp.S;
+    a.KR = ks.KR;
+    a.S = ks.S;
     a.NT = (int)p.NT;
     a.KS = (int)p.KS;
     a.slabs = slabs;
     a.partial = partial;
     a.spg_shift = 30;
-    a.positions = a.slots = nullptr;
-    a.cosb = a.sinb = nullptr;
-    a.kpool = a.vpool = nullptr;
-    a.rH = a.rHkv = a.rD = 0;
-    if (groups > 1)
+    if (groups > 1 && gptq_group64(K, groups))
         for (a.spg_shift = 0; (1 << a.spg_shift) < spg; ++a.spg_shift) {}
+    a.positions = r.positions;
+    a.slots = r.slots;
+    a.cosb = r.cosb;
+    a.sinb = r.sinb;
+    a.kpool = r.kpool;
+    a.vpool = r.vpool;
+    a.rH = r.H;
+    a.rHkv = r.Hkv;
+    a.rD = r.D;
+    a.k_scale = r.k_scale;
+    a.v_scale = r.v_scale;
+}
+
+template <int BMR, int ACT, int TW>
+static int launch_tall_one(dim3 grid, size_t lds, hipStream_t st, const GemmArgs& a) {
+    static bool attr = false;
+    if (!attr) {
+        TGIS_CHECK_HIP(hipFuncSetAttribute((const void*)gptq_gemm_tall_kernel<BMR, ACT, TW>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 128 * TRS * 2));
+        attr = true;
+    }
+    hipLaunchKernelGGL((gptq_gemm_tall_kernel<BMR, ACT, TW>), grid, dim3(256), lds, st, a);
+    return TGIS_OK;
+}
+
+// tall_ok() holds (checked by choose_gptq): no permutation, groups of 64 * 2^n rows
+static int launch_tall(const void* x, int64_t ldx, const void* prepared, const void* bias, void* out, int64_t ldo,
+                       int64_t M, int64_t K, int64_t N, int64_t groups, int act, float* slabs, int partial,
+                       const TallPlan& tp, hipStream_t st) {
+    PrepLayout p = prep_layout(K, N, groups);
+    GemmArgs a;
+    fill_args(a, x, ldx, prepared, p, partial ? nullptr : bias, nullptr, out, ldo, M, K, N, groups, {tp.KR, tp.S}, slabs,
+              partial);
     const int BM = 32 * tp.BMR;
     TGIS_CHECK_ARG(cdiv64(M, BM) <= 65535, "tgis_gptq_gemm: M too large for one launch");
     dim3 grid((unsigned)cdiv64(p.NT, 4 * tp.TW), (unsigned)cdiv64(M, BM), (unsigned)tp.S);
     const size_t lds = (size_t)2 * BM * TRS * sizeof(f16);
-#define TGIS_TALL(B, A, W)                                                                                     \
-    do {                                                                                                      \
-        static bool attr = false;                                                                             \
-        if (!attr) {                                                                                          \
-            TGIS_CHECK_HIP(hipFuncSetAttribute((const void*)gptq_gemm_tall_kernel<B, A, W>,                   \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 128 * TRS * 2)); \
-            attr = true;                                                                                      \
-        }                                                                                                     \
-        hipLaunchKernelGGL((gptq_gemm_tall_kernel<B, A, W>), grid, dim3(256), lds, st, a);                    \
-    } while (0)
-    if (tp.BMR == 4 && tp.TW == 2) {
-        if (act == 2) TGIS_TALL(4, 2, 2); else TGIS_TALL(4, 0, 2);
-    } else if (tp.BMR == 4) {
-        if (act == 2) TGIS_TALL(4, 2, 1); else TGIS_TALL(4, 0, 1);
-    } else {
-        if (act == 2) TGIS_TALL(2, 2, 1); else TGIS_TALL(2, 0, 1);
-    }
-#undef TGIS_TALL
+    // two tiles per wave with 128-row blocks only
+    const int rc = by_pair<pair_c<4, 2>, pair_c<4, 1>, pair_c<2, 1>>(tp.BMR, tp.TW, "tgis_gptq_gemm: tall plan (BMR, TW)",
+                                                                     [&](auto bw) {
+        constexpr int BMR = decltype(bw)::first, TW = decltype(bw)::second;
+        return by_bool(act == 2, [&](auto silu) {
+            return launch_tall_one<BMR, decltype(silu)::value ? 2 : 0, TW>(grid, lds, st, a);
+        });
+    });
+    if (rc != TGIS_OK) return rc;
     TGIS_CHECK_LAUNCH();
-    if (!partial && tp.S > 1) {
-        const int NP = (int)p.NT * 32;
-        dim3 rgrid((unsigned)cdiv64((int64_t)32 * (NP / 4), 256), (unsigned)cdiv64(M, 32));
-        hipLaunchKernelGGL(splitk_reduce_f16_kernel, rgrid, dim3(256), 0, st, slabs, (const f16*)bias, (f16*)out, ldo,
-                           (int)M, (int)N, NP, tp.S);
-        TGIS_CHECK_LAUNCH();
-    }
+    if (!partial && tp.S > 1) return gptq::reduce_slabs(a.slabs, a.bias, a.out, a.ldo, a.M, a.N, a.NT * 32, a.S, st);
     return TGIS_OK;
 }
 
@@ -609,9 +637,13 @@ static int launch_one(dim3 grid, size_t lds, hipStream_t st, const GemmArgs& a) 
     hipLaunchKernelGGL((gptq_gemm_kernel<TN, WK, ACT, G64, PERM, MR>), grid, dim3(64 * TN * WK), lds, st, a);
     return TGIS_OK;
 }
+// 32-row blocks of x per pass of the streaming kernel a plan runs: 64-row passes exist for two-k-part blocks only (LDS)
+static int gemm_row_class(const GemmPlan& pl) { return pl.WK == 2 ? pl.MR : 1; }
+
+// mr comes from gemm_row_class; the guard only keeps the 64-row instance from being compiled for four-k-part blocks
 template <int TN, int WK, int ACT, bool G64, bool PERM>
 static int launch_variant(int mr, dim3 grid, size_t lds, hipStream_t st, const GemmArgs& a) {
-    if constexpr (WK == 2) {  // 64-row passes exist for two-k-part blocks only (LDS)
+    if constexpr (WK == 2) {
         if (mr == 2) return launch_one<TN, WK, ACT, G64, PERM, 2>(grid, lds, st, a);
     }
     return launch_one<TN, WK, ACT, G64, PERM, 1>(grid, lds, st, a);
@@ -621,14 +653,6 @@ static int64_t silu_split_below() {  // blocks of the unsplit plan under which a
     static const int64_t v = getenv("TGIS_SILU_SPLIT_BELOW") ? atoll(getenv("TGIS_SILU_SPLIT_BELOW")) : 128;
     return v;
 }
-
-struct RopeEpi {
-    const int32_t *positions, *slots;
-    const f16 *cosb, *sinb;
-    f16 *kpool, *vpool;
-    int H, Hkv, D;
-    float k_scale = 1.f, v_scale = 1.f;  // one-byte cache (launch_gptq act 4)
-};
 
 template <int CT, int ACT, bool OUTF, int MR>
 static int launch_wide_mr(dim3 grid, hipStream_t st, const GemmArgs& a) {
@@ -652,134 +676,52 @@ static int launch_gptq(const void* x, int64_t ldx, const void* prepared, const v
                        int partial, const GemmPlan& pl, hipStream_t st, const RopeEpi* rope = nullptr) {
     PrepLayout p = prep_layout(K, N, groups);
     const int64_t mslabs = cdiv64(M, 32 * pl.MR);  // passes over the weights
-    const int64_t gs = K / groups;
-    const int64_t spg = gs / 64;  // k64-steps per group
-    const bool group64 = gptq_group64(K, groups);
     GemmArgs a;
-    a.x = (const f16*)x;
-    a.ldx = ldx;
-    a.prep = (const uint8_t*)prepared;
-    a.offB = p.offB;
-    a.bias = (const f16*)bias;
-    a.perm = perm;
-    a.out = (f16*)out;
-    a.ldo = ldo;
-    a.M = (int)M;
-    a.K = (int)K;
-    a.N = (int)N;
-    a.G = (int)groups;
-    a.gs = (int)gs;
-    a.KR = pl.KR;
-    a.S = pl.S;
-    a.NT = (int)p.NT;
-    a.KS = (int)p.KS;
-    a.slabs = slabs;
-    a.partial = partial;
-    a.spg_shift = 30;
-    a.positions = a.slots = nullptr;
-    a.cosb = a.sinb = nullptr;
-    a.kpool = a.vpool = nullptr;
-    a.rH = a.rHkv = a.rD = 0;
-    a.k_scale = a.v_scale = 1.f;
-    if (rope) {
-        a.positions = rope->positions;
-        a.slots = rope->slots;
-        a.cosb = rope->cosb;
-        a.sinb = rope->sinb;
-        a.kpool = rope->kpool;
-        a.vpool = rope->vpool;
-        a.rH = rope->H;
-        a.rHkv = rope->Hkv;
-        a.rD = rope->D;
-        a.k_scale = rope->k_scale;
-        a.v_scale = rope->v_scale;
-    }
-    if (groups > 1 && group64)
-        for (a.spg_shift = 0; (1 << a.spg_shift) < spg; ++a.spg_shift) {}
+    fill_args(a, x, ldx, prepared, p, bias, perm, out, ldo, M, K, N, groups, {pl.KR, pl.S}, slabs, partial, rope);
     if (ldx == TGIS_LD_FRAGMENTS) {
         // activation in fragment order: the kernel of gptq_wide_body.h; `pl` carries its plan as TN = CT, S (callers use
-        // wide_plan_as_gemm_plan); checked by the caller: wide_serves(), act in {0, 2, 3}, no permutation
+        // wide_plan_as_gemm_plan); checked by the caller: wide_serves(), act in {0, 2, 3, 4}, no permutation
         const bool outf = ldo == TGIS_LD_FRAGMENTS;
         dim3 wgrid((unsigned)cdiv64(p.NT, pl.TN), (unsigned)pl.S);
-#define TGIS_WIDE(CT)                                                                                   \
-    do {                                                                                                \
-        int rc_ = act == 3   ? launch_wide_one<CT, 3, false>(wgrid, st, a)                              \
-                  : act == 4 ? launch_wide_one<CT, 4, false>(wgrid, st, a)                              \
-                  : act == 2 ? (outf ? launch_wide_one<CT, 2, true>(wgrid, st, a)                       \
-                                     : launch_wide_one<CT, 2, false>(wgrid, st, a))                     \
-                             : launch_wide_one<CT, 0, false>(wgrid, st, a);                             \
-        if (rc_ != TGIS_OK) return rc_;                                                                 \
-    } while (0)
-        if (pl.TN == 4) TGIS_WIDE(4); else if (pl.TN == 3) TGIS_WIDE(3); else if (pl.TN == 1) TGIS_WIDE(1); else TGIS_WIDE(2);
-#undef TGIS_WIDE
+        const int rc = by_int<4, 3, 2, 1>(pl.TN, "tgis_gptq_gemm: fragment-order plan CT", [&](auto ct) {
+            constexpr int CT = decltype(ct)::value;
+            return by_int<0, 2, 3, 4>(act, "tgis_gptq_gemm: fragment-order act", [&](auto ac) {
+                constexpr int ACT = decltype(ac)::value;
+                if constexpr (ACT == 2)  // only the SiLU * up output can leave in fragment order
+                    return by_bool(outf, [&](auto of) { return launch_wide_one<CT, 2, decltype(of)::value>(wgrid, st, a); });
+                else
+                    return launch_wide_one<CT, ACT, false>(wgrid, st, a);
+            });
+        });
+        if (rc != TGIS_OK) return rc;
         TGIS_CHECK_LAUNCH();
-        if (!partial && pl.S > 1) {
-            const int NP = (int)p.NT * 32;
-            dim3 rgrid((unsigned)cdiv64((int64_t)32 * (NP / 4), 256), (unsigned)cdiv64(M, 32));
-            hipLaunchKernelGGL(splitk_reduce_f16_kernel, rgrid, dim3(256), 0, st, a.slabs, a.bias, a.out, a.ldo, a.M, a.N,
-                               NP, a.S);
-            TGIS_CHECK_LAUNCH();
-        }
+        if (!partial && pl.S > 1) return gptq::reduce_slabs(a.slabs, a.bias, a.out, a.ldo, a.M, a.N, a.NT * 32, a.S, st);
         return TGIS_OK;
     }
     dim3 grid((unsigned)cdiv64(p.NT, pl.TN), (unsigned)pl.S, (unsigned)mslabs);
     const size_t lds = (size_t)pl.WK * 2 * 32 * pl.MR * RS * sizeof(f16) + 64;  // x buffers + arrival counters
-#define TGIS_LAUNCH_GEMM(T, W, A, G, P)                                                        \
-    do {                                                                                       \
-        int rc_ = launch_variant<T, W, A, G, P>(pl.MR, grid, lds, st, a);                      \
-        if (rc_ != TGIS_OK) return rc_;                                                        \
-    } while (0)
-#define TGIS_LAUNCH_GEMM_W(A, G, P)                      \
-    do {                                                 \
-        const int tw = pl.TN * 10 + pl.WK;               \
-        if (tw == 44)                                    \
-            TGIS_LAUNCH_GEMM(4, 4, A, G, P);             \
-        else if (tw == 42)                               \
-            TGIS_LAUNCH_GEMM(4, 2, A, G, P);             \
-        else if (tw == 34)                               \
-            TGIS_LAUNCH_GEMM(3, 4, A, G, P);             \
-        else if (tw == 32)                               \
-            TGIS_LAUNCH_GEMM(3, 2, A, G, P);             \
-        else if (tw == 24)                               \
-            TGIS_LAUNCH_GEMM(2, 4, A, G, P);             \
-        else                                             \
-            TGIS_LAUNCH_GEMM(2, 2, A, G, P);             \
-    } while (0)
-    if (act == 3) {  // rope epilogue: 64 * 2^n groups, no act-order (checked by the caller)
-        TGIS_LAUNCH_GEMM_W(3, true, false);
-        TGIS_CHECK_LAUNCH();
-        return TGIS_OK;
-    }
-    if (act == 4) {  // the rope epilogue into a one-byte (e4m3) cache
-        TGIS_LAUNCH_GEMM_W(4, true, false);
-        TGIS_CHECK_LAUNCH();
-        return TGIS_OK;
-    }
-    const int variant = (act == 1 ? 4 : act == 2 ? 8 : 0) | (group64 ? 2 : 0) | (perm ? 1 : 0);
-    switch (variant) {
-        case 8: TGIS_LAUNCH_GEMM_W(2, false, false); break;
-        case 9: TGIS_LAUNCH_GEMM_W(2, false, true); break;
-        case 10: TGIS_LAUNCH_GEMM_W(2, true, false); break;
-        case 11: TGIS_LAUNCH_GEMM_W(2, true, true); break;
-        case 0: TGIS_LAUNCH_GEMM_W(0, false, false); break;
-        case 1: TGIS_LAUNCH_GEMM_W(0, false, true); break;
-        case 2: TGIS_LAUNCH_GEMM_W(0, true, false); break;
-        case 3: TGIS_LAUNCH_GEMM_W(0, true, true); break;
-        case 4: TGIS_LAUNCH_GEMM_W(1, false, false); break;
-        case 5: TGIS_LAUNCH_GEMM_W(1, false, true); break;
-        case 6: TGIS_LAUNCH_GEMM_W(1, true, false); break;
-        case 7: TGIS_LAUNCH_GEMM_W(1, true, true); break;
-    }
-#undef TGIS_LAUNCH_GEMM_W
-#undef TGIS_LAUNCH_GEMM
+    const int mr = gemm_row_class(pl);
+    const bool group64 = gptq_group64(K, groups);
+    const int rc = by_pair<pair_c<4, 4>, pair_c<4, 2>, pair_c<3, 4>, pair_c<3, 2>, pair_c<2, 4>, pair_c<2, 2>>(
+        pl.TN, pl.WK, "tgis_gptq_gemm: plan (TN, WK)", [&](auto tw) {
+        constexpr int TN = decltype(tw)::first, WK = decltype(tw)::second;
+        return by_int<0, 1, 2, 3, 4>(act, "tgis_gptq_gemm: act", [&](auto ac) {
+            constexpr int ACT = decltype(ac)::value;
+            if constexpr (ACT >= 3) {  // rope epilogues (4: into a one-byte e4m3 cache): 64 * 2^n groups, no act-order (caller)
+                return launch_variant<TN, WK, ACT, true, false>(mr, grid, lds, st, a);
+            } else {
+                return by_bool(group64, [&](auto g) {
+                    return by_bool(perm != nullptr, [&](auto pm) {
+                        return launch_variant<TN, WK, ACT, decltype(g)::value, decltype(pm)::value>(mr, grid, lds, st, a);
+                    });
+                });
+            }
+        });
+    });
+    if (rc != TGIS_OK) return rc;
     TGIS_CHECK_LAUNCH();
-    if (!partial && pl.S > 1 && !getenv("TGIS_GPTQ_NOREDUCE")) {
-        const int NP = (int)p.NT * 32;
-        dim3 rgrid((unsigned)cdiv64((int64_t)32 * (NP / 4), 256), (unsigned)cdiv64(M, 32));
-        hipLaunchKernelGGL(splitk_reduce_f16_kernel, rgrid, dim3(256), 0, st, a.slabs, a.bias, a.out, a.ldo, a.M, a.N,
-                           NP, a.S);
-        TGIS_CHECK_LAUNCH();
-    }
+    if (!partial && pl.S > 1 && !getenv("TGIS_GPTQ_NOREDUCE"))
+        return gptq::reduce_slabs(a.slabs, a.bias, a.out, a.ldo, a.M, a.N, a.NT * 32, a.S, st);
     return TGIS_OK;
 }
 
@@ -1042,7 +984,7 @@ extern "C" int tgis_debug_gemm_plan(int entry, int64_t M, int64_t K, int64_t N, 
         info[12] = finished && c.pl.S > 1;
         return TGIS_OK;
     }
-    info[5] = c.pl.WK == 2 ? c.pl.MR : 1;  // launch_variant: 64-row passes for two-k-part blocks only
+    info[5] = gemm_row_class(c.pl);
     info[8] = c.family == FAM_GPTQ_ROPE ? 3 : c.family == FAM_SPLIT_SILU ? 0 : act;
     info[9] = c.family == FAM_GPTQ_ROPE || gptq_group64(K, groups);
     info[10] = act_order != 0 && c.family != FAM_GPTQ_ROPE;

@@ -5,6 +5,7 @@
 //   y   = norm(res) * weight (+ bias)   [statistics in fp32 from the fp32 sum, one rounding at the end]
 // One 256-thread workgroup per row, 16-byte loads, row cached in registers (hidden <= 16384).
 #include "common.h"
+#include "dispatch.h"
 #include "rowwise_plan.h"
 
 namespace {
@@ -153,25 +154,19 @@ static int launch_norm(const void* x, const void* residual, const void* weight, 
     hipStream_t st = (hipStream_t)stream;
     TgisTimedScope timed(TGIS_OP_NORM, st);
     const bool wide = choose_norm(rows, hidden).nt == 512;
-#define TGIS_NORM_LAUNCH(T, P)                                                                                   \
-    do {                                                                                                         \
-        if (wide)                                                                                                \
-            hipLaunchKernelGGL((norm_kernel<T, RMS, P, 512>), dim3((unsigned)rows), dim3(512), 0, st, (const T*)x, \
-                               (const T*)residual, (const T*)weight, (const T*)bias, (T*)y, (T*)res_out,         \
-                               (int)hidden, eps, slabs, S, slab_ld, (const T*)xbias, y_frag);                    \
-        else                                                                                                     \
-            hipLaunchKernelGGL((norm_kernel<T, RMS, P, 256>), dim3((unsigned)rows), dim3(256), 0, st, (const T*)x, \
-                               (const T*)residual, (const T*)weight, (const T*)bias, (T*)y, (T*)res_out,         \
-                               (int)hidden, eps, slabs, S, slab_ld, (const T*)xbias, y_frag);                    \
-    } while (0)
-    if (dtype == TGIS_F16) {
-        if (slabs) TGIS_NORM_LAUNCH(f16, true); else TGIS_NORM_LAUNCH(f16, false);
-    } else {
-        if (slabs) TGIS_NORM_LAUNCH(bf16, true); else TGIS_NORM_LAUNCH(bf16, false);
-    }
-#undef TGIS_NORM_LAUNCH
-    TGIS_CHECK_LAUNCH();
-    return TGIS_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = type_of<decltype(t)>;
+        return by_bool(slabs != nullptr, [&](auto partial) {
+            return by_bool(wide, [&](auto w) {
+                constexpr int NT = decltype(w)::value ? 512 : 256;
+                hipLaunchKernelGGL((norm_kernel<T, RMS, decltype(partial)::value, NT>), dim3((unsigned)rows), dim3(NT), 0,
+                                   st, (const T*)x, (const T*)residual, (const T*)weight, (const T*)bias, (T*)y,
+                                   (T*)res_out, (int)hidden, eps, slabs, S, slab_ld, (const T*)xbias, y_frag);
+                TGIS_CHECK_LAUNCH();
+                return TGIS_OK;
+            });
+        });
+    });
 }
 
 // Parallel-residual layer boundary of GPT-NeoX (flash_neox_modeling.py:238-259): h' = h + A + B (+ biases) and two
@@ -305,18 +300,17 @@ static int launch_layernorm2(const void* h, const Addend& A, const Addend& B, co
     hipStream_t st = (hipStream_t)stream;
     TgisTimedScope timed(TGIS_OP_NORM, st);
     const bool wide = choose_norm(rows, hidden).nt == 512;
-#define TGIS_LN2_LAUNCH(T, NT)                                                                                       \
-    hipLaunchKernelGGL((layernorm2_kernel<T, NT>), dim3((unsigned)rows), dim3(NT), 0, st, (const T*)h, A, B,         \
-                       (const T*)w1, (const T*)b1, (const T*)w2, (const T*)b2, (T*)y1, (T*)y2, (T*)res_out,          \
-                       (int)hidden, eps)
-    if (dtype == TGIS_F16) {
-        if (wide) TGIS_LN2_LAUNCH(f16, 512); else TGIS_LN2_LAUNCH(f16, 256);
-    } else {
-        if (wide) TGIS_LN2_LAUNCH(bf16, 512); else TGIS_LN2_LAUNCH(bf16, 256);
-    }
-#undef TGIS_LN2_LAUNCH
-    TGIS_CHECK_LAUNCH();
-    return TGIS_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = type_of<decltype(t)>;
+        return by_bool(wide, [&](auto w) {
+            constexpr int NT = decltype(w)::value ? 512 : 256;
+            hipLaunchKernelGGL((layernorm2_kernel<T, NT>), dim3((unsigned)rows), dim3(NT), 0, st, (const T*)h, A, B,
+                               (const T*)w1, (const T*)b1, (const T*)w2, (const T*)b2, (T*)y1, (T*)y2, (T*)res_out,
+                               (int)hidden, eps);
+            TGIS_CHECK_LAUNCH();
+            return TGIS_OK;
+        });
+    });
 }
 
 }  // namespace

@@ -9,6 +9,7 @@
 //   V: [4 column groups][D][8], token tok in column (i>>2)*8 + tile*4 + (i&3), i = tok&15 (kv_layout.h)
 #include <algorithm>
 #include "common.h"
+#include "dispatch.h"
 #include "kv_layout.h"
 #include "rowwise_plan.h"
 
@@ -260,26 +261,20 @@ static int rope_launch(void* qkv, int64_t ld_qkv, const void* cos, const void* s
     const RopePlan plan = choose_rope(T, H, Hkv, D, rot_dim, cos != nullptr);
     const dim3 grid((unsigned)T, (unsigned)plan.gy);
     const bool gen = plan.gen;
-#define TGIS_ROPE_LAUNCH_KV(T, KV, G)                                                                                  \
-    do {                                                                                                               \
-        PartialIn<T> pin{slabs, S, slab_ld, (const T*)bias};                                                           \
-        hipLaunchKernelGGL((rope_kv_kernel<T, KV, G>), grid, dim3(256), 0, st, (T*)qkv, ld_qkv, (const T*)cos,         \
-                           (const T*)sin, positions, slots, (KV*)k_pool, (KV*)v_pool, H, Hkv, D, rot_dim, pin,         \
-                           k_scale, v_scale);                                                                          \
-    } while (0)
-#define TGIS_ROPE_LAUNCH(T, G)                                                                                         \
-    do {                                                                                                               \
-        if (kv_dtype == TGIS_KV_FP8_E4M3) TGIS_ROPE_LAUNCH_KV(T, uint8_t, G); else TGIS_ROPE_LAUNCH_KV(T, T, G);       \
-    } while (0)
-    if (dtype == TGIS_F16) {
-        if (gen) TGIS_ROPE_LAUNCH(f16, true); else TGIS_ROPE_LAUNCH(f16, false);
-    } else {
-        if (gen) TGIS_ROPE_LAUNCH(bf16, true); else TGIS_ROPE_LAUNCH(bf16, false);
-    }
-#undef TGIS_ROPE_LAUNCH
-#undef TGIS_ROPE_LAUNCH_KV
-    TGIS_CHECK_LAUNCH();
-    return TGIS_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = type_of<decltype(t)>;
+        return by_kv<T>(kv_dtype == TGIS_KV_FP8_E4M3, [&](auto kv) {
+            using KV = type_of<decltype(kv)>;
+            return by_bool(gen, [&](auto g) {
+                PartialIn<T> pin{slabs, S, slab_ld, (const T*)bias};
+                hipLaunchKernelGGL((rope_kv_kernel<T, KV, decltype(g)::value>), grid, dim3(256), 0, st, (T*)qkv, ld_qkv,
+                                   (const T*)cos, (const T*)sin, positions, slots, (KV*)k_pool, (KV*)v_pool, H, Hkv, D,
+                                   rot_dim, pin, k_scale, v_scale);
+                TGIS_CHECK_LAUNCH();
+                return TGIS_OK;
+            });
+        });
+    });
 }
 
 extern "C" int tgis_rope_kv_write(void* qkv, int64_t ld_qkv, const void* cos, const void* sin,
@@ -341,24 +336,19 @@ static int rope_prefill_launch(void* qkv, int64_t ld_qkv, const void* cos, const
     const dim3 grid((unsigned)(B * pps), (unsigned)Hkv);
     const size_t lds = (size_t)32 * (D + 8) * 2;
     const bool gen = plan.gen;
-#define TGIS_ROPE_PREFILL_LAUNCH_KV(T, KV, G)                                                                           \
-    hipLaunchKernelGGL((rope_kv_prefill_kernel<T, KV, G>), grid, dim3(256), lds, st, (const T*)qkv, ld_qkv,             \
-                       (const T*)cos, (const T*)sin, positions, cu_seqlens, block_tables, max_pages, (KV*)k_pool,       \
-                       (KV*)v_pool, H, Hkv, D, rot_dim, pps, k_scale, v_scale)
-#define TGIS_ROPE_PREFILL_LAUNCH(T, G)                                                                                  \
-    do {                                                                                                                \
-        if (kv_dtype == TGIS_KV_FP8_E4M3) TGIS_ROPE_PREFILL_LAUNCH_KV(T, uint8_t, G);                                   \
-        else TGIS_ROPE_PREFILL_LAUNCH_KV(T, T, G);                                                                      \
-    } while (0)
-    if (dtype == TGIS_F16) {
-        if (gen) TGIS_ROPE_PREFILL_LAUNCH(f16, true); else TGIS_ROPE_PREFILL_LAUNCH(f16, false);
-    } else {
-        if (gen) TGIS_ROPE_PREFILL_LAUNCH(bf16, true); else TGIS_ROPE_PREFILL_LAUNCH(bf16, false);
-    }
-#undef TGIS_ROPE_PREFILL_LAUNCH
-#undef TGIS_ROPE_PREFILL_LAUNCH_KV
-    TGIS_CHECK_LAUNCH();
-    return TGIS_OK;
+    return by_dtype(dtype, [&](auto t) {
+        using T = type_of<decltype(t)>;
+        return by_kv<T>(kv_dtype == TGIS_KV_FP8_E4M3, [&](auto kv) {
+            using KV = type_of<decltype(kv)>;
+            return by_bool(gen, [&](auto g) {
+                hipLaunchKernelGGL((rope_kv_prefill_kernel<T, KV, decltype(g)::value>), grid, dim3(256), lds, st,
+                                   (const T*)qkv, ld_qkv, (const T*)cos, (const T*)sin, positions, cu_seqlens, block_tables,
+                                   max_pages, (KV*)k_pool, (KV*)v_pool, H, Hkv, D, rot_dim, pps, k_scale, v_scale);
+                TGIS_CHECK_LAUNCH();
+                return TGIS_OK;
+            });
+        });
+    });
 }
 
 extern "C" int tgis_rope_kv_write_prefill(void* qkv, int64_t ld_qkv, const void* cos, const void* sin,
