@@ -322,6 +322,17 @@ int tgis_attn_paged_kv8(const void* q, int64_t ld_q, const void* k_pool, const v
                         int num_splits, void* workspace, int64_t workspace_bytes, void* stream, int kv_dtype,
                         float k_scale, float v_scale);
 
+/* ---- KV-cache statistics (replaces nothing in the reference, which has no quantised cache: the calibration pass of the
+ *      one-byte cache, utils/kv_cache.py) -------------------------------------------------------------- */
+/* Max |x| per kv head over the tokens that B sequences hold in ONE layer's 16-bit pools (dtype TGIS_F16 / TGIS_BF16; D 64,
+ * 96 or 128), max-merged into out [2][Hkv] fp32: row 0 = k (as cached: after rotary), row 1 = v.  The caller zeroes `out`
+ * once; calls accumulate (a max is exact in any order: the result is bit-identical to a host restatement).
+ *   block_tables [B, max_pages] int32, ctx_lens [B] int32: only tokens < ctx_lens[b] count — the slots past the last token
+ *   of a partly filled page are ignored, table entries past a sequence's last page are never dereferenced, ctx_lens[b] = 0
+ *   contributes nothing.  No allocation, no sync; B = 0 returns TGIS_OK. */
+int tgis_kv_absmax(const void* k_pool, const void* v_pool, const int32_t* block_tables, int64_t max_pages,
+                   const int32_t* ctx_lens, int64_t B, int Hkv, int D, int dtype, float* out, void* stream);
+
 /* ---- elementwise --------------------------------------------------------------------------------- */
 /* out[T,I] = act(gate_up[T,0:I]) * gate_up[T,I:2I]; act 1 = SiLU (flash_llama_modeling.py:332-335). */
 int tgis_act_mul(const void* gate_up, void* out, int64_t T, int64_t I, int act, int dtype, void* stream);

@@ -30,6 +30,7 @@ def _device_for(rank: int, world_size: int) -> torch.device:
 class BaseInferenceEngine:
     def __init__(self, model_path: Optional[str], model_config: Optional[Any], tokenizer=None) -> None:
         self.model = None  # set by the plugin once the weights are loaded
+        self.model_path = model_path  # the directory the weights come from (None: in-memory checkpoints)
         self.rank, self.world_size = _shard_env()
         self.device = _device_for(self.rank, self.world_size)
         self._config = model_config if model_config is not None else self._load_config(model_path)

@@ -31,8 +31,8 @@ from tgis_amd.models.model import Model
 from tgis_amd.models.types import Batch, GenerateError
 from tgis_amd.pb import generate_pb2
 from tgis_amd.utils.graph_segments import SegmentedGraph, no_gc_during_capture
-from tgis_amd.utils.kv_cache import (KV_CACHE_DTYPES, PAGE, PagedKVCache, kv_pool_dtype, pages_for_budget,
-                                     parse_kv_cache_dtype)
+from tgis_amd.utils.kv_cache import (KV_CACHE_DTYPES, KV_SCALES_HEADROOM, PAGE, PagedKVCache, kv_pool_dtype,
+                                     kv_scales_stats, pages_for_budget, parse_kv_cache_dtype, resolve_kv_scales)
 from tgis_amd.utils.token_types import InputTokens, TokenInfo
 from tgis_amd.utils.tokens import HeterogeneousNextTokenChooser, get_input_tokens_info, get_token_info
 
@@ -446,7 +446,7 @@ class FlashCausalLM(Model):
     def __init__(self, model_name: str, revision: Optional[str], deployment_framework: str, dtype: torch.dtype,
                  quantize: Optional[str], model_config: Union[Any] = None, auto_model_class=None,
                  max_sequence_length: Optional[int] = None, engine=None, kv_cache_pages: Optional[int] = None,
-                 kv_cache_dtype: Optional[str] = None):
+                 kv_cache_dtype: Optional[str] = None, kv_scales: Union[None, str, dict] = None):
         # KV cache element: "auto" (the model dtype) or "fp8_e4m3" (one byte, utils/kv_cache.py); None reads
         # TGIS_KV_CACHE_DTYPE.  Checked before anything is loaded — except on a rank of a tensor-parallel group, which first
         # tells its peers (_check_same_kv_dtype) so that they fail with it instead of waiting in that collective.
@@ -457,6 +457,8 @@ class FlashCausalLM(Model):
             if (getattr(engine, "world_size", 1) or 1) == 1:
                 raise
             self.kv_cache_dtype, self._kv_dtype_error = None, e
+        # kv_scales: the calibrated per-layer scales of a one-byte cache, the contents of a kv_cache_scales.json or its path
+        # (utils/kv_cache.py, resolve_kv_scales); None looks at TGIS_KV_SCALES, then next to the weights, else they stay 1.0
         if not torch.cuda.is_available():
             raise NotImplementedError("FlashCausalLM is only available on GPU")
         if engine is None:
@@ -499,6 +501,8 @@ class FlashCausalLM(Model):
         kv_cache_pages = self._agree_on_min(kv_cache_pages, engine)
         self.kv_cache = PagedKVCache(self.num_layers, self.num_kv_heads, self.head_size, kv_cache_pages, dtype,
                                      self.device, kv_dtype=self.kv_cache_dtype)
+        # before any page is written and any graph captured: both hold the scales
+        self._apply_kv_scales(kv_scales, engine)
         # tp > 1, TGIS_TP_GRAPHS = auto (default) | full | segments | false:
         #   full      one graph per step with the RCCL all-reduces / all-gather inside it (RCCL is capture-aware);
         #   segments  a chain of graphs with the collectives launched between them (utils/graph_segments.py);
@@ -608,6 +612,80 @@ class FlashCausalLM(Model):
             raise ValueError(f"tensor-parallel ranks disagree on the KV cache dtype (this rank: {self.kv_cache_dtype}; "
                              f"ranks use {KV_CACHE_DTYPES[lo]} and {KV_CACHE_DTYPES[hi]}): set TGIS_KV_CACHE_DTYPE alike "
                              f"on every rank")
+
+    def _apply_kv_scales(self, kv_scales, engine):
+        """Resolves the cache's scales (utils/kv_cache.py, resolve_kv_scales) and applies them.  Tensor parallel: rank 0
+        resolves, every rank applies rank 0's values — and a rank that fails (an unreadable file on rank 0, an explicit
+        argument with a 16-bit cache anywhere) tells its peers first, so that all of them raise instead of one waiting."""
+        world = engine.world_size if hasattr(engine, "world_size") else 1
+        pg = getattr(engine, "process_group", None)
+        tp = world > 1 and isinstance(pg, torch.distributed.ProcessGroup)
+        found, error = None, None
+        try:
+            if not tp or getattr(engine, "rank", 0) == 0:
+                found = resolve_kv_scales(kv_scales, self.kv_cache_dtype, self.num_layers, getattr(engine, "model_path", None))
+            elif kv_scales is not None and not self.kv_cache.is_fp8:
+                resolve_kv_scales(kv_scales, self.kv_cache_dtype, self.num_layers)  # raises: explicit scales, 16-bit cache
+        except (ValueError, OSError) as e:
+            if not tp:
+                raise
+            error = e
+        if tp:
+            dev = self.device if torch.distributed.get_backend(pg) == "nccl" else torch.device("cpu")
+            t = torch.zeros(1 + 2 * self.num_layers, dtype=torch.float64, device=dev)  # [found, k scales, v scales]
+            if found is not None:
+                t[0] = 1.0
+                t[1:] = torch.tensor(found[0] + found[1], dtype=torch.float64)
+            torch.distributed.broadcast(t, src=0, group=pg)
+            all_ok = self._agree_on_min(0 if error is None else -1, engine) == 0
+            if error is not None:
+                raise error
+            if not all_ok:
+                raise ValueError("another tensor-parallel rank could not resolve the KV cache scales")
+            vals = t.tolist()
+            found = (vals[1:1 + self.num_layers], vals[1 + self.num_layers:]) if vals[0] == 1.0 else None
+        if found is not None:
+            self.kv_cache.set_scales(*found)
+
+    def calibrate_kv_scales(self, batches, decode_steps: int = 0, headroom: float = KV_SCALES_HEADROOM) -> dict:
+        """The contents of a kv_cache_scales.json (utils/kv_cache.py) measured on this model: every generate_pb2.Batch of
+        `batches` is prefilled and decoded for `decode_steps` steps on the ordinary 16-bit cache, tgis_kv_absmax reads max |k|
+        and max |v| of its cached tokens layer by layer, and its pages go back to the pool.  Tensor parallel: every rank
+        runs it on the same batches; the heads of all ranks are reduced, every rank returns the same dict."""
+        if self.kv_cache.is_fp8:
+            raise ValueError("calibrate_kv_scales measures the 16-bit cache: build the model with kv_cache_dtype='auto'")
+        L, Hkv, D = self.num_layers, self.num_kv_heads, self.head_size
+        stats = torch.zeros((L, 2, Hkv), dtype=torch.float32, device=self.device)
+        tokens = 0
+        with self.context_manager():
+            for pb in batches:
+                if decode_steps and min(r.max_output_length for r in pb.requests) <= decode_steps:
+                    raise ValueError(f"{decode_steps} decode steps need requests with max_output_length > {decode_steps}")
+                batch, errs = self.batch_type.from_pb(pb, self.tokenizer, self.dtype, self.device, self.word_embeddings,
+                                                      self.prefix_cache, self.use_position_ids)
+                if errs:
+                    raise ValueError(f"calibration batch {pb.id}: {errs[0].message}")
+                try:
+                    self.generate_token(batch, first=True)
+                    for _ in range(decode_steps):
+                        self.generate_token(batch)
+                    cached = [n - 1 for n in batch.input_lengths]  # the token chosen last is not in the cache yet
+                    ctx = torch.tensor(cached, dtype=torch.int32, device=self.device)
+                    for l in range(L):
+                        native.kv_absmax(self.kv_cache.k_pool(l), self.kv_cache.v_pool(l), batch.block_tables, ctx, Hkv, D,
+                                         stats[l])
+                    tokens += sum(cached)
+                finally:
+                    batch.release()
+            absmax = stats.amax(dim=2)  # [L, 2] over this rank's heads
+            pg = self.process_group
+            if self.tp_world > 1 and isinstance(pg, torch.distributed.ProcessGroup):  # outside any capture
+                if torch.distributed.get_backend(pg) != "nccl":
+                    absmax = absmax.cpu()
+                torch.distributed.all_reduce(absmax, op=torch.distributed.ReduceOp.MAX, group=pg)
+            absmax = absmax.cpu().tolist()
+        return kv_scales_stats([a[0] for a in absmax], [a[1] for a in absmax], tokens, str(self.dtype).replace("torch.", ""),
+                               headroom)
 
     def _default_kv_pages(self) -> int:
         free, _total = torch.cuda.mem_get_info(self.device)

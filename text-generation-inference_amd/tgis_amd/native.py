@@ -94,6 +94,7 @@ SIGNATURES = {
                                  _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_int, _vp, _c_i64, _vp]),
     "tgis_attn_paged_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int,
                                      _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_int, _vp, _c_i64, _vp] + _KV8_ARGS),
+    "tgis_kv_absmax": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _c_int, _vp, _vp]),
     "tgis_act_mul": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _c_int, _vp]),
     "tgis_gelu": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_int, _vp]),
     "tgis_embedding": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp]),
@@ -709,6 +710,20 @@ def attn_paged(q, ld_q: int, k_pool, v_pool, block_tables, ctx_lens, cu_seqlens_
             _ptr(cu_seqlens_q), optr, ldo, B, H, Hkv, D, max_q_len, max_ctx, float(scale), dtype_code(q.dtype), num_splits,
             wptr, wbytes, _stream())
     _call_kv("tgis_attn_paged", args, k_pool, v_pool, kv_scales)
+    return out
+
+
+def kv_absmax(k_pool, v_pool, block_tables, ctx_lens, Hkv: int, D: int, out):
+    """Max-merges max |k| and max |v| per kv head over the cached tokens of block_tables / ctx_lens into out [2, Hkv] fp32
+    (row 0 = k, row 1 = v; zeroed once by the caller, calls accumulate).  One layer's 16-bit pools only: the statistic is
+    taken from a model running its ordinary cache."""
+    assert block_tables.dtype == torch.int32 and ctx_lens.dtype == torch.int32 and block_tables.is_contiguous()
+    assert k_pool.dtype == v_pool.dtype and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == 2 * Hkv
+    B = ctx_lens.numel()
+    assert block_tables.dim() == 2 and block_tables.shape[0] == B
+    _check(
+        load_library().tgis_kv_absmax(_ptr(k_pool), _ptr(v_pool), _ptr(block_tables), block_tables.shape[1], _ptr(ctx_lens),
+                                      B, Hkv, D, dtype_code(k_pool.dtype), _ptr(out), _stream()), "tgis_kv_absmax")
     return out
 
 
