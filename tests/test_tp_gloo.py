@@ -166,13 +166,12 @@ def _pages_worker(rank, world, port, ret):
     for p in (root, os.path.join(root, "text-generation-inference_amd")):
         if p not in sys.path:
             sys.path.insert(0, p)
-    from tgis_amd.models.flash_causal_lm import FlashCausalLM
     from tgis_amd.utils.dist import initialize_torch_distributed
+    from tgis_amd.utils.rank_group import RankGroup
 
     pg = initialize_torch_distributed(world, rank)
     engine = types.SimpleNamespace(process_group=pg, world_size=world)
-    me = types.SimpleNamespace(device=torch.device("cpu"))
-    ret[rank] = FlashCausalLM._agree_on_min(me, 1000 - 137 * rank, engine)
+    ret[rank] = RankGroup(engine, torch.device("cpu")).min_int(1000 - 137 * rank)
 
 
 def test_tp_ranks_agree_on_the_smallest_page_pool():

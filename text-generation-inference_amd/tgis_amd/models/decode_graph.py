@@ -1,0 +1,174 @@
+"""The captured decode step of FlashCausalLM: static buffers + HIP graph per (batch-size bucket, table width), the choice
+between one graph and a chain of segments under tensor parallelism, and the memory pool the captures share.
+
+The state stays on the model, where bench.py, the tests and tools/ read and set it: `lm._graphs`, `lm.graph_captures`,
+`lm.use_graphs`, `lm.max_graphs`, `lm.graph_mode`, `lm.graph_pool`, `lm.tp_world`, `lm.ranks` (utils/rank_group.py)."""
+import logging
+import time
+
+import torch
+
+from tgis_amd import native
+from tgis_amd.models.custom_modeling.flash_common import KVArgs
+from tgis_amd.utils.graph_segments import SegmentedGraph, no_gc_during_capture
+from tgis_amd.utils.kv_cache import PAGE
+
+logger = logging.getLogger(__name__)
+
+
+def renew_unheld_pool(lm):
+    """The allocator retires a graph pool with the last captured graph that holds it (every graph evicted, or a failed full
+    capture that took the pool's only graph with it): captures that follow start a new one."""
+    if lm.use_graphs and not any(d.graph is not None for d in lm._graphs.values()):
+        lm.graph_pool = torch.cuda.graph_pool_handle()
+
+
+def resolve_graph_mode(lm) -> str:
+    """"full" or "segments"; `auto` is settled once, identically on every rank."""
+    if lm.graph_mode == "auto":
+        try:
+            works = _collective_capture_works(lm)
+        except Exception as exc:  # an unusable probe must not take the server down: segments need no capture of RCCL
+            logger.warning("probing RCCL graph capture failed (%s)", exc)
+            works = False
+        lm.graph_mode = "full" if works else "segments"
+        logger.info("tensor-parallel decode graphs: %s", lm.graph_mode)
+    return lm.graph_mode
+
+
+def _collective_capture_works(lm) -> bool:
+    if not lm.ranks.nccl:
+        return False  # host-mediated collectives synchronise: they can never be inside a capture
+    pg = lm.ranks.process_group
+    world = pg.size()
+    t = torch.ones(1024, device=lm.device, dtype=torch.float32)
+    try:
+        torch.distributed.all_reduce(t, group=pg)  # communicator up before any capture
+        torch.cuda.synchronize(lm.device)
+        t.fill_(1.0)
+        g = torch.cuda.CUDAGraph()
+        with no_gc_during_capture(), torch.cuda.graph(g, capture_error_mode="thread_local"):
+            torch.distributed.all_reduce(t, group=pg)
+        g.replay()
+        g.replay()
+        torch.cuda.synchronize(lm.device)
+        ok = bool((t == float(world * world)).all().item())
+    except Exception as exc:
+        logger.warning("RCCL inside a captured graph is not usable here (%s)", exc)
+        native.clear_error()
+        ok = False
+    return lm.ranks.all_true(ok)
+
+
+class _DecodeGraph:
+    """Static buffers + captured HIP graph of one decode step for a (batch-size bucket, table width) pair."""
+
+    def __init__(self, lm, B: int, width: int):
+        dev = lm.device
+        self.rows = B
+        self.active = 0  # rows [0, active) hold a batch's sequences, the rest are inactive
+        self.input_ids = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.positions = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.block_tables = torch.full((B, width), lm.kv_cache.null_page, dtype=torch.int32, device=dev)
+        self.slots = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.ctx = torch.ones(B, dtype=torch.int32, device=dev)
+        self.cu_q = torch.arange(B + 1, dtype=torch.int32, device=dev)
+        self.max_ctx = width * PAGE
+        self.num_splits = native.attn_num_splits(B, lm.num_kv_heads, lm.num_heads, 1, self.max_ctx)
+        self.lm = lm
+        self.graph = None
+        self.logits = self.ids = self.logprobs = None
+        # greedy ids (int64) and their logprobs (f32) in ONE device buffer: one copy to the (pinned) host mirror per step
+        self.out_buf = torch.zeros(B * 12, dtype=torch.uint8, device=dev)
+        self.ids_buf = self.out_buf[:B * 8].view(torch.int64)
+        self.lps_buf = self.out_buf[B * 8:].view(torch.float32)
+        self.argmax_scratch = native.argmax_scratch(B, dev)
+        self.host_buf = torch.zeros(B * 12, dtype=torch.uint8).pin_memory()
+        self.host_ready = torch.cuda.Event()
+        # whose next-step inputs the static buffers already hold (tgis_decode_advance wrote them): identity of the
+        # batch's tensors, so that a pruned / concatenated / other batch always stages its own
+        self.staged_ids = self.staged_pos = self.staged_bt = None
+
+    def fetch_greedy(self):
+        """ids and logprobs of the step that just ran, as host lists: one device->host copy, one wait."""
+        self.host_buf.copy_(self.out_buf, non_blocking=True)
+        self.host_ready.record()
+        return self._read_host
+
+    def _read_host(self, want_logprobs: bool):
+        self.host_ready.synchronize()
+        B = self.ids_buf.numel()
+        ids = self.host_buf[:B * 8].view(torch.int64).tolist()
+        return ids, (self.host_buf[B * 8:].view(torch.float32).tolist() if want_logprobs else None)
+
+    def _step(self):
+        lm = self.lm
+        native.decode_slots(self.positions, self.block_tables, self.slots, self.ctx)
+        kv = KVArgs(cache=lm.kv_cache, block_tables=self.block_tables, ctx_lens=self.ctx, slots=self.slots,
+                    max_q_len=1, max_ctx=self.max_ctx, num_splits=self.num_splits)
+        logits = lm.model.forward(self.input_ids, self.positions, self.cu_q, self.max_ctx, None, kv)
+        ids, lps = native.argmax_logprob(logits, ids_out=self.ids_buf, logprob_out=self.lps_buf, scratch=self.argmax_scratch)
+        return logits, ids, lps
+
+    def run(self, input_ids, position_ids, block_tables):
+        """One decode step of a batch of n <= rows sequences; returns (logits, ids, logprobs) of its n rows."""
+        n = input_ids.numel()
+        if n < self.active:  # rows a larger batch used before: inactive again
+            self.positions[n:self.active].zero_()
+            self.input_ids[n:self.active].zero_()
+            self.block_tables[n:self.active].fill_(self.lm.kv_cache.null_page)
+        self.active = n
+        if input_ids is not self.staged_ids or position_ids is not self.staged_pos:
+            self.input_ids[:n].copy_(input_ids, non_blocking=True)
+            self.positions[:n].copy_(position_ids, non_blocking=True)
+        if block_tables is not self.staged_bt:
+            self.block_tables[:n].copy_(block_tables, non_blocking=True)
+            self.staged_bt = block_tables
+        self.staged_ids = self.staged_pos = None
+        logits, ids, lps = self._run()
+        return (logits, ids, lps) if n == self.rows else (logits[:n], ids[:n], lps[:n])
+
+    def _run(self):
+        if not self.lm.use_graphs:
+            return self._step()
+        if self.graph is None:
+            t_capture = time.perf_counter()
+            # warm-up: sizes the workspaces, builds rope tables and (tp > 1) initialises the RCCL communicators outside
+            # the capture
+            self._step()
+            torch.cuda.current_stream().synchronize()
+            g = None
+            if resolve_graph_mode(self.lm) == "full":
+                g = torch.cuda.CUDAGraph()
+                # tp > 1: RCCL's proxy and watchdog threads may call the runtime while this thread captures
+                kw = {"capture_error_mode": "thread_local"} if self.lm.tp_world > 1 else {}
+                ok = True
+                try:
+                    with no_gc_during_capture(), torch.cuda.graph(g, pool=self.lm.graph_pool, **kw):
+                        self.logits, self.ids, self.logprobs = self._step()
+                except Exception as exc:
+                    if self.lm.tp_world == 1:
+                        raise
+                    logger.warning("capturing the tensor-parallel step with RCCL inside failed (%s)", exc)
+                    native.clear_error()
+                    ok = False
+                if self.lm.tp_world > 1 and not self.lm.ranks.all_true(ok):
+                    # one rank failing is every rank's failure: all of them leave `full` together, or their collective
+                    # sequences would diverge (a capture issues no collective, so nobody is waiting inside one here)
+                    self.lm.graph_mode = "segments"
+                    g = None
+            if g is None:
+                renew_unheld_pool(self.lm)
+                g = SegmentedGraph(self.lm.device, pool=self.lm.graph_pool)
+                try:
+                    self.logits, self.ids, self.logprobs = g.record(self._step)
+                except Exception as exc:  # keep serving: the eager step needs nothing the capture set up
+                    logger.warning("segmented capture of the decode step failed (%s); running eagerly", exc)
+                    native.clear_error()
+                    self.lm.use_graphs = False
+                    return self._step()
+            self.graph = g
+            # (rows, table width, host ms of warm-up step + capture): what a new (bucket, width) pair costs a serving step
+            self.lm.graph_captures.append((self.rows, self.block_tables.shape[1], (time.perf_counter() - t_capture) * 1e3))
+        self.graph.replay()
+        return self.logits, self.ids, self.logprobs

@@ -27,16 +27,15 @@ import torch
 
 from tgis_amd import native
 from tgis_amd.models.custom_modeling.flash_common import KVArgs
+from tgis_amd.models.decode_graph import _DecodeGraph, renew_unheld_pool
 from tgis_amd.models.model import Model
 from tgis_amd.models.types import Batch, GenerateError
 from tgis_amd.pb import generate_pb2
-from tgis_amd.utils.graph_segments import SegmentedGraph, no_gc_during_capture
-from tgis_amd.utils.kv_cache import (KV_CACHE_DTYPES, KV_SCALES_HEADROOM, PAGE, PagedKVCache, kv_pool_dtype,
-                                     kv_scales_stats, pages_for_budget, parse_kv_cache_dtype, resolve_kv_scales)
+from tgis_amd.utils.kv_cache import (KV_SCALES_HEADROOM, PAGE, PagedKVCache, agree_kv_cache_dtype, agree_kv_scales,
+                                     kv_pool_dtype, kv_scales_stats, pages_for_budget, parse_kv_cache_dtype)
+from tgis_amd.utils.rank_group import RankGroup
 from tgis_amd.utils.token_types import InputTokens, TokenInfo
 from tgis_amd.utils.tokens import HeterogeneousNextTokenChooser, get_input_tokens_info, get_token_info
-
-logger = logging.getLogger(__name__)
 
 USE_GRAPHS = os.getenv("TGIS_DISABLE_GRAPHS", "false").lower() not in ("1", "true")
 
@@ -325,138 +324,16 @@ def graph_bucket(B: int) -> int:
     return (B + 7) // 8 * 8
 
 
-class _DecodeGraph:
-    """Static buffers + captured HIP graph of one decode step for a (batch-size bucket, table width) pair."""
-
-    def __init__(self, lm: "FlashCausalLM", B: int, width: int):
-        dev = lm.device
-        self.rows = B
-        self.active = 0  # rows [0, active) hold a batch's sequences, the rest are inactive
-        self.input_ids = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.positions = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.block_tables = torch.full((B, width), lm.kv_cache.null_page, dtype=torch.int32, device=dev)
-        self.slots = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.ctx = torch.ones(B, dtype=torch.int32, device=dev)
-        self.cu_q = torch.arange(B + 1, dtype=torch.int32, device=dev)
-        self.max_ctx = width * PAGE
-        self.num_splits = native.attn_num_splits(B, lm.num_kv_heads, lm.num_heads, 1, self.max_ctx)
-        self.lm = lm
-        self.graph = None
-        self.logits = self.ids = self.logprobs = None
-        # greedy ids (int64) and their logprobs (f32) in ONE device buffer: one copy to the (pinned) host mirror per step
-        self.out_buf = torch.zeros(B * 12, dtype=torch.uint8, device=dev)
-        self.ids_buf = self.out_buf[:B * 8].view(torch.int64)
-        self.lps_buf = self.out_buf[B * 8:].view(torch.float32)
-        self.argmax_scratch = native.argmax_scratch(B, dev)
-        self.host_buf = torch.zeros(B * 12, dtype=torch.uint8).pin_memory()
-        self.host_ready = torch.cuda.Event()
-        # whose next-step inputs the static buffers already hold (tgis_decode_advance wrote them): identity of the
-        # batch's tensors, so that a pruned / concatenated / other batch always stages its own
-        self.staged_ids = self.staged_pos = self.staged_bt = None
-
-    def fetch_greedy(self):
-        """ids and logprobs of the step that just ran, as host lists: one device->host copy, one wait."""
-        self.host_buf.copy_(self.out_buf, non_blocking=True)
-        self.host_ready.record()
-        return self._read_host
-
-    def _read_host(self, want_logprobs: bool):
-        self.host_ready.synchronize()
-        B = self.ids_buf.numel()
-        ids = self.host_buf[:B * 8].view(torch.int64).tolist()
-        return ids, (self.host_buf[B * 8:].view(torch.float32).tolist() if want_logprobs else None)
-
-    def _step(self):
-        lm = self.lm
-        native.decode_slots(self.positions, self.block_tables, self.slots, self.ctx)
-        kv = KVArgs(cache=lm.kv_cache, block_tables=self.block_tables, ctx_lens=self.ctx, slots=self.slots,
-                    max_q_len=1, max_ctx=self.max_ctx, num_splits=self.num_splits)
-        logits = lm.model.forward(self.input_ids, self.positions, self.cu_q, self.max_ctx, None, kv)
-        ids, lps = native.argmax_logprob(logits, ids_out=self.ids_buf, logprob_out=self.lps_buf, scratch=self.argmax_scratch)
-        return logits, ids, lps
-
-    def run(self, input_ids, position_ids, block_tables):
-        """One decode step of a batch of n <= rows sequences; returns (logits, ids, logprobs) of its n rows."""
-        n = input_ids.numel()
-        if n < self.active:  # rows a larger batch used before: inactive again
-            self.positions[n:self.active].zero_()
-            self.input_ids[n:self.active].zero_()
-            self.block_tables[n:self.active].fill_(self.lm.kv_cache.null_page)
-        self.active = n
-        if input_ids is not self.staged_ids or position_ids is not self.staged_pos:
-            self.input_ids[:n].copy_(input_ids, non_blocking=True)
-            self.positions[:n].copy_(position_ids, non_blocking=True)
-        if block_tables is not self.staged_bt:
-            self.block_tables[:n].copy_(block_tables, non_blocking=True)
-            self.staged_bt = block_tables
-        self.staged_ids = self.staged_pos = None
-        logits, ids, lps = self._run()
-        return (logits, ids, lps) if n == self.rows else (logits[:n], ids[:n], lps[:n])
-
-    def _run(self):
-        if not self.lm.use_graphs:
-            return self._step()
-        if self.graph is None:
-            t_capture = time.perf_counter()
-            # warm-up: sizes the workspaces, builds rope tables and (tp > 1) initialises the RCCL communicators outside
-            # the capture
-            self._step()
-            torch.cuda.current_stream().synchronize()
-            g = None
-            if self.lm.resolve_graph_mode() == "full":
-                g = torch.cuda.CUDAGraph()
-                # tp > 1: RCCL's proxy and watchdog threads may call the runtime while this thread captures
-                kw = {"capture_error_mode": "thread_local"} if self.lm.tp_world > 1 else {}
-                ok = True
-                try:
-                    with no_gc_during_capture(), torch.cuda.graph(g, pool=self.lm.graph_pool, **kw):
-                        self.logits, self.ids, self.logprobs = self._step()
-                except Exception as exc:
-                    if self.lm.tp_world == 1:
-                        raise
-                    logger.warning("capturing the tensor-parallel step with RCCL inside failed (%s)", exc)
-                    native.clear_error()
-                    ok = False
-                if self.lm.tp_world > 1 and not self.lm.all_ranks_agree(ok):
-                    # one rank failing is every rank's failure: all of them leave `full` together, or their collective
-                    # sequences would diverge (a capture issues no collective, so nobody is waiting inside one here)
-                    self.lm.graph_mode = "segments"
-                    g = None
-            if g is None:
-                if not any(d.graph is not None for d in self.lm._graphs.values()):
-                    # no captured graph holds the pool (e.g. the full capture above failed and took the pool's only
-                    # graph with it): the allocator has retired it, start a new one
-                    self.lm.graph_pool = torch.cuda.graph_pool_handle()
-                g = SegmentedGraph(self.lm.device, pool=self.lm.graph_pool)
-                try:
-                    self.logits, self.ids, self.logprobs = g.record(self._step)
-                except Exception as exc:  # keep serving: the eager step needs nothing the capture set up
-                    logger.warning("segmented capture of the decode step failed (%s); running eagerly", exc)
-                    native.clear_error()
-                    self.lm.use_graphs = False
-                    return self._step()
-            self.graph = g
-            # (rows, table width, host ms of warm-up step + capture): what a new (bucket, width) pair costs a serving step
-            self.lm.graph_captures.append((self.rows, self.block_tables.shape[1], (time.perf_counter() - t_capture) * 1e3))
-        self.graph.replay()
-        return self.logits, self.ids, self.logprobs
-
-
 class FlashCausalLM(Model):
     def __init__(self, model_name: str, revision: Optional[str], deployment_framework: str, dtype: torch.dtype,
                  quantize: Optional[str], model_config: Union[Any] = None, auto_model_class=None,
                  max_sequence_length: Optional[int] = None, engine=None, kv_cache_pages: Optional[int] = None,
                  kv_cache_dtype: Optional[str] = None, kv_scales: Union[None, str, dict] = None):
         # KV cache element: "auto" (the model dtype) or "fp8_e4m3" (one byte, utils/kv_cache.py); None reads
-        # TGIS_KV_CACHE_DTYPE.  Checked before anything is loaded — except on a rank of a tensor-parallel group, which first
-        # tells its peers (_check_same_kv_dtype) so that they fail with it instead of waiting in that collective.
-        self._kv_dtype_error = None
-        try:
-            self.kv_cache_dtype = parse_kv_cache_dtype(kv_cache_dtype)
-        except ValueError as e:
-            if (getattr(engine, "world_size", 1) or 1) == 1:
-                raise
-            self.kv_cache_dtype, self._kv_dtype_error = None, e
+        # TGIS_KV_CACHE_DTYPE.  Checked before anything is loaded — except on a rank of a tensor-parallel group, which loads
+        # its shard and then tells its peers (agree_kv_cache_dtype below): they sit in a collective only it can release.
+        if (getattr(engine, "world_size", 1) or 1) == 1:
+            parse_kv_cache_dtype(kv_cache_dtype)
         # kv_scales: the calibrated per-layer scales of a one-byte cache, the contents of a kv_cache_scales.json or its path
         # (utils/kv_cache.py, resolve_kv_scales); None looks at TGIS_KV_SCALES, then next to the weights, else they stay 1.0
         if not torch.cuda.is_available():
@@ -489,20 +366,23 @@ class FlashCausalLM(Model):
         self.num_layers = len(inner.layers)
         if hasattr(self.model, "post_init"):
             self.model.post_init()
-        # Tensor parallel: every rank reads and writes its shard of the same layers' pages with the same kernels — a rank
-        # whose environment asked for another cache dtype is a configuration error, raised here rather than served.
-        self._check_same_kv_dtype(engine)
+        # what tensor-parallel ranks must agree on, in this order on every rank: cache dtype, pages, scales, graph mode, seed
+        self.ranks = RankGroup(engine, self.device)
+        self.kv_cache_dtype = agree_kv_cache_dtype(self.ranks, kv_cache_dtype)
         if kv_cache_pages is None:
             kv_cache_pages = self._default_kv_pages()
         # Tensor parallel: every rank must hold the SAME number of pages.  Each rank sizes its pool from its own free
         # memory, and `grow_pages` raises OutOfPages before a decode step: a rank with fewer pages would leave the step
         # while the others enter its all-reduces (a hang instead of RESOURCE_EXHAUSTED), and the memory model a rank
         # reports to the router would differ from its peers'.  The smallest pool decides.
-        kv_cache_pages = self._agree_on_min(kv_cache_pages, engine)
+        kv_cache_pages = self.ranks.min_int(kv_cache_pages)
         self.kv_cache = PagedKVCache(self.num_layers, self.num_kv_heads, self.head_size, kv_cache_pages, dtype,
                                      self.device, kv_dtype=self.kv_cache_dtype)
         # before any page is written and any graph captured: both hold the scales
-        self._apply_kv_scales(kv_scales, engine)
+        scales = agree_kv_scales(self.ranks, kv_scales, self.kv_cache_dtype, self.num_layers,
+                                 getattr(engine, "model_path", None))
+        if scales is not None:
+            self.kv_cache.set_scales(*scales)
         # tp > 1, TGIS_TP_GRAPHS = auto (default) | full | segments | false:
         #   full      one graph per step with the RCCL all-reduces / all-gather inside it (RCCL is capture-aware);
         #   segments  a chain of graphs with the collectives launched between them (utils/graph_segments.py);
@@ -511,9 +391,7 @@ class FlashCausalLM(Model):
         #             RCCL group, else segments.
         # One rank's step at TP=8 shapes, collectives on a world-size-1 RCCL group (tools/tp_segments_rccl1.py):
         # 2.0 ms full, 3.2 ms segments, 4.4 ms eager.
-        tp = engine.world_size if hasattr(engine, "world_size") else 1
-        self.tp_world = tp
-        self.process_group = getattr(engine, "process_group", None)
+        tp = self.tp_world = self.ranks.world
         tp_mode = os.getenv("TGIS_TP_GRAPHS", "auto").lower()
         if tp == 1 or tp_mode in ("full", "1", "true"):
             self.graph_mode = "full"
@@ -522,14 +400,12 @@ class FlashCausalLM(Model):
         else:
             self.graph_mode = None
         self.use_graphs = USE_GRAPHS and self.graph_mode is not None
-        if tp > 1 and isinstance(self.process_group, torch.distributed.ProcessGroup):
+        if self.ranks.real:
             # requests without a seed must still draw the same tokens on every rank
             from tgis_amd.utils import tokens
 
             base = tokens.seed_base()
-            t = torch.tensor([base >> 32, base & 0xFFFFFFFF], dtype=torch.int64, device=self.device)
-            torch.distributed.broadcast(t, src=0, group=self.process_group)
-            hi, lo = t.tolist()
+            hi, lo = self.ranks.broadcast_int64_pair(base >> 32, base & 0xFFFFFFFF)
             tokens.set_seed_base((hi << 32) | lo)
         # captured decode steps, least recently used first; they share one memory pool (a step's intermediates are dead
         # once it has run, and its outputs are consumed before the next replay), and the number kept is bounded
@@ -537,115 +413,6 @@ class FlashCausalLM(Model):
         self.graph_captures = deque(maxlen=4096)  # (rows, pages per row, capture ms) of the latest captures
         self.max_graphs = int(os.getenv("TGIS_MAX_DECODE_GRAPHS", "48"))
         self.graph_pool = torch.cuda.graph_pool_handle() if self.use_graphs else None
-
-    def resolve_graph_mode(self) -> str:
-        """"full" or "segments"; `auto` is settled once, identically on every rank."""
-        if self.graph_mode == "auto":
-            try:
-                works = self._collective_capture_works()
-            except Exception as exc:  # an unusable probe must not take the server down: segments need no capture of RCCL
-                logger.warning("probing RCCL graph capture failed (%s)", exc)
-                works = False
-            self.graph_mode = "full" if works else "segments"
-            logger.info("tensor-parallel decode graphs: %s", self.graph_mode)
-        return self.graph_mode
-
-    def all_ranks_agree(self, ok: bool) -> bool:
-        """True iff `ok` holds on every rank of the tensor-parallel group (one small all-reduce, outside any capture)."""
-        pg = self.process_group
-        if self.tp_world == 1 or not isinstance(pg, torch.distributed.ProcessGroup):
-            return ok
-        dev = self.device if torch.distributed.get_backend(pg) == "nccl" else "cpu"
-        flag = torch.tensor([1 if ok else 0], device=dev, dtype=torch.int32)
-        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=pg)
-        return bool(flag.item())
-
-    def _collective_capture_works(self) -> bool:
-        pg = self.process_group
-        if not isinstance(pg, torch.distributed.ProcessGroup) or torch.distributed.get_backend(pg) != "nccl":
-            return False  # host-mediated collectives synchronise: they can never be inside a capture
-        world = pg.size()
-        t = torch.ones(1024, device=self.device, dtype=torch.float32)
-        ok = True
-        try:
-            torch.distributed.all_reduce(t, group=pg)  # communicator up before any capture
-            torch.cuda.synchronize(self.device)
-            t.fill_(1.0)
-            g = torch.cuda.CUDAGraph()
-            with no_gc_during_capture(), torch.cuda.graph(g, capture_error_mode="thread_local"):
-                torch.distributed.all_reduce(t, group=pg)
-            g.replay()
-            g.replay()
-            torch.cuda.synchronize(self.device)
-            ok = bool((t == float(world * world)).all().item())
-        except Exception as exc:
-            logger.warning("RCCL inside a captured graph is not usable here (%s)", exc)
-            native.clear_error()
-            ok = False
-        flag = torch.tensor([1 if ok else 0], device=self.device, dtype=torch.int32)
-        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=pg)
-        return bool(flag.item())
-
-    def _agree_on_min(self, value: int, engine) -> int:
-        """min of `value` over the tensor-parallel group (all-reduce MIN); the value itself on one rank."""
-        pg = getattr(engine, "process_group", None)
-        world = engine.world_size if hasattr(engine, "world_size") else 1
-        if world == 1 or not isinstance(pg, torch.distributed.ProcessGroup):
-            return int(value)
-        dev = self.device if torch.distributed.get_backend(pg) == "nccl" else torch.device("cpu")
-        t = torch.tensor([int(value)], dtype=torch.int64, device=dev)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MIN, group=pg)
-        return int(t.item())
-
-    def _check_same_kv_dtype(self, engine):
-        world = engine.world_size if hasattr(engine, "world_size") else 1
-        if world == 1:
-            return
-        # (-1: this rank's value was not a KV cache dtype at all)
-        code = -1 if self._kv_dtype_error is not None else KV_CACHE_DTYPES.index(self.kv_cache_dtype)
-        lo, hi = self._agree_on_min(code, engine), -self._agree_on_min(-code, engine)
-        if self._kv_dtype_error is not None:
-            raise self._kv_dtype_error
-        if lo < 0:
-            raise ValueError("another tensor-parallel rank was given an unsupported KV cache dtype (TGIS_KV_CACHE_DTYPE)")
-        if lo != hi:
-            raise ValueError(f"tensor-parallel ranks disagree on the KV cache dtype (this rank: {self.kv_cache_dtype}; "
-                             f"ranks use {KV_CACHE_DTYPES[lo]} and {KV_CACHE_DTYPES[hi]}): set TGIS_KV_CACHE_DTYPE alike "
-                             f"on every rank")
-
-    def _apply_kv_scales(self, kv_scales, engine):
-        """Resolves the cache's scales (utils/kv_cache.py, resolve_kv_scales) and applies them.  Tensor parallel: rank 0
-        resolves, every rank applies rank 0's values — and a rank that fails (an unreadable file on rank 0, an explicit
-        argument with a 16-bit cache anywhere) tells its peers first, so that all of them raise instead of one waiting."""
-        world = engine.world_size if hasattr(engine, "world_size") else 1
-        pg = getattr(engine, "process_group", None)
-        tp = world > 1 and isinstance(pg, torch.distributed.ProcessGroup)
-        found, error = None, None
-        try:
-            if not tp or getattr(engine, "rank", 0) == 0:
-                found = resolve_kv_scales(kv_scales, self.kv_cache_dtype, self.num_layers, getattr(engine, "model_path", None))
-            elif kv_scales is not None and not self.kv_cache.is_fp8:
-                resolve_kv_scales(kv_scales, self.kv_cache_dtype, self.num_layers)  # raises: explicit scales, 16-bit cache
-        except (ValueError, OSError) as e:
-            if not tp:
-                raise
-            error = e
-        if tp:
-            dev = self.device if torch.distributed.get_backend(pg) == "nccl" else torch.device("cpu")
-            t = torch.zeros(1 + 2 * self.num_layers, dtype=torch.float64, device=dev)  # [found, k scales, v scales]
-            if found is not None:
-                t[0] = 1.0
-                t[1:] = torch.tensor(found[0] + found[1], dtype=torch.float64)
-            torch.distributed.broadcast(t, src=0, group=pg)
-            all_ok = self._agree_on_min(0 if error is None else -1, engine) == 0
-            if error is not None:
-                raise error
-            if not all_ok:
-                raise ValueError("another tensor-parallel rank could not resolve the KV cache scales")
-            vals = t.tolist()
-            found = (vals[1:1 + self.num_layers], vals[1 + self.num_layers:]) if vals[0] == 1.0 else None
-        if found is not None:
-            self.kv_cache.set_scales(*found)
 
     def calibrate_kv_scales(self, batches, decode_steps: int = 0, headroom: float = KV_SCALES_HEADROOM) -> dict:
         """The contents of a kv_cache_scales.json (utils/kv_cache.py) measured on this model: every generate_pb2.Batch of
@@ -677,13 +444,8 @@ class FlashCausalLM(Model):
                     tokens += sum(cached)
                 finally:
                     batch.release()
-            absmax = stats.amax(dim=2)  # [L, 2] over this rank's heads
-            pg = self.process_group
-            if self.tp_world > 1 and isinstance(pg, torch.distributed.ProcessGroup):  # outside any capture
-                if torch.distributed.get_backend(pg) != "nccl":
-                    absmax = absmax.cpu()
-                torch.distributed.all_reduce(absmax, op=torch.distributed.ReduceOp.MAX, group=pg)
-            absmax = absmax.cpu().tolist()
+            # [L, 2] over this rank's heads, then over the ranks (outside any capture)
+            absmax = self.ranks.max_reduce(stats.amax(dim=2)).cpu().tolist()
         return kv_scales_stats([a[0] for a in absmax], [a[1] for a in absmax], tokens, str(self.dtype).replace("torch.", ""),
                                headroom)
 
@@ -743,9 +505,7 @@ class FlashCausalLM(Model):
         if g is None:
             while len(self._graphs) >= self.max_graphs:
                 self._graphs.popitem(last=False)
-            if not self._graphs and self.graph_pool is not None:
-                # the allocator retires a pool with its last graph: captures that follow start a new one
-                self.graph_pool = torch.cuda.graph_pool_handle()
+            renew_unheld_pool(self)
             g = self._graphs[key] = _DecodeGraph(self, *key)
         else:
             self._graphs.move_to_end(key)

@@ -57,6 +57,25 @@ def parse_kv_cache_dtype(value: Optional[str] = None) -> str:
     return name
 
 
+def agree_kv_cache_dtype(group, value: Optional[str] = None) -> str:
+    """`parse_kv_cache_dtype(value)`, the same on every rank of `group` (utils/rank_group.py).  Every rank reads and writes its
+    shard of the same layers' pages with the same kernels: a rank whose environment asked for another cache dtype is a
+    configuration error, raised on every rank rather than served — and a rank whose value does not parse tells its peers
+    first, so that they fail with it instead of waiting in a collective."""
+    try:
+        name, error = parse_kv_cache_dtype(value), None
+    except ValueError as e:
+        name, error = None, e
+    group.fail_together(error, "another tensor-parallel rank was given an unsupported KV cache dtype (TGIS_KV_CACHE_DTYPE)")
+    code = KV_CACHE_DTYPES.index(name)
+    lo, hi = group.min_int(code), group.max_int(code)
+    if lo != hi:
+        raise ValueError(f"tensor-parallel ranks disagree on the KV cache dtype (this rank: {name}; "
+                         f"ranks use {KV_CACHE_DTYPES[lo]} and {KV_CACHE_DTYPES[hi]}): set TGIS_KV_CACHE_DTYPE alike "
+                         f"on every rank")
+    return name
+
+
 def kv_pool_dtype(kv_dtype: str, model_dtype: torch.dtype) -> torch.dtype:
     """Element type of the pool tensor: the model dtype, or uint8 holding e4m3 codes."""
     return torch.uint8 if parse_kv_cache_dtype(kv_dtype) == "fp8_e4m3" else model_dtype
@@ -247,3 +266,21 @@ def resolve_kv_scales(kv_scales: Union[None, str, Dict], kv_dtype: str, num_laye
     if not path:
         return None
     return check_kv_scales(load_kv_scales(path, num_layers), num_layers)
+
+
+def agree_kv_scales(group, kv_scales: Union[None, str, Dict], kv_dtype: str, num_layers: int,
+                    model_dir: Optional[str] = None) -> Optional[Tuple[List[float], List[float]]]:
+    """`resolve_kv_scales`, the same on every rank of `group` (utils/rank_group.py): rank 0 resolves and every rank gets rank
+    0's values.  A rank that fails (an unreadable file on rank 0, an explicit argument with a 16-bit cache anywhere) tells
+    its peers first, so that all of them raise instead of one waiting."""
+    found, error = None, None
+    try:
+        if group.rank == 0 or not group.real:
+            found = resolve_kv_scales(kv_scales, kv_dtype, num_layers, model_dir)
+        elif kv_scales is not None and parse_kv_cache_dtype(kv_dtype) != "fp8_e4m3":
+            resolve_kv_scales(kv_scales, kv_dtype, num_layers)  # raises: explicit scales, 16-bit cache
+    except (ValueError, OSError) as e:
+        error = e
+    flat = group.broadcast_from_rank0(None if found is None else found[0] + found[1], 2 * num_layers)
+    group.fail_together(error, "another tensor-parallel rank could not resolve the KV cache scales")
+    return None if flat is None else (flat[:num_layers], flat[num_layers:])

@@ -11,6 +11,7 @@ import argparse
 import os
 import sys
 import time
+import types
 
 os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
 os.environ.setdefault("MASTER_PORT", "29531")
@@ -37,6 +38,7 @@ def main():
     from tgis_amd.utils import layers
     from tgis_amd.utils.graph_segments import collective
     from tgis_amd.utils.kv_cache import PagedKVCache
+    from tgis_amd.utils.rank_group import RankGroup
 
     torch.cuda.set_device(0)
     torch.distributed.init_process_group("nccl", world_size=1, rank=0)
@@ -101,7 +103,8 @@ def main():
         run(f"tp{args.tp} rank: one graph, RCCL inside", "full", plain)
         run(f"tp{args.tp} rank: segments, RCCL seams", "segments", plain)
         run(f"tp{args.tp} rank: eager", None, plain)
-        lm.process_group = pg  # the probe of the default mode against a real RCCL group
+        # the probe of the default mode against a real RCCL group
+        lm.ranks = RankGroup(types.SimpleNamespace(world_size=args.tp, rank=0, process_group=pg), lm.device)
         run(f"tp{args.tp} rank: auto (probe -> {{mode}})", "auto", plain)
     else:
         run("full graph, no collectives", "full", plain)
