@@ -294,6 +294,24 @@ int tgis_rope_kv_write_prefill_kv8(void* qkv, int64_t ld_qkv, const void* cos, c
                                    void* v_pool, int64_t B, int64_t T, int64_t max_len, int H, int Hkv, int D, int rot_dim,
                                    int dtype, void* stream, int kv_dtype, float k_scale, float v_scale);
 
+/* tgis_rope_kv_write_prefill / _kv8 behind a reused prefix (KV prefix reuse: the first past_lens[b] tokens of sequence b
+ * are already in the cache, on pages it shares with the request that wrote them; the reference recomputes them,
+ * flash_llama_modeling.py:262-268,282 over the whole prompt): token i of sequence b in `qkv` is cache position
+ * past_lens[b] + i and goes to table entry past_lens[b] / 32 + i / 32.
+ *   past_lens [B] int32 (device): every entry a multiple of 32 (precondition; the caller builds it from host ints),
+ *   and past_lens[b] / 32 + ceil(len_b / 32) <= max_pages.  cu_seqlens, T and max_len describe the SUFFIX tokens only.
+ * Everything else is the fresh form; no page in front of past_lens[b] / 32 is stored to.  All-zero past_lens is
+ * tgis_rope_kv_write_prefill bit for bit.  A null past_lens is TGIS_EINVAL. */
+int tgis_rope_kv_write_prefill_at(void* qkv, int64_t ld_qkv, const void* cos, const void* sin, const int32_t* positions,
+                                  const int32_t* cu_seqlens, const int32_t* block_tables, int64_t max_pages, void* k_pool,
+                                  void* v_pool, int64_t B, int64_t T, int64_t max_len, int H, int Hkv, int D, int rot_dim,
+                                  int dtype, void* stream, const int32_t* past_lens);
+int tgis_rope_kv_write_prefill_at_kv8(void* qkv, int64_t ld_qkv, const void* cos, const void* sin, const int32_t* positions,
+                                      const int32_t* cu_seqlens, const int32_t* block_tables, int64_t max_pages,
+                                      void* k_pool, void* v_pool, int64_t B, int64_t T, int64_t max_len, int H, int Hkv,
+                                      int D, int rot_dim, int dtype, void* stream, int kv_dtype, float k_scale,
+                                      float v_scale, const int32_t* past_lens);
+
 /* ---- paged attention, prefill and decode (replaces flash_attn_2_cuda.varlen_fwd,
  *      utils/flash_attn.py:43-78) ---------------------------------------------------------------- */
 /* Number of key-range splits the launcher will use for this shape (so callers can size workspace). */

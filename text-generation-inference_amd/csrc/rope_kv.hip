@@ -131,14 +131,18 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(T* qkv, int64_t ld, const 
 // stored 16 tokens x 16 bytes at a time (contiguous 256-byte runs of the K layout); its v rows are transposed through
 // LDS so that every store is a full 16-byte run of the [column group][D][8] layout (consecutive threads: consecutive runs).  The per-token kernel above issues 16-byte
 // (k) and 2-byte (v) stores scattered over the page: fine for the 32 tokens of a decode step, ~4x slower than this on a
-// 32k-token prefill.  Precondition: token i of sequence b sits at cache position i (a fresh prefill; its rotary
-// position comes from `positions` like everywhere else).  Slots of the last page past the sequence end get zeros.
+// 32k-token prefill.  Precondition: token i of sequence b sits at cache position past_lens[b] + i, past_lens[b] a multiple
+// of 32 (null: 0, a fresh prefill; behind a reused prefix: the tokens its shared pages hold) — so the block's 32 tokens
+// are one whole page, table entry past_lens[b] / 32 + p, and no page in front of it is touched.  The rotary position
+// comes from `positions` like everywhere else.  Slots of the last page past the sequence end get zeros.
 // KV as in rope_kv_kernel.
 template <typename T, typename KV, bool GEN>
 __global__ __launch_bounds__(256) void rope_kv_prefill_kernel(const T* __restrict__ qkv, int64_t ld,
                                                               const T* __restrict__ cosb, const T* __restrict__ sinb,
                                                               const int32_t* __restrict__ positions,
-                                                              const int32_t* __restrict__ cu, const int32_t* __restrict__ bt,
+                                                              const int32_t* __restrict__ cu,
+                                                              const int32_t* __restrict__ past_lens,
+                                                              const int32_t* __restrict__ bt,
                                                               int64_t max_pages, KV* __restrict__ kpool,
                                                               KV* __restrict__ vpool, int H, int Hkv, int D, int rot,
                                                               int pages_per_seq, float k_scale, float v_scale) {
@@ -150,7 +154,9 @@ __global__ __launch_bounds__(256) void rope_kv_prefill_kernel(const T* __restric
     const int i0 = p * 32;
     if (i0 >= len) return;
     const int ntok = min(32, len - i0);
-    const int page = bt[(int64_t)b * max_pages + p];
+    const int tp = (past_lens ? past_lens[b] >> 5 : 0) + p;  // table entry of this page
+    if (tp >= max_pages) return;  // (a past_lens the table has no room for: nothing is read or written)
+    const int page = bt[(int64_t)b * max_pages + tp];
     const int tid = threadIdx.x;
     const int c8 = D >> 3, rh8 = rot >> 4;
     KV* kb = kpool + ((int64_t)page * Hkv + hk) * 32 * D;
@@ -312,7 +318,8 @@ extern "C" int tgis_rope_kv_write_partial_kv8(const float* slabs, int num_slabs,
 }
 
 static int rope_prefill_launch(void* qkv, int64_t ld_qkv, const void* cos, const void* sin, const int32_t* positions,
-                               const int32_t* cu_seqlens, const int32_t* block_tables, int64_t max_pages, void* k_pool,
+                               const int32_t* cu_seqlens, const int32_t* past_lens, const int32_t* block_tables,
+                               int64_t max_pages, void* k_pool,
                                void* v_pool, int64_t B, int64_t T, int64_t max_len, int H, int Hkv, int D, int rot_dim,
                                int dtype, void* stream, int kv_dtype, float k_scale, float v_scale) {
     TGIS_CHECK_ARG(qkv && cu_seqlens && block_tables && k_pool && v_pool, "tgis_rope_kv_write_prefill: null tensor");
@@ -324,14 +331,15 @@ static int rope_prefill_launch(void* qkv, int64_t ld_qkv, const void* cos, const
     TGIS_CHECK_ARG(dtype == TGIS_F16 || dtype == TGIS_BF16, "tgis_rope_kv_write_prefill: bad dtype");
     TGIS_CHECK_KV_ARGS("tgis_rope_kv_write_prefill_kv8", kv_dtype, k_scale, v_scale);
     if (B == 0 || T == 0) return TGIS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const RopePrefillPlan plan = choose_rope_prefill(max_len, rot_dim, cos != nullptr);
+    const int pps = plan.pps;
+    // (before the q launch: a refused call has launched nothing)
+    TGIS_CHECK_ARG(pps <= max_pages && B * pps <= 2147483647LL && Hkv <= 65535, "tgis_rope_kv_write_prefill: grid too large");
     // q heads: rotated in place by the per-token kernel (no cache traffic: Hkv = 0, no pools)
     int rc = rope_launch(qkv, ld_qkv, cos, sin, positions, nullptr, nullptr, nullptr, T, H, 0, D, rot_dim, dtype, stream,
                          nullptr, 0, 0, nullptr);
     if (rc != TGIS_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const RopePrefillPlan plan = choose_rope_prefill(max_len, rot_dim, cos != nullptr);
-    const int pps = plan.pps;
-    TGIS_CHECK_ARG(pps <= max_pages && B * pps <= 2147483647LL && Hkv <= 65535, "tgis_rope_kv_write_prefill: grid too large");
     TgisTimedScope timed(TGIS_OP_ROPE_KV, st);
     const dim3 grid((unsigned)(B * pps), (unsigned)Hkv);
     const size_t lds = (size_t)32 * (D + 8) * 2;
@@ -342,8 +350,8 @@ static int rope_prefill_launch(void* qkv, int64_t ld_qkv, const void* cos, const
             using KV = type_of<decltype(kv)>;
             return by_bool(gen, [&](auto g) {
                 hipLaunchKernelGGL((rope_kv_prefill_kernel<T, KV, decltype(g)::value>), grid, dim3(256), lds, st,
-                                   (const T*)qkv, ld_qkv, (const T*)cos, (const T*)sin, positions, cu_seqlens, block_tables,
-                                   max_pages, (KV*)k_pool, (KV*)v_pool, H, Hkv, D, rot_dim, pps, k_scale, v_scale);
+                                   (const T*)qkv, ld_qkv, (const T*)cos, (const T*)sin, positions, cu_seqlens, past_lens,
+                                   block_tables, max_pages, (KV*)k_pool, (KV*)v_pool, H, Hkv, D, rot_dim, pps, k_scale, v_scale);
                 TGIS_CHECK_LAUNCH();
                 return TGIS_OK;
             });
@@ -356,8 +364,8 @@ extern "C" int tgis_rope_kv_write_prefill(void* qkv, int64_t ld_qkv, const void*
                                           const int32_t* block_tables, int64_t max_pages, void* k_pool, void* v_pool,
                                           int64_t B, int64_t T, int64_t max_len, int H, int Hkv, int D, int rot_dim,
                                           int dtype, void* stream) {
-    return rope_prefill_launch(qkv, ld_qkv, cos, sin, positions, cu_seqlens, block_tables, max_pages, k_pool, v_pool, B, T,
-                               max_len, H, Hkv, D, rot_dim, dtype, stream, TGIS_KV_MODEL, 1.f, 1.f);
+    return rope_prefill_launch(qkv, ld_qkv, cos, sin, positions, cu_seqlens, nullptr, block_tables, max_pages, k_pool,
+                               v_pool, B, T, max_len, H, Hkv, D, rot_dim, dtype, stream, TGIS_KV_MODEL, 1.f, 1.f);
 }
 
 extern "C" int tgis_rope_kv_write_prefill_kv8(void* qkv, int64_t ld_qkv, const void* cos, const void* sin,
@@ -365,6 +373,29 @@ extern "C" int tgis_rope_kv_write_prefill_kv8(void* qkv, int64_t ld_qkv, const v
                                               const int32_t* block_tables, int64_t max_pages, void* k_pool, void* v_pool,
                                               int64_t B, int64_t T, int64_t max_len, int H, int Hkv, int D, int rot_dim,
                                               int dtype, void* stream, int kv_dtype, float k_scale, float v_scale) {
-    return rope_prefill_launch(qkv, ld_qkv, cos, sin, positions, cu_seqlens, block_tables, max_pages, k_pool, v_pool, B, T,
-                               max_len, H, Hkv, D, rot_dim, dtype, stream, kv_dtype, k_scale, v_scale);
+    return rope_prefill_launch(qkv, ld_qkv, cos, sin, positions, cu_seqlens, nullptr, block_tables, max_pages, k_pool,
+                               v_pool, B, T, max_len, H, Hkv, D, rot_dim, dtype, stream, kv_dtype, k_scale, v_scale);
+}
+
+// The page-wise writer behind a reused prefix: token i of sequence b is cache position past_lens[b] + i (multiples of 32,
+// device), max_len bounds the suffix lengths cu_seqlens describes.  Pages in front of past_lens[b] / 32 are never stored to.
+extern "C" int tgis_rope_kv_write_prefill_at(void* qkv, int64_t ld_qkv, const void* cos, const void* sin,
+                                             const int32_t* positions, const int32_t* cu_seqlens,
+                                             const int32_t* block_tables, int64_t max_pages, void* k_pool, void* v_pool,
+                                             int64_t B, int64_t T, int64_t max_len, int H, int Hkv, int D, int rot_dim,
+                                             int dtype, void* stream, const int32_t* past_lens) {
+    TGIS_CHECK_ARG(past_lens, "tgis_rope_kv_write_prefill_at: null past_lens");
+    return rope_prefill_launch(qkv, ld_qkv, cos, sin, positions, cu_seqlens, past_lens, block_tables, max_pages, k_pool,
+                               v_pool, B, T, max_len, H, Hkv, D, rot_dim, dtype, stream, TGIS_KV_MODEL, 1.f, 1.f);
+}
+
+extern "C" int tgis_rope_kv_write_prefill_at_kv8(void* qkv, int64_t ld_qkv, const void* cos, const void* sin,
+                                                 const int32_t* positions, const int32_t* cu_seqlens,
+                                                 const int32_t* block_tables, int64_t max_pages, void* k_pool,
+                                                 void* v_pool, int64_t B, int64_t T, int64_t max_len, int H, int Hkv, int D,
+                                                 int rot_dim, int dtype, void* stream, int kv_dtype, float k_scale,
+                                                 float v_scale, const int32_t* past_lens) {
+    TGIS_CHECK_ARG(past_lens, "tgis_rope_kv_write_prefill_at_kv8: null past_lens");
+    return rope_prefill_launch(qkv, ld_qkv, cos, sin, positions, cu_seqlens, past_lens, block_tables, max_pages, k_pool,
+                               v_pool, B, T, max_len, H, Hkv, D, rot_dim, dtype, stream, kv_dtype, k_scale, v_scale);
 }

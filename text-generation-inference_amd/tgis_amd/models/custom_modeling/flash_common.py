@@ -24,6 +24,8 @@ class KVArgs:
     max_ctx: int                       # upper bound of ctx_lens (launch shaping only)
     num_splits: int = 1                # attention key splits (decode)
     fresh_prefill: bool = False        # every sequence starts at cache position 0: page-wise cache writes
+    past_lens: Optional[torch.Tensor] = None  # [B] int32: tokens already cached on reused pages (multiples of 32) in
+    #                                    front of this prefill's: page-wise cache writes starting behind them
 
 
 def layer_pools(kv: KVArgs, layer_id: int):
@@ -36,12 +38,16 @@ def layer_pools(kv: KVArgs, layer_id: int):
 
 def write_kv(qkv, kv: KVArgs, layer_id: int, H: int, Hkv: int, D: int, rot_dim: int, cos, sin, position_ids, cu_seqlens_q):
     """Rotates q and k of `qkv` [T, (H + 2 Hkv) D] (cos is None: no rotary) and scatters k and v to their page slots;
-    returns the activation whose first H D columns attention reads.  A fresh prefill writes page-wise; everything else per
-    token, which at decode sizes also finishes the split-K sum (and the bias) of a `native.Partial`."""
+    returns the activation whose first H D columns attention reads.  A fresh prefill writes page-wise, and so does one
+    behind reused pages (`past_lens`); everything else per token, which at decode sizes also finishes the split-K sum (and
+    the bias) of a `native.Partial`."""
     k_pool, v_pool, scales = layer_pools(kv, layer_id)
     if kv.fresh_prefill and not isinstance(qkv, native.Partial):
         return native.rope_kv_write_prefill(qkv, cos, sin, position_ids, cu_seqlens_q, kv.block_tables, k_pool, v_pool,
                                             kv.max_q_len, H, Hkv, D, rot_dim, **scales)
+    if kv.past_lens is not None and not isinstance(qkv, native.Partial):
+        return native.rope_kv_write_prefill_at(qkv, cos, sin, position_ids, cu_seqlens_q, kv.block_tables, k_pool, v_pool,
+                                               kv.max_q_len, H, Hkv, D, rot_dim, kv.past_lens, **scales)
     return native.rope_kv_write(qkv, cos, sin, position_ids, kv.slots, k_pool, v_pool, H, Hkv, D, rot_dim, **scales)
 
 

@@ -31,8 +31,9 @@ from tgis_amd.models.decode_graph import _DecodeGraph, renew_unheld_pool
 from tgis_amd.models.model import Model
 from tgis_amd.models.types import Batch, GenerateError
 from tgis_amd.pb import generate_pb2
-from tgis_amd.utils.kv_cache import (KV_SCALES_HEADROOM, PAGE, PagedKVCache, agree_kv_cache_dtype, agree_kv_scales,
-                                     kv_pool_dtype, kv_scales_stats, pages_for_budget, parse_kv_cache_dtype)
+from tgis_amd.utils.kv_cache import (KV_SCALES_HEADROOM, PAGE, OutOfPages, PagedKVCache, agree_kv_cache_dtype,
+                                     agree_kv_prefix_reuse, agree_kv_scales, kv_pool_dtype, kv_scales_stats,
+                                     pages_for_budget, parse_kv_cache_dtype, parse_kv_prefix_reuse)
 from tgis_amd.utils.rank_group import RankGroup
 from tgis_amd.utils.token_types import InputTokens, TokenInfo
 from tgis_amd.utils.tokens import HeterogeneousNextTokenChooser, get_input_tokens_info, get_token_info
@@ -69,6 +70,10 @@ class FlashCausalLMBatch(Batch):
     kv_cache: Optional[PagedKVCache] = None
     pages: Optional[List[List[int]]] = None
     block_tables: Optional[torch.Tensor] = None
+    # KV prefix reuse (utils/kv_cache.py): the prompts' token ids on the host, from `from_pb` to the prefill, which is their
+    # only consumer; and, from `allocate_pages`, how many leading tokens of each request sit on pages it shares
+    prompt_token_ids: Optional[List[List[int]]] = None
+    reused_lengths: Optional[List[int]] = None
 
     def get_id(self) -> int:
         return self.batch_id
@@ -83,16 +88,45 @@ class FlashCausalLMBatch(Batch):
         batch-weight model (router/src/batch_types.rs:46-118) counts tokens present, not max_output_length."""
         assert self.pages is None
         need = [PagedKVCache.pages_for(n + 1) for n in self.input_lengths]
-        flat = kv_cache.alloc(sum(need))  # raises OutOfPages before anything is taken
+        # KV prefix reuse: the leading pages a request shares with an earlier one come first in its list (pinned by
+        # `match`), the pool deals only the rest.  Tensor-parallel ranks need no collective here: every rank sees the same
+        # request stream and holds the same number of pages (FlashCausalLM, ranks.min_int), and the index is a
+        # deterministic function of the two, so every rank maps the same pages.
+        shared = [[] for _ in need]
+        if getattr(kv_cache, "prefix_reuse", False) and self.reuse_lookup_ok():
+            shared = [kv_cache.match(ids) for ids in self.prompt_token_ids]
+        own = [n - len(s) for n, s in zip(need, shared)]
+        try:
+            flat = kv_cache.alloc(sum(own))  # raises OutOfPages before anything is taken
+        except OutOfPages:
+            for s in shared:
+                kv_cache.free(s)
+            raise
         self.kv_cache = kv_cache
+        self.reused_lengths = [len(s) * PAGE for s in shared]
         # page-major: page p of every sequence, then page p + 1 (kv_cache.py: the pages the decode blocks read at the same
         # time are then neighbours in the pool)
-        self.pages, it = [[] for _ in need], iter(flat)
-        for p in range(max(need, default=0)):
-            for i in range(len(need)):
-                if p < need[i]:
+        self.pages, it = shared, iter(flat)
+        for p in range(max(own, default=0)):
+            for i in range(len(own)):
+                if p < own[i]:
                     self.pages[i].append(next(it))
         self._rebuild_block_tables()
+
+    def reuse_lookup_ok(self) -> bool:
+        """Whether this batch's prefill may start behind cached pages.  Not with prompt-tuning prefixes (`inputs_embeds`:
+        the pad ids in their place do not describe the content), and not when a request wants `details.input_toks`: every
+        prompt position's logits are then needed, and `_process_new_tokens` indexes them by the logical `cu_seqlens`."""
+        return (self.prompt_token_ids is not None and self.inputs_embeds is None
+                and not any(r.details.input_toks for r in self.requests))
+
+    def register_prompt_pages(self):
+        """After the prefill: the full prompt pages become findable (not those of prompt-tuning prefixes)."""
+        ids, self.prompt_token_ids = self.prompt_token_ids, None
+        if ids is None or self.inputs_embeds is not None or not getattr(self.kv_cache, "prefix_reuse", False):
+            return
+        for pages, toks in zip(self.pages, ids):
+            self.kv_cache.register(pages, toks)
 
     def grow_pages(self):
         """Before a decode step: every sequence owns the page its next token (position input_length - 1) lands on."""
@@ -169,12 +203,13 @@ class FlashCausalLMBatch(Batch):
                               return_token_type_ids=False)["input_ids"]
         all_input_ids_tensor = torch.full((len(requests), max(total_lengths)), tokenizer.pad_token_id,
                                           dtype=torch.int64, device=device)
-        input_ids, position_ids, chooser_params, return_logprobs = [], [], [], []
+        input_ids, position_ids, chooser_params, return_logprobs, prompt_token_ids = [], [], [], [], []
         for i, (r, toks, input_length) in enumerate(zip(requests, tokenized, input_lengths)):
             if r.truncate:
                 toks = toks[-r.input_length:]
                 if getattr(tokenizer, "add_bos_token", False):
                     toks[0] = tokenizer.bos_token_id  # keep a BOS at the front after left-truncation
+            prompt_token_ids.append([int(t) for t in toks])
             toks = all_input_ids_tensor.new_tensor(toks)
             # a prefix occupies the first (input_length - r.input_length) positions as pad ids
             all_input_ids_tensor[i, input_length - r.input_length:input_length] = toks
@@ -205,6 +240,7 @@ class FlashCausalLMBatch(Batch):
             max_seqlen=max_seqlen, past_key_values=None, input_lengths=input_lengths,
             total_lengths=total_lengths, all_input_ids_tensor=all_input_ids_tensor,
             next_token_chooser=next_token_chooser, pad_token_id=tokenizer.pad_token_id,
+            prompt_token_ids=prompt_token_ids,
         ), errors
 
     @classmethod
@@ -328,12 +364,16 @@ class FlashCausalLM(Model):
     def __init__(self, model_name: str, revision: Optional[str], deployment_framework: str, dtype: torch.dtype,
                  quantize: Optional[str], model_config: Union[Any] = None, auto_model_class=None,
                  max_sequence_length: Optional[int] = None, engine=None, kv_cache_pages: Optional[int] = None,
-                 kv_cache_dtype: Optional[str] = None, kv_scales: Union[None, str, dict] = None):
+                 kv_cache_dtype: Optional[str] = None, kv_scales: Union[None, str, dict] = None,
+                 kv_prefix_reuse: Optional[bool] = None):
         # KV cache element: "auto" (the model dtype) or "fp8_e4m3" (one byte, utils/kv_cache.py); None reads
         # TGIS_KV_CACHE_DTYPE.  Checked before anything is loaded — except on a rank of a tensor-parallel group, which loads
         # its shard and then tells its peers (agree_kv_cache_dtype below): they sit in a collective only it can release.
+        # kv_prefix_reuse: requests share the cached pages of a common prompt prefix (utils/kv_cache.py); None reads
+        # TGIS_KV_PREFIX_REUSE (true / false, default false).  Checked and agreed on like the cache dtype.
         if (getattr(engine, "world_size", 1) or 1) == 1:
             parse_kv_cache_dtype(kv_cache_dtype)
+            parse_kv_prefix_reuse(kv_prefix_reuse)
         # kv_scales: the calibrated per-layer scales of a one-byte cache, the contents of a kv_cache_scales.json or its path
         # (utils/kv_cache.py, resolve_kv_scales); None looks at TGIS_KV_SCALES, then next to the weights, else they stay 1.0
         if not torch.cuda.is_available():
@@ -366,9 +406,11 @@ class FlashCausalLM(Model):
         self.num_layers = len(inner.layers)
         if hasattr(self.model, "post_init"):
             self.model.post_init()
-        # what tensor-parallel ranks must agree on, in this order on every rank: cache dtype, pages, scales, graph mode, seed
+        # what tensor-parallel ranks must agree on, in this order on every rank: cache dtype, prefix reuse, pages, scales,
+        # graph mode, seed
         self.ranks = RankGroup(engine, self.device)
         self.kv_cache_dtype = agree_kv_cache_dtype(self.ranks, kv_cache_dtype)
+        self.kv_prefix_reuse = agree_kv_prefix_reuse(self.ranks, kv_prefix_reuse)
         if kv_cache_pages is None:
             kv_cache_pages = self._default_kv_pages()
         # Tensor parallel: every rank must hold the SAME number of pages.  Each rank sizes its pool from its own free
@@ -377,7 +419,7 @@ class FlashCausalLM(Model):
         # reports to the router would differ from its peers'.  The smallest pool decides.
         kv_cache_pages = self.ranks.min_int(kv_cache_pages)
         self.kv_cache = PagedKVCache(self.num_layers, self.num_kv_heads, self.head_size, kv_cache_pages, dtype,
-                                     self.device, kv_dtype=self.kv_cache_dtype)
+                                     self.device, kv_dtype=self.kv_cache_dtype, prefix_reuse=self.kv_prefix_reuse)
         # before any page is written and any graph captured: both hold the scales
         scales = agree_kv_scales(self.ranks, kv_scales, self.kv_cache_dtype, self.num_layers,
                                  getattr(engine, "model_path", None))
@@ -483,7 +525,47 @@ class FlashCausalLM(Model):
         return generated_tokens, input_token_infos, decode_errors, forward_time_ns
 
     def _prefill_forward(self, batch: FlashCausalLMBatch):
+        before = self.kv_cache.reuse_stats() if self.kv_prefix_reuse else None
         batch.allocate_pages(self.kv_cache)
+        self._need_all_logits = any(r.details.input_toks for r in batch.requests)
+        if any(batch.reused_lengths):
+            out = self._prefill_suffix_forward(batch)
+        else:
+            out = self._prefill_fresh_forward(batch)
+        batch.register_prompt_pages()
+        if before is not None and logging.getLogger().isEnabledFor(logging.DEBUG):
+            after = self.kv_cache.reuse_stats()
+            logging.debug("KV prefix reuse, batch %s: %s", batch.batch_id, {k: after[k] - before[k] for k in after})
+        return out
+
+    def _prefill_suffix_forward(self, batch: FlashCausalLMBatch):
+        """The prefill of a batch of which at least one request found its leading pages in the cache (KV prefix reuse): only
+        the tokens behind them go through the model, at their true positions, attending over the whole context; their k and
+        v are written page-wise starting at the first own page.  `batch.cu_seqlens`, `position_ids` and the rest of the
+        reference's logical slot contract stay those of the whole prompts."""
+        lens, hits = batch.input_lengths, batch.reused_lengths
+        starts = np.cumsum([0] + lens[:-1])
+        take = np.concatenate([s + np.arange(h, l) for s, h, l in zip(starts, hits, lens)])
+        positions = np.concatenate([np.arange(h, l) for h, l in zip(hits, lens)]).astype(np.int32)
+        slots = np.concatenate([
+            np.asarray(p, dtype=np.int64)[np.arange(h, l) // PAGE] * PAGE + np.arange(h, l) % PAGE
+            for p, h, l in zip(batch.pages, hits, lens)]).astype(np.int32)
+        suffix = [l - h for h, l in zip(hits, lens)]
+        cu_q = np.concatenate([[0], np.cumsum(suffix)]).astype(np.int32)
+        dev = self.device
+        up = (lambda a: torch.from_numpy(a).to(dev, non_blocking=True))
+        cu_q = up(cu_q)
+        max_q, max_ctx = max(suffix), max(lens)
+        # a few tokens over a long cached context are the decode forms of the attention: their key splits apply
+        kv = KVArgs(cache=self.kv_cache, block_tables=batch.block_tables,
+                    ctx_lens=torch.tensor(lens, dtype=torch.int32, device=dev), slots=up(slots),
+                    max_q_len=max_q, max_ctx=max_ctx,
+                    num_splits=native.attn_num_splits(len(lens), self.num_kv_heads, self.num_heads, max_q, max_ctx),
+                    past_lens=native.past_lens_tensor(hits, dev) if FRESH_PREFILL_KV else None)
+        return self.model.forward(batch.input_ids.index_select(0, up(take)), up(positions), cu_q, batch.max_seqlen, None,
+                                  kv, (cu_q[1:] - 1).long())
+
+    def _prefill_fresh_forward(self, batch: FlashCausalLMBatch):
         lens = batch.input_lengths
         slots = np.concatenate([
             np.asarray(p, dtype=np.int64)[np.arange(l) // PAGE] * PAGE + np.arange(l) % PAGE
@@ -493,7 +575,6 @@ class FlashCausalLM(Model):
                     ctx_lens=torch.tensor(lens, dtype=torch.int32, device=dev),
                     slots=torch.from_numpy(slots).to(dev, non_blocking=True),
                     max_q_len=max(lens), max_ctx=max(lens), num_splits=1, fresh_prefill=FRESH_PREFILL_KV)
-        self._need_all_logits = any(r.details.input_toks for r in batch.requests)
         lm_head_indices = None if self._need_all_logits else (batch.cu_seqlens[1:] - 1).long()
         return self.model.forward(batch.input_ids, batch.position_ids.to(torch.int32), batch.cu_seqlens,
                                   batch.max_seqlen, batch.inputs_embeds, kv, lm_head_indices)

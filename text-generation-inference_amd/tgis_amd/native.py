@@ -88,6 +88,10 @@ SIGNATURES = {
                                                 _c_int, _c_int, _c_int, _c_int, _c_int, _vp] + _KV8_ARGS),
     "tgis_rope_kv_write_prefill_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64,
                                                 _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _vp] + _KV8_ARGS),
+    "tgis_rope_kv_write_prefill_at": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64,
+                                               _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    "tgis_rope_kv_write_prefill_at_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64,
+                                                   _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _vp] + _KV8_ARGS + [_vp]),
     "tgis_attn_num_splits": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _c_i64]),
     "tgis_attn_workspace_bytes": (_c_i64, [_c_i64, _c_int, _c_int, _c_int, _c_int]),
     "tgis_attn_paged": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int,
@@ -149,15 +153,15 @@ def kv_is8(pool: Optional[torch.Tensor]) -> bool:
     return pool is not None and pool.dtype in KV8_DTYPES
 
 
-def _call_kv(name: str, args: tuple, k_pool, v_pool, kv_scales) -> None:
+def _call_kv(name: str, args: tuple, k_pool, v_pool, kv_scales, tail: tuple = ()) -> None:
     """One launch of the entry point `name` that writes or reads the KV cache: `name` itself on 16-bit pools, its `_kv8`
-    twin with (kv_dtype, k_scale, v_scale) appended on one-byte pools."""
+    twin with (kv_dtype, k_scale, v_scale) appended on one-byte pools; `tail` follows either way."""
     if kv_is8(k_pool):
         assert kv_is8(v_pool) and k_pool.dtype == v_pool.dtype, "k and v pools must both hold e4m3 codes"
         k_scale, v_scale = (1.0, 1.0) if kv_scales is None else kv_scales
         name += "_kv8"
         args += (KV_FP8_E4M3, float(k_scale), float(v_scale))
-    _check(getattr(load_library(), name)(*args), name)
+    _check(getattr(load_library(), name)(*(args + tail)), name)
 
 
 def dtype_code(dt: torch.dtype) -> int:
@@ -680,6 +684,31 @@ def rope_kv_write_prefill(qkv, cos, sin, positions, cu_seqlens, block_tables, k_
             block_tables.shape[1], _ptr(k_pool), _ptr(v_pool), B, qkv.shape[0], max_len, H, Hkv, D, rot_dim,
             dtype_code(qkv.dtype), _stream())
     _call_kv("tgis_rope_kv_write_prefill", args, k_pool, v_pool, kv_scales)
+    return qkv
+
+
+def past_lens_tensor(past_lens, device) -> torch.Tensor:
+    """[B] int32 on `device` from host ints: how many tokens of each sequence already sit in the cache in front of a
+    prefill's.  Whole pages only, which is what rope_kv_write_prefill_at requires and cannot check on the device."""
+    past = [int(n) for n in past_lens]
+    assert all(n >= 0 and n % 32 == 0 for n in past), f"past_lens must be non-negative multiples of 32: {past}"
+    return torch.tensor(past, dtype=torch.int32, device=device)
+
+
+def rope_kv_write_prefill_at(qkv, cos, sin, positions, cu_seqlens, block_tables, k_pool, v_pool, max_len: int, H: int,
+                             Hkv: int, D: int, rot_dim: int, past_lens, kv_scales=(1.0, 1.0)):
+    """rope_kv_write_prefill behind a cached prefix: token i of sequence b = cache position past_lens[b] + i.  `past_lens`
+    is a list of host ints or the tensor `past_lens_tensor` made of one (a forward makes it once for all its layers);
+    `cu_seqlens` and `max_len` describe the suffix tokens in `qkv`.  Pages in front of past_lens[b] / 32 are not written."""
+    assert qkv.dim() == 2 and qkv.stride(1) == 1 and block_tables.is_contiguous()
+    if not isinstance(past_lens, torch.Tensor):
+        past_lens = past_lens_tensor(past_lens, qkv.device)
+    B = block_tables.shape[0]
+    assert past_lens.dtype == torch.int32 and past_lens.is_contiguous() and past_lens.numel() == B
+    args = (_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(positions), _ptr(cu_seqlens), _ptr(block_tables),
+            block_tables.shape[1], _ptr(k_pool), _ptr(v_pool), B, qkv.shape[0], max_len, H, Hkv, D, rot_dim,
+            dtype_code(qkv.dtype), _stream())
+    _call_kv("tgis_rope_kv_write_prefill_at", args, k_pool, v_pool, kv_scales, tail=(_ptr(past_lens),))
     return qkv
 
 

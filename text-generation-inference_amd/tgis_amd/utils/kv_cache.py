@@ -32,12 +32,23 @@ measurement) leaves a factor for activations larger than any the prompts produce
 precision being flat over its normals.  The result is the file `kv_cache_scales.json` (`save_kv_scales` / `load_kv_scales`)
 that FlashCausalLM looks for (`resolve_kv_scales`: its `kv_scales` argument, TGIS_KV_SCALES, the weights' directory) and
 applies with `PagedKVCache.set_scales` before any page is written or any graph captured.  Without one the scales stay 1.0.
+
+KV prefix reuse (opt-in, `prefix_reuse=True` / TGIS_KV_PREFIX_REUSE; not the reference's prompt-tuning
+`prefix_cache`).  A full page of PROMPT tokens is never rewritten once the prefill has passed it: its owner only writes at
+positions >= its prompt length.  Such pages are indexed by content, key (serial of the entry of the page in front of it, the
+page's 32 token ids) — a chain, so equal keys mean equal whole prefixes, compared as tuples: no hashes to collide.  Serials
+are never reused, so a page whose parent was evicted can never match again.  Pages carry a reference count: 1 from `alloc`,
++1 for every request that maps them through `match`, -1 per `free`.  At 0 an indexed page keeps its contents and waits in
+an LRU; `alloc` takes heap pages first and then evicts from it, oldest first.  `free_pages` counts both.  Everything is
+host-side and deterministic in the request stream, so tensor-parallel ranks, which see the same stream and hold the same
+number of pages, stay in step without talking.
 """
 import heapq
 import json
 import math
 import os
-from typing import Dict, List, Optional, Tuple, Union
+from collections import OrderedDict
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -76,6 +87,34 @@ def agree_kv_cache_dtype(group, value: Optional[str] = None) -> str:
     return name
 
 
+def parse_kv_prefix_reuse(value: Union[None, bool, str] = None) -> bool:
+    """Whether full prompt pages are shared between requests: `value`, or TGIS_KV_PREFIX_REUSE when it is None (unset:
+    false).  A bool, "true" or "false"; anything else raises."""
+    if value is None:
+        value = os.getenv("TGIS_KV_PREFIX_REUSE", "false")
+    if isinstance(value, bool):
+        return value
+    name = str(value).strip().lower()
+    if name not in ("true", "false"):
+        raise ValueError(f"KV prefix reuse {value!r} is not supported (true or false)")
+    return name == "true"
+
+
+def agree_kv_prefix_reuse(group, value: Union[None, bool, str] = None) -> bool:
+    """`parse_kv_prefix_reuse(value)`, the same on every rank of `group` (utils/rank_group.py), like agree_kv_cache_dtype:
+    ranks that disagreed would map different pages for the same request and write different block tables."""
+    try:
+        flag, error = parse_kv_prefix_reuse(value), None
+    except ValueError as e:
+        flag, error = False, e
+    group.fail_together(error, "another tensor-parallel rank was given an unsupported KV prefix reuse setting "
+                               "(TGIS_KV_PREFIX_REUSE)")
+    if group.min_int(int(flag)) != group.max_int(int(flag)):
+        raise ValueError(f"tensor-parallel ranks disagree on KV prefix reuse (this rank: {str(flag).lower()}): set "
+                         f"TGIS_KV_PREFIX_REUSE alike on every rank")
+    return flag
+
+
 def kv_pool_dtype(kv_dtype: str, model_dtype: torch.dtype) -> torch.dtype:
     """Element type of the pool tensor: the model dtype, or uint8 holding e4m3 codes."""
     return torch.uint8 if parse_kv_cache_dtype(kv_dtype) == "fp8_e4m3" else model_dtype
@@ -92,13 +131,16 @@ def pages_for_budget(budget_bytes: int, num_layers: int, num_kv_heads: int, head
     return max(min_pages, int(budget_bytes) // kv_bytes_per_page(num_layers, num_kv_heads, head_dim, elem_bytes))
 
 
+REUSE_STATS = ("lookups", "hit_pages", "looked_up_pages", "registered", "evictions")
+
+
 class OutOfPages(RuntimeError):
     """Maps to gRPC RESOURCE_EXHAUSTED like a CUDA OOM does in the reference (server.py:48-51)."""
 
 
 class PagedKVCache:
     def __init__(self, num_layers: int, num_kv_heads: int, head_dim: int, num_pages: int, dtype, device,
-                 kv_dtype: str = "auto"):
+                 kv_dtype: str = "auto", prefix_reuse: bool = False):
         self.num_layers, self.num_kv_heads, self.head_dim = num_layers, num_kv_heads, head_dim
         self.num_pages = num_pages
         self.kv_dtype = parse_kv_cache_dtype(kv_dtype)
@@ -114,10 +156,18 @@ class PagedKVCache:
         self.pool = torch.zeros((num_layers, 2, num_pages + 1, num_kv_heads, PAGE * head_dim), dtype=dtype, device=device)
         self.null_page = num_pages
         self._free = list(range(num_pages))  # a heap (heapq), trivially one to begin with
+        # KV prefix reuse (module docstring); none of this is looked at when it is off
+        self.prefix_reuse = bool(prefix_reuse)
+        self._refs: Dict[int, int] = {}  # handed-out page -> holders
+        self._index: Dict[Tuple[int, Tuple[int, ...]], Tuple[int, int]] = {}  # (parent serial, tokens) -> (page, serial)
+        self._entry: Dict[int, Tuple[Tuple[int, Tuple[int, ...]], int]] = {}  # indexed page -> (its key, its serial)
+        self._lru: "OrderedDict[int, None]" = OrderedDict()  # indexed pages nobody holds, oldest first
+        self._serial = 0
+        self._stats = dict.fromkeys(REUSE_STATS, 0)
 
     @property
     def free_pages(self) -> int:
-        return len(self._free)
+        return len(self._free) + len(self._lru)
 
     def bytes_per_token(self) -> int:
         return self.num_layers * 2 * self.num_kv_heads * self.head_dim * self.pool.element_size()
@@ -140,6 +190,12 @@ class PagedKVCache:
             raise ValueError("KV cache scales cannot change while pages are handed out")
         k, v = _checked_scales(k_scales, self.num_layers, "k_scales"), _checked_scales(v_scales, self.num_layers, "v_scales")
         self.k_scales, self.v_scales = k, v
+        # cached pages hold codes of the old scales: forget them
+        for p in self._lru:
+            heapq.heappush(self._free, p)
+        self._lru.clear()
+        self._index.clear()
+        self._entry.clear()
 
     def k_pool(self, layer: int) -> torch.Tensor:
         return self.pool[layer, 0]
@@ -148,14 +204,90 @@ class PagedKVCache:
         return self.pool[layer, 1]
 
     def alloc(self, n: int) -> List[int]:
-        """The n lowest free page ids, ascending.  All or nothing: OutOfPages before anything is taken."""
-        if n > len(self._free):
-            raise OutOfPages(f"KV cache exhausted: need {n} pages, {len(self._free)} free of {self.num_pages}")
-        return [heapq.heappop(self._free) for _ in range(n)]
+        """The n lowest free page ids, ascending.  All or nothing: OutOfPages before anything is taken.
+        With prefix reuse: heap pages first, then the least recently used cached pages, whose index entries go."""
+        if not self.prefix_reuse:
+            if n > len(self._free):
+                raise OutOfPages(f"KV cache exhausted: need {n} pages, {len(self._free)} free of {self.num_pages}")
+            return [heapq.heappop(self._free) for _ in range(n)]
+        if n > self.free_pages:
+            raise OutOfPages(f"KV cache exhausted: need {n} pages, {self.free_pages} free of {self.num_pages} "
+                             f"({len(self._lru)} of them cached)")
+        pages = [heapq.heappop(self._free) for _ in range(min(n, len(self._free)))]
+        while len(pages) < n:
+            p, _ = self._lru.popitem(last=False)
+            del self._index[self._entry.pop(p)[0]]
+            self._stats["evictions"] += 1
+            pages.append(p)
+        for p in pages:
+            self._refs[p] = 1
+        return pages
 
     def free(self, pages: List[int]):
-        for p in pages:
-            heapq.heappush(self._free, p)
+        """Gives up one hold on each page.  With prefix reuse a page goes on only when its last holder lets go: back to the
+        heap, or, indexed, to the young end of the LRU with its contents kept — the pages of one call deepest first, so
+        that a chain is evicted from its tail and no page outlives the parent it can only be found through."""
+        if not self.prefix_reuse:
+            for p in pages:
+                heapq.heappush(self._free, p)
+            return
+        for p in reversed(pages):
+            self._refs[p] -= 1
+            if self._refs[p] == 0:
+                del self._refs[p]
+                if p in self._entry:
+                    self._lru[p] = None
+                else:
+                    heapq.heappush(self._free, p)
+
+    # ---- KV prefix reuse ------------------------------------------------------------------------------------------------------
+    def match(self, token_ids: Sequence[int]) -> List[int]:
+        """The longest chain of indexed pages that holds a prefix of the prompt `token_ids`, at most (len - 1) // 32 of them:
+        one prompt token at least is always computed, its logits choose the first generated token.  Every page returned is
+        pinned (one more holder, out of the LRU): the caller keeps it or gives it back with `free`."""
+        if not self.prefix_reuse:
+            return []
+        cap = max(len(token_ids) - 1, 0) // PAGE
+        self._stats["lookups"] += 1
+        self._stats["looked_up_pages"] += cap
+        pages, parent = [], 0
+        for i in range(cap):
+            hit = self._index.get((parent, tuple(token_ids[i * PAGE:(i + 1) * PAGE])))
+            if hit is None:
+                break
+            page, parent = hit
+            self._lru.pop(page, None)
+            self._refs[page] = self._refs.get(page, 0) + 1
+            pages.append(page)
+        self._stats["hit_pages"] += len(pages)
+        return pages
+
+    def register(self, pages: Sequence[int], token_ids: Sequence[int]) -> None:
+        """After a prefill has written them: indexes every full page of the prompt (page p < len // 32 of the request's page
+        list `pages`) that is not indexed yet, chained to the page in front of it.  Where the same content is indexed
+        already on another page, that entry stays, this page stays private and the chain goes on from the entry."""
+        if not self.prefix_reuse:
+            return
+        parent = 0
+        for i in range(len(token_ids) // PAGE):
+            page = pages[i]
+            if page in self._entry:
+                parent = self._entry[page][1]
+                continue
+            key = (parent, tuple(token_ids[i * PAGE:(i + 1) * PAGE]))
+            if key in self._index:
+                parent = self._index[key][1]
+                continue
+            self._serial += 1
+            self._index[key] = (page, self._serial)
+            self._entry[page] = (key, self._serial)
+            self._stats["registered"] += 1
+            parent = self._serial
+
+    def reuse_stats(self) -> Dict[str, int]:
+        """Counters since construction: `lookups` (match calls), `looked_up_pages` (pages they could have hit), `hit_pages`,
+        `registered` (index entries made), `evictions` (entries dropped for their page).  All zero with reuse off."""
+        return dict(self._stats)
 
     @staticmethod
     def pages_for(tokens: int) -> int:
