@@ -179,6 +179,40 @@ int tgis_dense_gemm_rope_kv8(const void* x, int64_t ldx, const void* prepared, c
 int tgis_gptq_dequant_f16(const void* prepared, void* w_out, int64_t K, int64_t N, int64_t groups,
                           int flags, void* stream);
 
+/* ---- GPTQ 8-bit linear (replaces the Triton QuantLinear that get_linear gives every GPTQ width but 4,
+ *      utils/layers.py:184-199; normative arithmetic utils/gptq/quant_linear.py:130-192,259) -------------------------------
+ * W[k,n] = f16((q[k,n] - (z[g(k),n] + 1)) * s[g(k),n]), q and z unsigned bytes, z + 1 not masked back to a byte (a stored
+ * 255 is a zero point of 256); the weight is rounded to f16 once, accumulation is fp32, the output f16 (+ bias).
+ * Every entry point requires K % 32 == 0, N % 32 == 0 and (K / groups) % 16 == 0 and refuses anything else. */
+
+/* Bytes of the prepared image of a [K,N] 8-bit matrix with `groups` groups (w8 [N/32][K/64 + 1][2][64][16 B]
+ * + sz [N/32][groups][32]).  Call site: QuantLinear.__init__ / pack, utils/gptq/quant_linear.py:130-192,259. */
+int64_t tgis_gptq8_prepared_bytes(int64_t K, int64_t N, int64_t groups);
+
+/* Repack qweight [K/4, N] int32, qzeros [groups, N/4] int32, scales [groups, N] f16 into the image; g_idx_host / perm_out as
+ * tgis_gptq_prepare (act-order rows are sorted by group, perm_out receives the gather the activation needs).  flags must
+ * be 0.  One-time, at load: replaces the buffers QuantLinear keeps (utils/gptq/quant_linear.py:130-192,259). */
+int tgis_gptq8_prepare(const int32_t* qweight, const int32_t* qzeros, const void* scales, const int32_t* g_idx_host,
+                       int32_t* perm_out, int64_t K, int64_t N, int64_t groups, int flags, void* prepared, void* stream);
+
+/* Workspace of one tgis_gptq8_gemm_f16 call: the 4096-byte counter region of the int4 convention (zero before and after
+ * the call; this launch does not touch it) followed by the fp32 split-K slabs (utils/gptq/quant_linear.py:130-192,259). */
+int64_t tgis_gptq8_gemm_workspace_bytes(int64_t M, int64_t K, int64_t N);
+
+/* out[M,N] f16 = x[M,K] f16 @ dequant(W) (+ bias), 1 <= M <= 64 (a larger M is an argument error: the caller dequantises
+ * with tgis_gptq8_dequant_f16 and uses a library GEMM).  ldx / ldo: row strides in elements (ldx % 8 == 0, x 16-byte
+ * aligned).  perm (int32 [K] or NULL) gathers x columns, -1 reads a zero.  act 0, or 1: x is [M, 2K] and the operand is
+ * silu(x[:, :K]) * x[:, K:].  Deterministic: k-parts and split-K slabs are summed in fixed order.  No allocation, no
+ * synchronisation.  Replaces QuantLinear.forward, utils/gptq/quant_linear.py:130-192,259. */
+int tgis_gptq8_gemm_f16(const void* x, int64_t ldx, const void* prepared, const void* bias, const int32_t* perm, void* out,
+                        int64_t ldo, int64_t M, int64_t K, int64_t N, int64_t groups, int act, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
+/* Dense f16 [K,N] (row-major, rows in image order) of a prepared 8-bit matrix, for the large-M library GEMM; bit-equal to
+ * ((q - z - 1).float() * s.float()).half().  Replaces the dequantisation inside QuantLinear.forward,
+ * utils/gptq/quant_linear.py:130-192,259. */
+int tgis_gptq8_dequant_f16(const void* prepared, void* w_out, int64_t K, int64_t N, int64_t groups, void* stream);
+
 /* ---- dense skinny GEMM (replaces F.linear / torch.mm at decode sizes, utils/layers.py:110-111,
  *      lm_head utils/layers.py:261) -------------------------------------------------------------- */
 int64_t tgis_dense_prepared_bytes(int64_t N, int64_t K);

@@ -32,8 +32,9 @@ class InferenceEngine(BaseInferenceEngine):
 
 
 def llama_tensors(config, quantize: Optional[str], seed: int, groupsize: int = 128, device="cpu",
-                  dtype=torch.float16, head_scale: float = 1.0) -> Dict[str, torch.Tensor]:
-    """Seeded full (unsharded) Llama checkpoint as a name -> tensor dict in HF naming."""
+                  dtype=torch.float16, head_scale: float = 1.0, bits: int = 4) -> Dict[str, torch.Tensor]:
+    """Seeded full (unsharded) Llama checkpoint as a name -> tensor dict in HF naming.  bits: GPTQ width, 4 or 8."""
+    assert bits in (4, 8), bits
     g = torch.Generator(device=device).manual_seed(seed)
     E, I, V = config.hidden_size, config.intermediate_size, config.vocab_size
     D = E // config.num_attention_heads
@@ -56,7 +57,23 @@ def llama_tensors(config, quantize: Optional[str], seed: int, groupsize: int = 1
                                ).to(torch.float16)
         t[f"{name}.g_idx"] = (torch.arange(k, device=device, dtype=torch.int32) // groupsize)
 
-    lin = gptq if quantize == "gptq" else dense
+    def gptq8(name, n, k):
+        G = k // groupsize
+        q = torch.randint(0, 256, (k // 4, 4, n), generator=g, device=device, dtype=torch.int64)
+        shifts = 8 * torch.arange(4, device=device, dtype=torch.int64)
+        qw = (q << shifts.view(1, 4, 1)).sum(1)
+        t[f"{name}.qweight"] = torch.where(qw >= 2**31, qw - 2**32, qw).to(torch.int32)
+        # stored zero bytes 118..134 (true zero points 119..135, centred on the mean code 127.5), for the reason given
+        # above: a common offset of the dequantised weights is a rank-one term that overflows fp16 activations
+        zn = torch.randint(118, 135, (G, n // 4, 4), generator=g, device=device, dtype=torch.int64)
+        zw = (zn << shifts).sum(-1)
+        t[f"{name}.qzeros"] = torch.where(zw >= 2**31, zw - 2**32, zw).to(torch.int32)
+        # the 4-bit recipe's weight range (+-0.02 * U(0.5, 1.5)) over 255 steps instead of 15
+        t[f"{name}.scales"] = ((torch.rand(G, n, generator=g, device=device) + 0.5) * (2.0 / 255.0) * 0.02
+                               ).to(torch.float16)
+        t[f"{name}.g_idx"] = (torch.arange(k, device=device, dtype=torch.int32) // groupsize)
+
+    lin = (gptq8 if bits == 8 else gptq) if quantize == "gptq" else dense
     t["model.embed_tokens.weight"] = (torch.randn(V, E, generator=g, device=device) * 0.02).to(dtype)
     for i in range(config.num_hidden_layers):
         p = f"model.layers.{i}"

@@ -47,6 +47,12 @@ SIGNATURES = {
     "tgis_gptq_gemm_f16_partial": (_c_int, [_vp, _c_i64, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp, _c_i64,
                                             ctypes.POINTER(_c_int), ctypes.POINTER(_c_i64), _vp]),
     "tgis_gptq_dequant_f16": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _vp]),
+    "tgis_gptq8_prepared_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
+    "tgis_gptq8_prepare": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _vp, _vp]),
+    "tgis_gptq8_gemm_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
+    "tgis_gptq8_gemm_f16": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
+                                     _c_int, _vp, _c_i64, _vp]),
+    "tgis_gptq8_dequant_f16": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp]),
     "tgis_dense_gemm_rope": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64, _c_i64,
                                       _c_i64, _c_i64, _c_i64, _c_int, _vp]),
     "tgis_dense_gemm_rope_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64,
@@ -299,7 +305,8 @@ class GptqWeight:
             self.flags = 2 | (int(rope[0]) << 8) | (int(rope[1]) << 20)
         self.partial_plan = {}  # pass count -> (slab bytes, S, ld) of the deferred-reduce form, filled on first use
         if bits != 4:
-            raise TgisHipError("only 4-bit GPTQ is supported (exllamav2.py:105)")
+            raise TgisHipError(f"GPTQ is supported at 4 and 8 bits, not {bits}; this is the 4-bit image (exllamav2.py:105), "
+                               "8 bits take Gptq8Weight")
         lib = load_library()
         self.K = qweight.shape[0] * 8
         self.N = qweight.shape[1]
@@ -478,6 +485,80 @@ def gptq_dequant(w: GptqWeight) -> torch.Tensor:
     out = torch.empty((w.K, w.N), dtype=torch.float16, device=w.image.device)
     _check(load_library().tgis_gptq_dequant_f16(_ptr(w.image), _ptr(out), w.K, w.N, w.groups, w.flags, _stream()),
            "tgis_gptq_dequant_f16")
+    return out
+
+
+# ---- GPTQ, 8 bits --------------------------------------------------------------------------------------
+GPTQ8_MAX_M = 64  # rows the fused 8-bit kernel serves (above: gptq8_dequant + a library GEMM)
+
+
+class Gptq8Weight:
+    """Prepared 8-bit GPTQ matrix (csrc/gptq8_gemm_body.h); what QuantLinear holds for bits = 8
+    (utils/gptq/quant_linear.py:259).  Takes the g_idx forms of GptqWeight: None, a [K] tensor (act-order when not
+    trivial), or ("perm", gather index [K] with -1 = zero, activation columns) for rows already in image order."""
+
+    def __init__(self, qweight, qzeros, scales, g_idx, bits: int, groupsize: int):
+        if bits != 8:
+            raise TgisHipError(f"Gptq8Weight is the 8-bit image, not {bits} bits")
+        lib = load_library()
+        self.K = qweight.shape[0] * 4
+        self.N = qweight.shape[1]
+        self.groups = qzeros.shape[0]
+        dev = qweight.device
+        qweight = qweight.contiguous()
+        qzeros = qzeros.contiguous()
+        scales = scales.to(torch.float16).contiguous()
+        self.perm = None
+        self.in_features = self.K  # columns of the activation (differs from K only for padded act-order row shards)
+        gi = perm_buf = explicit = None
+        if isinstance(g_idx, tuple):
+            _, explicit, self.in_features = g_idx
+            assert explicit.numel() == self.K
+            g_idx = None
+        if g_idx is not None:
+            assert g_idx.numel() == self.K
+            gi = g_idx.to("cpu", torch.int32).contiguous()
+            perm_buf = torch.empty(self.K, dtype=torch.int32, device=dev)
+        self.image = torch.empty(lib.tgis_gptq8_prepared_bytes(self.K, self.N, self.groups), dtype=torch.uint8, device=dev)
+        _check(
+            lib.tgis_gptq8_prepare(_ptr(qweight), _ptr(qzeros), _ptr(scales), gi.data_ptr() if gi is not None else None,
+                                   _ptr(perm_buf), self.K, self.N, self.groups, 0, _ptr(self.image), _stream()),
+            "tgis_gptq8_prepare")
+        if gi is not None:
+            gs = self.K // self.groups
+            if not bool((gi == (torch.arange(self.K, dtype=torch.int32) // gs)).all()):
+                self.perm = perm_buf
+        if explicit is not None:
+            self.perm = explicit.to(dev, torch.int32).contiguous()
+        torch.cuda.current_stream().synchronize()  # qweight/qzeros/scales may be freed by the caller
+
+    def workspace_bytes(self, M: int) -> int:
+        return load_library().tgis_gptq8_gemm_workspace_bytes(M, self.K, self.N)
+
+
+def gptq8_gemm(x, w: Gptq8Weight, ws: Workspace, bias=None, act: int = 0, out=None):
+    """out[M <= 64, N] = x @ dequant(W) (+ bias); act 1: x is [M, 2K] and silu(x[:, :K]) * x[:, K:] is the operand."""
+    assert x.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1
+    M = x.shape[0]
+    assert x.shape[1] == (2 * w.in_features if act == 1 else w.in_features), (x.shape, w.in_features, act)
+    assert act != 1 or w.in_features == w.K
+    if out is None:
+        out = torch.empty((M, w.N), dtype=torch.float16, device=x.device)
+    ws.ensure(w.workspace_bytes(M))
+    _check(
+        load_library().tgis_gptq8_gemm_f16(_ptr(x), x.stride(0), _ptr(w.image), _ptr(bias), _ptr(w.perm), _ptr(out),
+                                           out.stride(0), M, w.K, w.N, w.groups, act, ws.ptr, ws.nbytes, _stream()),
+        "tgis_gptq8_gemm_f16")
+    return out
+
+
+def gptq8_dequant(w: Gptq8Weight, out=None) -> torch.Tensor:
+    """Dense f16 [K,N] (rows in the prepared order: permuted by w.perm for act-order matrices)."""
+    if out is None:
+        out = torch.empty((w.K, w.N), dtype=torch.float16, device=w.image.device)
+    assert out.shape == (w.K, w.N) and out.dtype == torch.float16 and out.is_contiguous()
+    _check(load_library().tgis_gptq8_dequant_f16(_ptr(w.image), _ptr(out), w.K, w.N, w.groups, _stream()),
+           "tgis_gptq8_dequant_f16")
     return out
 
 

@@ -3,7 +3,8 @@
 Mirrors utils/layers.py of the reference: `FastLinear` (:104-111), the `get_linear` quant registry
 (:172-203), `TensorParallelHead` (:215-277), `TensorParallelColumnLinear` (:280-297),
 `TensorParallelRowLinear` (all-reduce, :300-322), `TensorParallelEmbedding` (:325-357) and
-`PositionRotaryEmbedding` (:406-490); `Ex4bitLinearV2` mirrors utils/gptq/exllamav2.py:100-144.
+`PositionRotaryEmbedding` (:406-490); `Ex4bitLinearV2` mirrors utils/gptq/exllamav2.py:100-144, `Gptq8Linear` the
+`QuantLinear` of 8-bit checkpoints (utils/gptq/quant_linear.py:259).
 Every forward runs a kernel of libtgis_hip.so (decode-sized M) or, for prefill-sized M, a library GEMM
 on the same device; there is no CPU path."""
 import math
@@ -109,11 +110,31 @@ class FastLinear:
     __call__ = forward
 
 
+_TEMP_DQ = {}
+
+
+def _dequant_scratch(device, height: int, width: int) -> torch.Tensor:
+    """The one dense f16 [K, N] scratch that large-M GPTQ forwards (either width) dequantise into."""
+    key = (str(device), height, width)
+    buf = _TEMP_DQ.get(key)
+    if buf is None:
+        _TEMP_DQ.clear()  # one scratch at a time, like exllama's temp_dq
+        buf = _TEMP_DQ[key] = torch.empty((height, width), dtype=torch.float16, device=device)
+    return buf
+
+
+def _gather_columns(x: torch.Tensor, q_handle) -> torch.Tensor:
+    """x[:, perm] for an act-order image; index -1 (a pad row of a padded shard) reads a zero column."""
+    perm = q_handle.perm.long()
+    if q_handle.in_features != q_handle.K:
+        x = torch.nn.functional.pad(x, (0, 1))
+        perm = torch.where(perm < 0, torch.full_like(perm, x.shape[1] - 1), perm)
+    return x.index_select(1, perm)
+
+
 class Ex4bitLinearV2:
     """4-bit GPTQ linear.  Construction keeps the checkpoint tensors; `post_init` repacks them for the
     kernels (the reference defers this the same way, server.py:347-354)."""
-    _temp_dq = {}
-
     def __init__(self, qweight, qzeros, scales, g_idx, bias, bits, groupsize):
         assert bits == 4
         self.device = qweight.device
@@ -153,13 +174,7 @@ class Ex4bitLinearV2:
         return got
 
     def _dequant_scratch(self) -> torch.Tensor:
-        key = (str(self.device), self.height, self.width)
-        buf = Ex4bitLinearV2._temp_dq.get(key)
-        if buf is None:
-            Ex4bitLinearV2._temp_dq.clear()  # one scratch at a time, like exllama's temp_dq
-            buf = Ex4bitLinearV2._temp_dq[key] = torch.empty((self.height, self.width), dtype=torch.float16,
-                                                             device=self.device)
-        return buf
+        return _dequant_scratch(self.device, self.height, self.width)
 
     def wants_fragments(self, rows: int, act: int = 0) -> bool:
         """Should the producer of this linear's operand write it in fragment order (native.FragAct) for `rows` decode
@@ -199,15 +214,58 @@ class Ex4bitLinearV2:
     def _large_m(self, x: torch.Tensor) -> torch.Tensor:
         """prefill-sized M: dequantise once into scratch, then a library GEMM (exllamav2.py:87 "M > 50")."""
         if self.q_handle.perm is not None:
-            perm = self.q_handle.perm.long()
-            if self.q_handle.in_features != self.q_handle.K:  # padded shard: index -1 reads a zero column
-                x = torch.nn.functional.pad(x, (0, 1))
-                perm = torch.where(perm < 0, torch.full_like(perm, x.shape[1] - 1), perm)
-            x = x.index_select(1, perm)
+            x = _gather_columns(x, self.q_handle)
         w = self._dequant_scratch()
         native._check(native.load_library().tgis_gptq_dequant_f16(
             self.q_handle.image.data_ptr(), w.data_ptr(), self.height, self.width, self.q_handle.groups,
             self.q_handle.flags, native._stream()), "tgis_gptq_dequant_f16")
+        out = torch.matmul(x, w)
+        if self.bias is not None:
+            out.add_(self.bias)
+        return out
+
+    __call__ = forward
+
+
+class Gptq8Linear:
+    """8-bit GPTQ linear: the QuantLinear the reference builds for bits = 8 (utils/layers.py:184-199,
+    utils/gptq/quant_linear.py:259).  Deliberately without the gate_up / rope_heads / wants_fragments attributes of
+    Ex4bitLinearV2: the models' duck typing then takes their generic paths (separate rope + cache write,
+    down_proj(act=1), a reduced f16 tensor where partial=True is asked)."""
+
+    def __init__(self, qweight, qzeros, scales, g_idx, bias, bits, groupsize):
+        if bits != 8:
+            raise NotImplementedError("Gptq8Linear is the 8-bit linear.")
+        self.device = qweight.device
+        self.qweight, self.qzeros, self.scales = qweight, qzeros, scales
+        self.g_idx = g_idx if isinstance(g_idx, tuple) else (g_idx.cpu() if g_idx is not None else None)
+        self.bias = bias
+        self.bits, self.groupsize = bits, groupsize
+        self.height = qweight.shape[0] * 4
+        self.width = qweight.shape[1]
+        self.q_handle: Optional[native.Gptq8Weight] = None
+
+    def post_init(self):
+        self.q_handle = native.Gptq8Weight(self.qweight, self.qzeros, self.scales, self.g_idx, self.bits, self.groupsize)
+        self.qweight = self.qzeros = self.scales = None  # the prepared image replaces them
+
+    def forward(self, x, act: int = 0, partial: bool = False, out_frag: bool = False):
+        """Always the reduced f16 tensor: `partial` is accepted and not honoured (no deferred-reduce form at 8 bits)."""
+        assert not out_frag and not isinstance(x, native.FragAct), "8-bit linears take and give row-major activations"
+        if self.q_handle is None:
+            self.post_init()
+        if act and self.q_handle.in_features != self.q_handle.K:
+            # a padded act-order row shard: the kernel's act 1 finds the up half K columns behind the gate half, which holds
+            # only while the activation has K columns — SiLU * up runs as a launch of its own in front of the GEMM
+            x, act = native.act_mul(x, self.q_handle.in_features), 0
+        if x.shape[0] <= native.GPTQ8_MAX_M:
+            return native.gptq8_gemm(x, self.q_handle, workspace(x.device), bias=self.bias, act=act)
+        # the reference's own M > 50 path (exllamav2.py:87): dequantise once into the shared scratch, then a library GEMM
+        if act:
+            x = native.act_mul(x, self.q_handle.in_features)
+        if self.q_handle.perm is not None:
+            x = _gather_columns(x, self.q_handle)
+        w = native.gptq8_dequant(self.q_handle, out=_dequant_scratch(self.device, self.height, self.width))
         out = torch.matmul(x, w)
         if self.bias is not None:
             out.add_(self.bias)
@@ -224,7 +282,11 @@ def get_linear(weight, bias, quantize):
             qweight, qzeros, scales, g_idx, bits, groupsize, _use = weight
         except Exception:
             raise NotImplementedError("The passed weight is not `gptq` compatible, loader needs to be updated.")
-        return Ex4bitLinearV2(qweight, qzeros, scales, g_idx, bias, bits, groupsize)
+        if bits == 4:
+            return Ex4bitLinearV2(qweight, qzeros, scales, g_idx, bias, bits, groupsize)
+        if bits == 8:
+            return Gptq8Linear(qweight, qzeros, scales, g_idx, bias, bits, groupsize)
+        raise NotImplementedError("Only 4 and 8 bits are supported.")
     raise NotImplementedError(f"Quantization `{quantize}` is not implemented yet.")
 
 
