@@ -80,7 +80,10 @@ __global__ void gptq8_dequant_kernel(const uint8_t* __restrict__ prep, int64_t o
     const float s = (float)szh[0], z1 = (float)szh[1] - 1024.f;
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-        const float v = ((float)((q >> (8 * b)) & 255u) - z1) * s;  // exact in fp32 (9 x 11 bits): one rounding, to f16
+        float v = ((float)((q >> (8 * b)) & 255u) - z1) * s;  // exact in fp32 (9 x 11 bits): one rounding, to f16
+        // the product stays apart from its rounding: fused into one v_fma_mixlo_f16 (a * s + 0), a product of -0 (s = 0
+        // under a negative q - z - 1) came out as +0
+        asm volatile("" : "+v"(v));
         wout[(int64_t)(k0 + b) * N + n] = (f16)v;
     }
 }
