@@ -409,6 +409,42 @@ int tgis_decode_advance(const int64_t* ids, int64_t* ids_copy, int64_t* position
                         int64_t ld_all, int32_t* cu_seqlens, const int32_t* cu_seqlens_q, int64_t* stage_ids,
                         int32_t* stage_positions, int64_t B, void* stream);
 
+/* ---- prompt-lookup speculative decoding (greedy requests) -----------------------------------------
+ * The reference verifies several drafted tokens per forward (models/paged_causal_lm.py:481-562 the step, :630-657 when it
+ * is taken, utils/paged.py the flattened inputs and the acceptance); its drafter is a trained MLP speculator, here the
+ * drafts are looked up in the request's own context.  K drafts per request, 0 <= K <= 7; a verify forward has K + 1 rows
+ * per request: its latest token, then its drafts.  No allocation, no sync; B = 0 returns TGIS_OK. */
+/* The K + 1-row form of tgis_decode_slots (utils/paged.py prepare_inputs_with_speculation: input ids, positions and slot
+ * mapping of the flattened candidates).  positions [B] int32: position of each request's latest token; latest_ids [B]
+ * int64; drafts [B, K] int64 (K = 0: may be NULL).  Row r = b (K + 1) + j: input_ids[r] = j ? drafts[b][j - 1] :
+ * latest_ids[b]; positions_out[r] = positions[b] + j; slots[r] = block_tables[b][pos / 32] * 32 + pos % 32 of that
+ * position (a table index past max_pages - 1 is clamped to it); ctx_lens[b] = positions[b] + K + 1. */
+int tgis_spec_stage(const int32_t* positions, const int64_t* latest_ids, const int64_t* drafts, int64_t K,
+                    const int32_t* block_tables, int64_t max_pages, int64_t* input_ids, int32_t* positions_out,
+                    int32_t* slots, int32_t* ctx_lens, int64_t B, void* stream);
+/* The K + 1-token form of tgis_decode_advance (utils/paged.py process_outputs_with_speculation: the longest correct
+ * candidate prefix; paged_causal_lm.py:530-562 what is emitted and the new inputs).  argmax_ids int64 / argmax_logprobs f32
+ * [B, K + 1]: the greedy choice behind every verify row; drafts [B, K].  With a = the longest prefix of argmax_ids[b][j] ==
+ * drafts[b][j], request b emits the a + 1 tokens argmax_ids[b][0 .. a]:
+ *   n_emit [B] int32 = a + 1;  out_ids int64 / out_logprobs f32 [B, K + 1] (NULL: skip): the emitted entries, then -1 / 0;
+ *   all_input_ids[b][position_ids[b] + 1 + j] = emitted id j (row stride ld_all, NULL: skip; columns >= ld_all are not
+ *   written);  position_ids int64 [B] += n_emit;  latest_ids [B] (NULL: skip) = the last emitted id;  cu_seqlens int32
+ *   [B + 1] (NULL: skip): entry b += sum of n_emit[i], i < b;  stage_ids int64 [B] / stage_positions int32 [B] (NULL:
+ *   skip): the new latest ids / positions once more, e.g. into the static inputs of a captured step.
+ * One workgroup serves the batch.  K = 0 is tgis_decode_advance (cu_seqlens_q = arange) bit for bit. */
+int tgis_spec_accept(const int64_t* argmax_ids, const float* argmax_logprobs, const int64_t* drafts, int64_t K,
+                     int32_t* n_emit, int64_t* out_ids, float* out_logprobs, int64_t* latest_ids, int64_t* position_ids,
+                     int64_t* all_input_ids, int64_t ld_all, int32_t* cu_seqlens, int64_t* stage_ids,
+                     int32_t* stage_positions, int64_t B, void* stream);
+/* The drafter (stands where the reference calls its speculator, utils/paged.py prepare_inputs_with_speculation): prompt
+ * lookup.  The context of request b is all_input_ids[b][0 .. len), len = position_ids[b] + 1 (clamped to [0, ld_all]).  For
+ * n = N .. 1 (1 <= N <= 4): the largest j with j + n < len and tokens[j .. j + n) == tokens[len - n .. len); the first n
+ * that has one wins.  drafts[b] [K] int64 (1 <= K <= 7) = tokens[j + n .. j + n + K), id 0 where the context ends;
+ * hits[b] int32 = n, or 0 with all-zero drafts when nothing matched; hits_copy [B] (NULL: skip) receives hits once more
+ * (the buffer that travels to the host).  One workgroup per request. */
+int tgis_spec_propose(const int64_t* all_input_ids, int64_t ld_all, const int64_t* position_ids, int64_t K, int64_t N,
+                      int64_t* drafts, int32_t* hits, int32_t* hits_copy, int64_t B, void* stream);
+
 /* ---- greedy sampling (Greedy + log_softmax + gather, utils/tokens.py:44-46,238-271,388-397) ------ */
 /* Per row: token = argmax (lowest id on ties), logprob = logit[token] - logsumexp(row).
  * logits [B,V] f32 (logits_f32 != 0) or model dtype. ids_out int64 [B], logprob_out f32 [B].

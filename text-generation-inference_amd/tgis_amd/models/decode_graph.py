@@ -1,5 +1,6 @@
 """The captured decode step of FlashCausalLM: static buffers + HIP graph per (batch-size bucket, table width), the choice
-between one graph and a chain of segments under tensor parallelism, and the memory pool the captures share.
+between one graph and a chain of segments under tensor parallelism, and the memory pool the captures share.  With
+speculative decoding on (utils/spec_decode.py) the verify step is captured the same way, per (bucket, table width, K).
 
 The state stays on the model, where bench.py, the tests and tools/ read and set it: `lm._graphs`, `lm.graph_captures`,
 `lm.use_graphs`, `lm.max_graphs`, `lm.graph_mode`, `lm.graph_pool`, `lm.tp_world`, `lm.ranks` (utils/rank_group.py)."""
@@ -60,30 +61,70 @@ def _collective_capture_works(lm) -> bool:
     return lm.ranks.all_true(ok)
 
 
+class _SpecOut:
+    """What a greedy step of a speculating model sends to the host, in ONE device buffer and one copy to its pinned mirror:
+    the emitted ids int64 [B, K + 1] and their logprobs f32 [B, K + 1] (tgis_spec_accept), how many of them count, n_emit
+    int32 [B], and the hits int32 [B] of the lookup that drafted the next step (tgis_spec_propose)."""
+
+    def __init__(self, B: int, K: int, dev):
+        R = B * (K + 1)
+        self.K1 = K + 1
+        self.buf = torch.zeros(R * 12 + B * 8, dtype=torch.uint8, device=dev)
+        self.host = torch.zeros(R * 12 + B * 8, dtype=torch.uint8).pin_memory()
+        self.ids, self.lps, self.n_emit, self.hits = self._views(self.buf, B, R)
+        self.ready = torch.cuda.Event()
+
+    @staticmethod
+    def _views(buf, B, R):
+        return (buf[:R * 8].view(torch.int64), buf[R * 8:R * 12].view(torch.float32),
+                buf[R * 12:R * 12 + B * 4].view(torch.int32), buf[R * 12 + B * 4:].view(torch.int32))
+
+    def fetch(self):
+        self.host.copy_(self.buf, non_blocking=True)
+        self.ready.record()
+
+    def read(self, n: int, want_logprobs: bool):
+        """(ids [n * (K + 1)], logprobs or None, n_emit [n], hits [n]) of the first n requests, as host lists."""
+        self.ready.synchronize()
+        B = self.n_emit.numel()
+        ids, lps, n_emit, hits = self._views(self.host, B, B * self.K1)
+        return (ids[:n * self.K1].tolist(), lps[:n * self.K1].tolist() if want_logprobs else None, n_emit[:n].tolist(),
+                hits[:n].tolist())
+
+
 class _DecodeGraph:
     """Static buffers + captured HIP graph of one decode step for a (batch-size bucket, table width) pair."""
 
+    K = 0  # drafts per request: none in the plain step
+
     def __init__(self, lm, B: int, width: int):
+        self._init_buffers(lm, B, width, B)
+        dev = lm.device
+        self.ctx = torch.ones(B, dtype=torch.int32, device=dev)
+        self.cu_q = torch.arange(B + 1, dtype=torch.int32, device=dev)
+        self.num_splits = native.attn_num_splits(B, lm.num_kv_heads, lm.num_heads, 1, self.max_ctx)
+        # a speculating model's plain steps report through tgis_spec_accept (K = 0) too: the next lookup's hits ride along
+        self.spec_out = _SpecOut(B, 0, dev) if getattr(lm, "spec_tokens", 0) else None
+
+    def _init_buffers(self, lm, B: int, width: int, R: int):
+        """What the plain and the verify step share: the per-request inputs, and R rows of slots and greedy outputs."""
         dev = lm.device
         self.rows = B
         self.active = 0  # rows [0, active) hold a batch's sequences, the rest are inactive
         self.input_ids = torch.zeros(B, dtype=torch.int64, device=dev)
         self.positions = torch.zeros(B, dtype=torch.int32, device=dev)
         self.block_tables = torch.full((B, width), lm.kv_cache.null_page, dtype=torch.int32, device=dev)
-        self.slots = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.ctx = torch.ones(B, dtype=torch.int32, device=dev)
-        self.cu_q = torch.arange(B + 1, dtype=torch.int32, device=dev)
+        self.slots = torch.zeros(R, dtype=torch.int32, device=dev)
         self.max_ctx = width * PAGE
-        self.num_splits = native.attn_num_splits(B, lm.num_kv_heads, lm.num_heads, 1, self.max_ctx)
         self.lm = lm
         self.graph = None
         self.logits = self.ids = self.logprobs = None
         # greedy ids (int64) and their logprobs (f32) in ONE device buffer: one copy to the (pinned) host mirror per step
-        self.out_buf = torch.zeros(B * 12, dtype=torch.uint8, device=dev)
-        self.ids_buf = self.out_buf[:B * 8].view(torch.int64)
-        self.lps_buf = self.out_buf[B * 8:].view(torch.float32)
-        self.argmax_scratch = native.argmax_scratch(B, dev)
-        self.host_buf = torch.zeros(B * 12, dtype=torch.uint8).pin_memory()
+        self.out_buf = torch.zeros(R * 12, dtype=torch.uint8, device=dev)
+        self.ids_buf = self.out_buf[:R * 8].view(torch.int64)
+        self.lps_buf = self.out_buf[R * 8:].view(torch.float32)
+        self.argmax_scratch = native.argmax_scratch(R, dev)
+        self.host_buf = torch.zeros(R * 12, dtype=torch.uint8).pin_memory()
         self.host_ready = torch.cuda.Event()
         # whose next-step inputs the static buffers already hold (tgis_decode_advance wrote them): identity of the
         # batch's tensors, so that a pruned / concatenated / other batch always stages its own
@@ -112,6 +153,12 @@ class _DecodeGraph:
 
     def run(self, input_ids, position_ids, block_tables):
         """One decode step of a batch of n <= rows sequences; returns (logits, ids, logprobs) of its n rows."""
+        n = self._stage(input_ids, position_ids, block_tables)
+        logits, ids, lps = self._run()
+        return (logits, ids, lps) if n == self.rows else (logits[:n], ids[:n], lps[:n])
+
+    def _stage(self, input_ids, position_ids, block_tables) -> int:
+        """The batch's inputs into the static buffers (those the launch after the last step left there are skipped)."""
         n = input_ids.numel()
         if n < self.active:  # rows a larger batch used before: inactive again
             self.positions[n:self.active].zero_()
@@ -125,8 +172,7 @@ class _DecodeGraph:
             self.block_tables[:n].copy_(block_tables, non_blocking=True)
             self.staged_bt = block_tables
         self.staged_ids = self.staged_pos = None
-        logits, ids, lps = self._run()
-        return (logits, ids, lps) if n == self.rows else (logits[:n], ids[:n], lps[:n])
+        return n
 
     def _run(self):
         if not self.lm.use_graphs:
@@ -168,7 +214,49 @@ class _DecodeGraph:
                     self.lm.use_graphs = False
                     return self._step()
             self.graph = g
-            # (rows, table width, host ms of warm-up step + capture): what a new (bucket, width) pair costs a serving step
-            self.lm.graph_captures.append((self.rows, self.block_tables.shape[1], (time.perf_counter() - t_capture) * 1e3))
+            # (rows, table width, host ms of warm-up step + capture, K): what a new (bucket, width[, K]) key costs a serving step
+            self.lm.graph_captures.append((self.rows, self.block_tables.shape[1], (time.perf_counter() - t_capture) * 1e3,
+                                           self.K))
         self.graph.replay()
         return self.logits, self.ids, self.logprobs
+
+
+class _VerifyGraph(_DecodeGraph):
+    """The verify step of speculative decoding for a (batch-size bucket, table width, K) triple: K + 1 rows per request, its
+    latest token and its K drafts, through the generic q_len > 1 forward (rotary and cache write per token, the attention's
+    decode form with one key split), then the greedy choice behind every row.  `input_ids` / `positions` stay the
+    per-request inputs, as in the plain step, so that the launch after either step can leave the next inputs in them."""
+
+    def __init__(self, lm, B: int, width: int, K: int):
+        R = B * (K + 1)
+        self._init_buffers(lm, B, width, R)
+        dev = lm.device
+        self.K = K
+        self.drafts = torch.zeros((B, K), dtype=torch.int64, device=dev)
+        self.row_ids = torch.zeros(R, dtype=torch.int64, device=dev)
+        self.row_positions = torch.zeros(R, dtype=torch.int32, device=dev)
+        self.ctx = torch.full((B,), K + 1, dtype=torch.int32, device=dev)
+        self.cu_q = torch.arange(B + 1, dtype=torch.int32, device=dev) * (K + 1)
+        self.num_splits = 1  # the attention's q_len > 1 forms take no key splits
+        self.spec_out = _SpecOut(B, K, dev)
+
+    def _step(self):
+        lm = self.lm
+        native.spec_stage(self.positions, self.input_ids, self.drafts, self.block_tables, self.row_ids, self.row_positions,
+                          self.slots, self.ctx)
+        kv = KVArgs(cache=lm.kv_cache, block_tables=self.block_tables, ctx_lens=self.ctx, slots=self.slots,
+                    max_q_len=self.K + 1, max_ctx=self.max_ctx, num_splits=1)
+        logits = lm.model.forward(self.row_ids, self.row_positions, self.cu_q, self.max_ctx, None, kv)
+        ids, lps = native.argmax_logprob(logits, ids_out=self.ids_buf, logprob_out=self.lps_buf, scratch=self.argmax_scratch)
+        return logits, ids, lps
+
+    def run(self, input_ids, position_ids, block_tables, drafts):
+        """One verify step of a batch of n <= rows sequences; returns (logits, ids, logprobs) of its n (K + 1) rows."""
+        n = input_ids.numel()
+        if n < self.active:
+            self.drafts[n:self.active].zero_()
+        self.drafts[:n].copy_(drafts, non_blocking=True)
+        self._stage(input_ids, position_ids, block_tables)
+        logits, ids, lps = self._run()
+        r = n * (self.K + 1)
+        return logits[:r], ids[:r], lps[:r]

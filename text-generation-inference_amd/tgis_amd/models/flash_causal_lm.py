@@ -27,7 +27,7 @@ import torch
 
 from tgis_amd import native
 from tgis_amd.models.custom_modeling.flash_common import KVArgs
-from tgis_amd.models.decode_graph import _DecodeGraph, renew_unheld_pool
+from tgis_amd.models.decode_graph import _DecodeGraph, _VerifyGraph, renew_unheld_pool
 from tgis_amd.models.model import Model
 from tgis_amd.models.types import Batch, GenerateError
 from tgis_amd.pb import generate_pb2
@@ -35,6 +35,8 @@ from tgis_amd.utils.kv_cache import (KV_SCALES_HEADROOM, PAGE, OutOfPages, Paged
                                      agree_kv_prefix_reuse, agree_kv_scales, kv_pool_dtype, kv_scales_stats,
                                      pages_for_budget, parse_kv_cache_dtype, parse_kv_prefix_reuse)
 from tgis_amd.utils.rank_group import RankGroup
+from tgis_amd.utils.spec_decode import (check_spec_world, fallback_cause, may_ever_verify, new_stats, parse_spec_ngram,
+                                        parse_spec_tokens)
 from tgis_amd.utils.token_types import InputTokens, TokenInfo
 from tgis_amd.utils.tokens import HeterogeneousNextTokenChooser, get_input_tokens_info, get_token_info
 
@@ -74,6 +76,12 @@ class FlashCausalLMBatch(Batch):
     # only consumer; and, from `allocate_pages`, how many leading tokens of each request sit on pages it shares
     prompt_token_ids: Optional[List[List[int]]] = None
     reused_lengths: Optional[List[int]] = None
+    # speculative decoding (utils/spec_decode.py), set by the prefill of a model that has it on: K and N, and on the device
+    # the K tokens drafted for each request's next step [B, K] and the suffix length their lookup matched [B] (0 = none)
+    spec_tokens: int = 0
+    spec_ngram: int = 0
+    spec_drafts: Optional[torch.Tensor] = None
+    spec_hits: Optional[torch.Tensor] = None
 
     def get_id(self) -> int:
         return self.batch_id
@@ -128,21 +136,60 @@ class FlashCausalLMBatch(Batch):
         for pages, toks in zip(self.pages, ids):
             self.kv_cache.register(pages, toks)
 
-    def grow_pages(self):
-        """Before a decode step: every sequence owns the page its next token (position input_length - 1) lands on."""
-        short = [i for i, (p, n) in enumerate(zip(self.pages, self.input_lengths)) if len(p) * PAGE < n]
+    def grow_pages(self, ahead: int = 0):
+        """Before a decode step: every sequence owns the page its next token (position input_length - 1) lands on, and
+        those of the `ahead` positions behind it (a verify step writes its drafts' keys and values there)."""
+        short = [i for i, (p, n) in enumerate(zip(self.pages, self.input_lengths)) if len(p) * PAGE < n + ahead]
         if not short:
             return
-        flat = self.kv_cache.alloc(len(short))  # all or nothing: OutOfPages leaves the batch as it was
-        for i, pg in zip(short, flat):
-            self.pages[i].append(pg)
+        need = {i: PagedKVCache.pages_for(self.input_lengths[i] + ahead) - len(self.pages[i]) for i in short}
+        flat = iter(self.kv_cache.alloc(sum(need[i] for i in short)))  # all or nothing: OutOfPages leaves the batch as it was
+        for i in short:
+            self.pages[i].extend(next(flat) for _ in range(need[i]))
         width = self.block_tables.shape[1]
         if max(len(self.pages[i]) for i in short) > width or getattr(self, "_bt_host", None) is None:
             self._rebuild_block_tables()
         else:  # edit the host copy and upload the few KB again (the same copy the prefill made: nothing new to load)
             for i in short:
-                self._bt_host[i, len(self.pages[i]) - 1] = self.pages[i][-1]
+                have = len(self.pages[i])
+                self._bt_host[i, have - need[i]:have] = self.pages[i][-need[i]:]
             self.block_tables = torch.from_numpy(self._bt_host).to(self.block_tables.device, non_blocking=True)
+
+    # ---- speculative decoding ---------------------------------------------------------------------
+    def propose_drafts(self, hits_copy: Optional[torch.Tensor] = None):
+        """Drafts for the next step of every request, looked up in its own context (tgis_spec_propose): after the prefill,
+        after every greedy step, and after concatenate / prune rebuilt the tensors it reads.  A no-op with the option off."""
+        if not self.spec_tokens:
+            return
+        B = len(self)
+        if self.spec_drafts is None or self.spec_drafts.shape[0] != B:
+            dev = self.position_ids.device
+            self.spec_drafts = torch.zeros((B, self.spec_tokens), dtype=torch.int64, device=dev)
+            self.spec_hits = torch.zeros(B, dtype=torch.int32, device=dev)
+        native.spec_propose(self.all_input_ids_tensor, self.position_ids, self.spec_ngram, self.spec_drafts, self.spec_hits,
+                            hits_copy)
+        self._spec_seen = None
+        self._spec_stale = False
+
+    def drafts_are_stale(self):
+        """A step that could not lead to a verify step (sampling or details in the batch, a bucket too wide) skips the
+        lookup; the step rule drafts anew before it looks at the hits, should the batch ever get that far."""
+        self._spec_stale = True
+
+    def spec_hits_host(self) -> List[int]:
+        """`spec_hits` on the host.  A greedy step brings them along in its one copy (`note_spec_hits`); only a tensor the
+        batch has not seen yet is fetched: after a prefill, concatenate or prune, or one a caller put in its place (whoever
+        wants other drafts verified assigns new `spec_drafts` / `spec_hits` tensors rather than writing into these)."""
+        if getattr(self, "_spec_stale", False):
+            self.propose_drafts()
+        t = self.spec_hits
+        seen = getattr(self, "_spec_seen", None)
+        if seen is None or seen[0] is not t:
+            seen = self._spec_seen = (t, t.tolist())
+        return seen[1]
+
+    def note_spec_hits(self, hits: List[int]):
+        self._spec_seen = (self.spec_hits, hits)
 
     def _rebuild_block_tables(self):
         # as wide as the longest sequence can ever get (pages themselves are taken lazily): the decode graph of a batch
@@ -290,7 +337,7 @@ class FlashCausalLMBatch(Batch):
             max_seqlen=max_seqlen, past_key_values=None, input_lengths=input_lengths,
             total_lengths=total_lengths, all_input_ids_tensor=all_input_ids_tensor,
             next_token_chooser=next_token_chooser, pad_token_id=first.pad_token_id,
-            kv_cache=first.kv_cache, pages=None)
+            kv_cache=first.kv_cache, pages=None, spec_tokens=first.spec_tokens, spec_ngram=first.spec_ngram)
         merged.pages = pages
         try:
             merged._rebuild_block_tables()
@@ -300,6 +347,7 @@ class FlashCausalLMBatch(Batch):
         for batch in batches:
             batch.pages = None
             batch.block_tables = None
+        merged.propose_drafts()
         return merged
 
     @classmethod
@@ -336,6 +384,8 @@ class FlashCausalLMBatch(Batch):
             batch.cu_seqlens = torch.cumsum(cu, dim=0, dtype=torch.int32)
         batch.cu_seqlens_q = batch.cu_seqlens_q[:new_size + 1]
         batch._rebuild_block_tables()
+        batch.spec_drafts = batch.spec_hits = None
+        batch.propose_drafts()
         return batch
 
 
@@ -365,7 +415,8 @@ class FlashCausalLM(Model):
                  quantize: Optional[str], model_config: Union[Any] = None, auto_model_class=None,
                  max_sequence_length: Optional[int] = None, engine=None, kv_cache_pages: Optional[int] = None,
                  kv_cache_dtype: Optional[str] = None, kv_scales: Union[None, str, dict] = None,
-                 kv_prefix_reuse: Optional[bool] = None):
+                 kv_prefix_reuse: Optional[bool] = None, spec_tokens: Optional[int] = None,
+                 spec_ngram: Optional[int] = None):
         # KV cache element: "auto" (the model dtype) or "fp8_e4m3" (one byte, utils/kv_cache.py); None reads
         # TGIS_KV_CACHE_DTYPE.  Checked before anything is loaded — except on a rank of a tensor-parallel group, which loads
         # its shard and then tells its peers (agree_kv_cache_dtype below): they sit in a collective only it can release.
@@ -374,6 +425,12 @@ class FlashCausalLM(Model):
         if (getattr(engine, "world_size", 1) or 1) == 1:
             parse_kv_cache_dtype(kv_cache_dtype)
             parse_kv_prefix_reuse(kv_prefix_reuse)
+        # spec_tokens: K > 0 turns prompt-lookup speculative decoding on (utils/spec_decode.py): greedy batches verify K
+        # drafted tokens per request and step; None reads TGIS_SPEC_TOKENS (0 / unset = off, 1 .. 7).  spec_ngram: the
+        # longest suffix looked up (TGIS_SPEC_NGRAM, default 3, 1 .. 4).  Not under tensor parallelism.
+        self.spec_tokens = parse_spec_tokens(spec_tokens)
+        self.spec_ngram = parse_spec_ngram(spec_ngram)
+        check_spec_world(self.spec_tokens, getattr(engine, "world_size", 1) or 1)
         # kv_scales: the calibrated per-layer scales of a one-byte cache, the contents of a kv_cache_scales.json or its path
         # (utils/kv_cache.py, resolve_kv_scales); None looks at TGIS_KV_SCALES, then next to the weights, else they stay 1.0
         if not torch.cuda.is_available():
@@ -409,6 +466,8 @@ class FlashCausalLM(Model):
         # what tensor-parallel ranks must agree on, in this order on every rank: cache dtype, prefix reuse, pages, scales,
         # graph mode, seed
         self.ranks = RankGroup(engine, self.device)
+        check_spec_world(self.spec_tokens, self.ranks.world)
+        self._spec_stats = new_stats()
         self.kv_cache_dtype = agree_kv_cache_dtype(self.ranks, kv_cache_dtype)
         self.kv_prefix_reuse = agree_kv_prefix_reuse(self.ranks, kv_prefix_reuse)
         if kv_cache_pages is None:
@@ -452,7 +511,7 @@ class FlashCausalLM(Model):
         # captured decode steps, least recently used first; they share one memory pool (a step's intermediates are dead
         # once it has run, and its outputs are consumed before the next replay), and the number kept is bounded
         self._graphs = OrderedDict()
-        self.graph_captures = deque(maxlen=4096)  # (rows, pages per row, capture ms) of the latest captures
+        self.graph_captures = deque(maxlen=4096)  # (rows, pages per row, capture ms, K: 0 = plain step) of the latest captures
         self.max_graphs = int(os.getenv("TGIS_MAX_DECODE_GRAPHS", "48"))
         self.graph_pool = torch.cuda.graph_pool_handle() if self.use_graphs else None
 
@@ -491,6 +550,12 @@ class FlashCausalLM(Model):
         return kv_scales_stats([a[0] for a in absmax], [a[1] for a in absmax], tokens, str(self.dtype).replace("torch.", ""),
                                headroom)
 
+    def spec_stats(self) -> dict:
+        """Counters of speculative decoding since construction (all zero with the option off): decode steps, those that
+        verified drafts, the plain steps of a speculating model by cause (utils/spec_decode.py FALLBACK_CAUSES), tokens
+        drafted, drafts accepted, tokens emitted by decode steps."""
+        return dict(self._spec_stats)
+
     def _default_kv_pages(self) -> int:
         free, _total = torch.cuda.mem_get_info(self.device)
         frac = float(os.getenv("TGIS_KV_CACHE_FRACTION", "0.85"))
@@ -505,6 +570,9 @@ class FlashCausalLM(Model):
     def generate_token(self, batch: FlashCausalLMBatch, first: bool = False, for_concat: bool = False,
                        ) -> Tuple[List[TokenInfo], Optional[List[InputTokens]], List[GenerateError], int]:
         start_time = time.time_ns()
+        spec_before = None
+        if self.spec_tokens and not first and logging.getLogger().isEnabledFor(logging.DEBUG):
+            spec_before = self.spec_stats()
         if first:
             out, fused = self._prefill_forward(batch), None
         else:
@@ -522,6 +590,15 @@ class FlashCausalLM(Model):
         if first:
             batch.cu_seqlens.add_(batch.cu_seqlens_q)
         batch.max_seqlen += 1
+        if self.spec_tokens:
+            batch.max_seqlen = max(batch.input_lengths)  # a verify step adds up to K + 1 tokens to a request
+            if first:
+                batch.spec_tokens, batch.spec_ngram = self.spec_tokens, self.spec_ngram
+                batch.propose_drafts()
+            if spec_before is not None:
+                after = self.spec_stats()
+                logging.debug("speculative decoding, batch %s: %s", batch.batch_id,
+                              {k: after[k] - spec_before[k] for k in after})
         return generated_tokens, input_token_infos, decode_errors, forward_time_ns
 
     def _prefill_forward(self, batch: FlashCausalLMBatch):
@@ -580,18 +657,47 @@ class FlashCausalLM(Model):
                                   batch.max_seqlen, batch.inputs_embeds, kv, lm_head_indices)
 
     def _decode_forward(self, batch: FlashCausalLMBatch):
-        batch.grow_pages()
+        verify = self.spec_tokens > 0 and self._grow_for_verify(batch)
+        if not verify:
+            batch.grow_pages()
         key = (graph_bucket(len(batch)), batch.block_tables.shape[1])
+        if verify:
+            key += (self.spec_tokens,)
         g = self._graphs.get(key)
         if g is None:
             while len(self._graphs) >= self.max_graphs:
                 self._graphs.popitem(last=False)
             renew_unheld_pool(self)
-            g = self._graphs[key] = _DecodeGraph(self, *key)
+            g = self._graphs[key] = (_VerifyGraph if verify else _DecodeGraph)(self, *key)
         else:
             self._graphs.move_to_end(key)
-        logits, ids, lps = g.run(batch.input_ids, batch.position_ids, batch.block_tables)
+        if verify:
+            logits, ids, lps = g.run(batch.input_ids, batch.position_ids, batch.block_tables, batch.spec_drafts)
+        else:
+            logits, ids, lps = g.run(batch.input_ids, batch.position_ids, batch.block_tables)
         return logits, (ids, lps, g)
+
+    def _grow_for_verify(self, batch: FlashCausalLMBatch) -> bool:
+        """Whether this decode step verifies the batch's drafts (utils/spec_decode.py, fallback_cause); if so its requests
+        own the pages of K + 1 more tokens afterwards.  A pool that cannot provide them is one more cause to run the plain
+        step, which grows by one token as it always did: speculation never exhausts the pool by itself."""
+        K, st = self.spec_tokens, self._spec_stats
+        st["decode_steps"] += 1
+        ntc = batch.next_token_chooser
+        greedy = ntc.is_plain_greedy and batch.spec_hits is not None
+        cause = fallback_cause(
+            K, graph_bucket(len(batch)), greedy, any(r.details.top_n_toks or r.details.ranks for r in batch.requests),
+            [t - n for t, n in zip(batch.total_lengths, batch.input_lengths)], batch.spec_hits_host)
+        if cause is None:
+            try:
+                batch.grow_pages(ahead=K)
+            except OutOfPages:
+                cause = "pages"
+        if cause is not None:
+            st["fallback_" + cause] += 1
+            return False
+        st["verify_steps"] += 1
+        return True
 
     def _process_prefill(self, batch: FlashCausalLMBatch, out):
         generated_tokens: List[TokenInfo] = []
@@ -623,6 +729,10 @@ class FlashCausalLM(Model):
         ntc = batch.next_token_chooser
         simple = ntc.is_plain_greedy and not any(r.details.top_n_toks or r.details.ranks for r in batch.requests)
         graph = fused[2] if fused is not None else None
+        if self.spec_tokens and not prefill:
+            self._spec_stats["emitted"] += len(batch)  # (a verify step adds the drafts it accepted)
+            if simple and graph is not None and batch.spec_hits is not None:
+                return self._process_spec_tokens(batch, fused, generated_tokens, decode_errors)
         read_host = None
         if simple:
             # one kernel (already part of the decode graph), one device->host copy for the whole batch
@@ -647,6 +757,8 @@ class FlashCausalLM(Model):
                 stage_positions=graph.positions[:len(batch)] if graph is not None else None)
             if graph is not None:
                 graph.staged_ids, graph.staged_pos = next_token_ids, batch.position_ids
+            if self.spec_tokens:  # (a batch below its min_new_tokens turns plain greedy without being rebuilt)
+                batch.drafts_are_stale()
 
         if read_host is not None:
             ids_host, lps_host = read_host(any(ntc.return_logprobs))
@@ -672,6 +784,43 @@ class FlashCausalLM(Model):
                 decode_errors.append(GenerateError(request_id=request.id,
                                                    message=f"Token decoding error: {str(e)}"))
             batch.input_lengths[i] += 1
+        return next_token_ids
+
+    def _process_spec_tokens(self, batch: FlashCausalLMBatch, fused, generated_tokens: List[TokenInfo],
+                             decode_errors: List[GenerateError]):
+        """What follows a greedy decode step of a speculating model, verify (K drafts per request) or plain (K = 0): one
+        launch accepts and does the bookkeeping of `_process_new_tokens` for up to K + 1 tokens per request
+        (tgis_spec_accept), one drafts the next step (tgis_spec_propose), one copy brings ids, logprobs, counts and the
+        lookup's hits to the host.  Request i contributes n_emit[i] TokenInfos, in order."""
+        ids, lps, graph = fused
+        B, K, K1, out = len(batch), graph.K, graph.K + 1, graph.spec_out
+        next_token_ids = native.spec_accept(
+            ids, lps, batch.spec_drafts if K else None, out.n_emit[:B], batch.position_ids, out_ids=out.ids[:B * K1],
+            out_logprobs=out.lps[:B * K1], all_input_ids=batch.all_input_ids_tensor, cu_seqlens=batch.cu_seqlens,
+            stage_ids=graph.input_ids[:B], stage_positions=graph.positions[:B])
+        graph.staged_ids, graph.staged_pos = next_token_ids, batch.position_ids
+        drafting = may_ever_verify(self.spec_tokens, graph_bucket(B))
+        if drafting:
+            batch.propose_drafts(hits_copy=out.hits[:B])
+        else:
+            batch.drafts_are_stale()
+        out.fetch()
+        want_lps = any(batch.next_token_chooser.return_logprobs)
+        ids_host, lps_host, n_emit, hits = out.read(B, want_lps)
+        if drafting:
+            batch.note_spec_hits(hits)
+        for i, request in enumerate(batch.requests):
+            for j in range(i * K1, i * K1 + n_emit[i]):
+                info = TokenInfo(request_id=request.id, token_id=ids_host[j])
+                if lps_host is not None and request.details.logprobs:
+                    info.logprob = lps_host[j]
+                generated_tokens.append(info)
+            batch.input_lengths[i] += n_emit[i]
+        if K:
+            st = self._spec_stats
+            st["drafted"] += K * B  # every request's K draft rows are verified, the zero drafts of a lookup that missed too
+            st["accepted"] += sum(n_emit) - B
+            st["emitted"] += sum(n_emit) - B
         return next_token_ids
 
     @staticmethod

@@ -110,6 +110,9 @@ SIGNATURES = {
     "tgis_embedding": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp]),
     "tgis_decode_slots": (_c_int, [_vp, _vp, _c_i64, _vp, _vp, _c_i64, _vp]),
     "tgis_decode_advance": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp]),
+    "tgis_spec_stage": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp]),
+    "tgis_spec_accept": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp]),
+    "tgis_spec_propose": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _c_i64, _vp]),
     "tgis_argmax_logprob": (_c_int, [_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _c_i64, _vp]),
     "tgis_argmax_scratch_bytes": (_c_i64, [_c_i64]),
     "tgis_warp_sample": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64,
@@ -902,6 +905,68 @@ def decode_advance(ids, position_ids, all_input_ids=None, cu_seqlens=None, cu_se
                                            _ptr(cu_seqlens), _ptr(cu_seqlens_q), _ptr(stage_ids), _ptr(stage_positions),
                                            B, _stream()), "tgis_decode_advance")
     return out
+
+
+def _is(t, dtype, numel):
+    return t.dtype == dtype and t.numel() == numel and t.is_contiguous()
+
+
+def spec_stage(positions, latest_ids, drafts, block_tables, input_ids, positions_out, slots, ctx_lens):
+    """The inputs of a verify forward (tgis_spec_stage): K + 1 rows per request, its latest token and its K drafts at the
+    positions behind it, their cache slots from the block table, ctx_lens = position + K + 1."""
+    B = positions.numel()
+    K = drafts.shape[1] if drafts is not None else 0
+    R = B * (K + 1)
+    assert _is(positions, torch.int32, B) and _is(latest_ids, torch.int64, B) and _is(ctx_lens, torch.int32, B)
+    assert drafts is None or (drafts.shape == (B, K) and _is(drafts, torch.int64, B * K))
+    assert block_tables.dtype == torch.int32 and block_tables.shape[0] == B and block_tables.is_contiguous()
+    assert _is(input_ids, torch.int64, R) and _is(positions_out, torch.int32, R) and _is(slots, torch.int32, R)
+    _check(
+        load_library().tgis_spec_stage(_ptr(positions), _ptr(latest_ids), _ptr(drafts), K, _ptr(block_tables),
+                                       block_tables.shape[1], _ptr(input_ids), _ptr(positions_out), _ptr(slots),
+                                       _ptr(ctx_lens), B, _stream()), "tgis_spec_stage")
+
+
+def spec_accept(argmax_ids, argmax_logprobs, drafts, n_emit, position_ids, out_ids=None, out_logprobs=None,
+                all_input_ids=None, cu_seqlens=None, stage_ids=None, stage_positions=None):
+    """After a verify step (tgis_spec_accept): request b emits the greedy ids behind its longest accepted draft prefix and
+    the one that follows it; n_emit, the emitted ids / logprobs, position_ids += n_emit, the scatter into all_input_ids and
+    the prefix sums onto cu_seqlens in one launch.  Returns the new latest ids.  drafts None (K = 0): decode_advance."""
+    B = position_ids.numel()
+    K = drafts.shape[1] if drafts is not None else 0
+    R = B * (K + 1)
+    assert _is(argmax_ids, torch.int64, R) and _is(position_ids, torch.int64, B) and _is(n_emit, torch.int32, B)
+    assert drafts is None or (drafts.shape == (B, K) and _is(drafts, torch.int64, B * K))
+    assert argmax_logprobs is None or _is(argmax_logprobs, torch.float32, R)
+    assert out_ids is None or _is(out_ids, torch.int64, R)
+    assert out_logprobs is None or (_is(out_logprobs, torch.float32, R) and argmax_logprobs is not None)
+    ld = 0
+    if all_input_ids is not None:
+        assert all_input_ids.dtype == torch.int64 and all_input_ids.stride(1) == 1 and all_input_ids.shape[0] >= B
+        ld = all_input_ids.stride(0)
+    assert cu_seqlens is None or _is(cu_seqlens, torch.int32, B + 1)
+    assert stage_ids is None or _is(stage_ids, torch.int64, B)
+    assert stage_positions is None or _is(stage_positions, torch.int32, B)
+    latest = torch.empty(B, dtype=torch.int64, device=position_ids.device)
+    _check(
+        load_library().tgis_spec_accept(_ptr(argmax_ids), _ptr(argmax_logprobs), _ptr(drafts), K, _ptr(n_emit),
+                                        _ptr(out_ids), _ptr(out_logprobs), _ptr(latest), _ptr(position_ids),
+                                        _ptr(all_input_ids), ld, _ptr(cu_seqlens), _ptr(stage_ids), _ptr(stage_positions),
+                                        B, _stream()), "tgis_spec_accept")
+    return latest
+
+
+def spec_propose(all_input_ids, position_ids, ngram: int, drafts, hits, hits_copy=None):
+    """Prompt lookup (tgis_spec_propose): drafts [B, K] = the tokens that followed the latest earlier occurrence of the
+    longest suffix (<= ngram tokens) of each request's context all_input_ids[b, :position_ids[b] + 1]; hits [B] = the
+    length that matched, 0 = none."""
+    B, K = drafts.shape
+    assert all_input_ids.dtype == torch.int64 and all_input_ids.stride(1) == 1 and all_input_ids.shape[0] >= B
+    assert _is(position_ids, torch.int64, B) and _is(drafts, torch.int64, B * K) and _is(hits, torch.int32, B)
+    assert hits_copy is None or _is(hits_copy, torch.int32, B)
+    _check(
+        load_library().tgis_spec_propose(_ptr(all_input_ids), all_input_ids.stride(0), _ptr(position_ids), K, ngram,
+                                         _ptr(drafts), _ptr(hits), _ptr(hits_copy), B, _stream()), "tgis_spec_propose")
 
 
 def argmax_scratch(B: int, device) -> torch.Tensor:

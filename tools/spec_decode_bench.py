@@ -1,0 +1,225 @@
+"""What a verify step of prompt-lookup speculative decoding (FlashCausalLM(spec_tokens=K)) costs next to the plain decode step,
+on the synthetic cfg3 engine built as bench.py builds it, context 1024.
+
+Per (B, K), in one process: the median ms of the captured plain step and of the captured verify step (HIP events around graph
+replays); their ratio is the break-even number of tokens a verify step must emit.  Then two runs through generate_token, host
+clock with a device sync on both sides, in tokens/s: one whose drafts are forced to the model's own continuation (every
+draft accepted wherever the two launch forms agree on the token; the count is reported) and one whose drafts are garbage (none
+accepted: the cost of speculating in vain).  The plain run of the same requests is the third figure.  An untimed pass of a few
+steps in front of every timed run pays the captures of the graphs it uses; forced drafts are gathered on the device and the
+hits are told to the batch (note_spec_hits), so no timed step reads the device beyond its one copy of the results.
+
+Random weights at this size decide many tokens by less than fp16 rounding, and a verify forward of B (K + 1) rows takes other
+GEMM plans than a plain step of B rows: a forced run may leave the plain run's id stream.  For every request that does, the
+tool records the first such token, the plain step's own top-2 logit margin there and max |the verify row's logits - the plain
+step's|, and the largest such distance over all tokens on which the streams agree, so that a near-tie is shown, not supposed.
+
+SYNTHETIC WEIGHTS SAY NOTHING ABOUT REAL ACCEPTANCE RATES: the forced runs bracket what the mechanism costs and can give; how
+often a lookup's drafts are right depends on the model and the prompts, and is not measured here.
+
+    python tools/spec_decode_bench.py [--config llama2-7b-gptq] [--tokens 32] > profiles/spec_decode_bench.json"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "text-generation-inference_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+from tgis_amd.inference_engine.synthetic import InferenceEngine, llama_tensors  # noqa: E402
+from tgis_amd.models.custom_modeling.flash_llama_modeling import LlamaConfig  # noqa: E402
+from tgis_amd.models.flash_causal_lm import FlashCausalLM, graph_bucket  # noqa: E402
+from tgis_amd.pb import generate_pb2  # noqa: E402
+from tgis_amd.utils.kv_cache import PagedKVCache  # noqa: E402
+from tgis_amd.utils.spec_decode import MAX_VERIFY_ROWS  # noqa: E402
+
+CTX, BS, KS = 1024, [1, 4, 8, 16], [3, 7]
+
+
+class IdTokenizer:
+    """'t17 t203' -> [17, 203]."""
+
+    def __init__(self, vocab_size):
+        self.vocab_size, self.pad_token_id, self.bos_token_id, self.eos_token_id = vocab_size, 0, 1, 2
+        self.add_bos_token = False
+
+    def __call__(self, texts, truncation=True, max_length=None, return_token_type_ids=False, **kw):
+        return {"input_ids": [[int(w[1:]) for w in t.split()] for t in texts]}
+
+
+def prefill(lm, tok, prompts, max_new):
+    reqs = [generate_pb2.Request(id=i, inputs=" ".join(f"t{t}" for t in p), input_length=len(p), truncate=False,
+                                 max_output_length=max_new) for i, p in enumerate(prompts)]
+    batch, errs = lm.batch_type.from_pb(generate_pb2.Batch(id=0, requests=reqs), tok, lm.dtype, lm.device, lm.word_embeddings,
+                                        None, True)
+    assert not errs
+    toks = lm.generate_token(batch, first=True)[0]
+    return batch, {t.request_id: [t.token_id] for t in toks}
+
+
+class Tap:
+    """Keeps the fp32 logits of the latest generate_token call (what the model hands to the chooser)."""
+
+    def __init__(self, lm):
+        self.rows = None
+        orig = lm._process_new_tokens
+
+        def tapped(batch, out, *a, **kw):
+            self.rows = out
+            return orig(batch, out, *a, **kw)
+
+        lm._process_new_tokens = tapped
+
+
+def decode(lm, batch, streams, tokens, force=None, tap=None, keep=None, against=None):
+    """Decode steps until every request has `tokens` tokens; `force(batch, streams)` sets the drafts before each step.
+    keep: a list that receives every step's logits (the plain run; one row per request and token).  against = (plain
+    streams, plain logits): every emitted token is held against the plain run until its request's stream parts from it.
+    Returns (seconds, steps, tokens emitted, partings) — one record per request that parted: the token index, the plain
+    run's top-2 logit margin there, and max |this run's logits row - the plain run's| for that token."""
+    torch.cuda.synchronize()
+    t0, steps, emitted, trace = time.perf_counter(), 0, 0, []
+    while min(len(s) for s in streams.values()) < tokens:
+        if force is not None:
+            force(batch, streams)
+        before = {r.id: len(streams[r.id]) for r in batch.requests}
+        toks = lm.generate_token(batch)[0]
+        if keep is not None:
+            keep.append(tap.rows.clone())
+        for t in toks:
+            streams[t.request_id].append(t.token_id)
+            emitted += 1
+        if against is not None:  # (a device copy; it is looked at after the clock has stopped)
+            trace.append((tap.rows.clone(), before, {rid: len(streams[rid]) for rid in before}, list(before)))
+        steps += 1
+    torch.cuda.synchronize()
+    sec = time.perf_counter() - t0
+    parted, partings, worst = set(), [], 0.0
+    for rows, before, after, order in trace:
+        plain, plain_logits = against
+        per = rows.shape[0] // len(order)
+        for i, rid in enumerate(order):
+            for j in range(per):
+                t = before[rid] + j
+                if rid in parted or t >= after[rid] or t >= len(plain[rid]) or t - 1 >= len(plain_logits):
+                    break  # (rows behind a rejected draft say nothing)
+                ref = plain_logits[t - 1][rid]  # the plain step that chose token t (token 0 is the prefill's)
+                diff = float((rows[i * per + j] - ref).abs().max())
+                if streams[rid][t] != plain[rid][t]:
+                    top = ref.topk(2).values
+                    partings.append({"request": rid, "token": t, "plain_top2_margin": round(float(top[0] - top[1]), 4),
+                                     "max_abs_logit_diff": round(diff, 4)})
+                    parted.add(rid)
+                else:
+                    worst = max(worst, diff)
+    return sec, steps, emitted, partings, round(worst, 4)
+
+
+def replay_ms(g, n=30):
+    """Median ms of n replays of a captured step (its static inputs stay what the last step left: same shapes, same work)."""
+    assert g.graph is not None
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+    for _ in range(3):
+        g.graph.replay()
+    for a, b in ev:
+        a.record()
+        g.graph.replay()
+        b.record()
+    torch.cuda.synchronize()
+    return statistics.median(a.elapsed_time(b) for a, b in ev)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="llama2-7b-gptq", choices=sorted(bench.CONFIGS))
+    ap.add_argument("--tokens", type=int, default=32, help="tokens generated per request in the timed runs")
+    args = ap.parse_args()
+    kw, quantize, dtype_s, _, _ = bench.CONFIGS[args.config]
+    cfg, dtype, dev = LlamaConfig(**kw), getattr(torch, dtype_s), torch.device("cuda:0")
+    tensors = llama_tensors(cfg, quantize, seed=1234, device=dev, dtype=dtype)
+    tok = IdTokenizer(cfg.vocab_size)
+    eng = InferenceEngine(tensors, cfg, dtype, quantize, tokenizer=tok)
+    del tensors
+    T = args.tokens
+    max_new = T + 16  # every timed step keeps K + 1 tokens in hand
+    pages = max(BS) * PagedKVCache.pages_for(CTX + max_new) + 8
+    rng = np.random.default_rng(2025)
+    for K in KS:
+        lm = FlashCausalLM("synthetic", None, "synthetic", dtype, quantize, engine=eng, kv_cache_pages=pages, spec_tokens=K)
+        assert lm.use_graphs
+        tap = Tap(lm)
+        for B in BS:
+            res = {"config": args.config, "ctx": CTX, "B": B, "K": K, "tokens_per_request": T,
+                   "note": "synthetic weights: says nothing about real acceptance rates"}
+            if graph_bucket(B) * (K + 1) > MAX_VERIFY_ROWS:
+                res["skipped"] = f"graph_bucket(B) * (K + 1) = {graph_bucket(B) * (K + 1)} > {MAX_VERIFY_ROWS}: such a batch never verifies"
+                print(json.dumps(res), flush=True)
+                continue
+            prompts = [rng.integers(3, cfg.vocab_size, size=CTX).tolist() for _ in range(B)]
+
+            ones, zeros = [1] * B, [0] * B
+
+            def no_drafts(batch, streams):  # every step the plain one; the host learns the hits without a read
+                batch.spec_hits = torch.zeros_like(batch.spec_hits)
+                batch.note_spec_hits(zeros)
+
+            def garbage(batch, streams):
+                batch.spec_drafts = torch.full_like(batch.spec_drafts, 3)
+                batch.spec_hits = torch.ones_like(batch.spec_hits)
+                batch.note_spec_hits(ones)
+
+            def run(force, n, **kw):
+                """An untimed pass of a few steps in front (it pays the captures of the graphs the mode uses), then the
+                timed one."""
+                for timed in (False, True):
+                    batch, streams = prefill(lm, tok, prompts, max_new)
+                    before = lm.spec_stats()
+                    out = decode(lm, batch, streams, n if timed else 1 + 2 * (K + 1), force=force, tap=tap,
+                                 **(kw if timed else {}))
+                    width = batch.block_tables.shape[1]
+                    batch.release()
+                return out, streams, {k: v - before[k] for k, v in lm.spec_stats().items()}, width
+
+            with lm.context_manager():
+                # the plain run: the model's own continuation and its logits
+                plain_logits = []
+                (sec, steps, emitted, _, _), plain, _, width = run(no_drafts, T + K, keep=plain_logits)
+                res["plain_tokens_per_s"] = round(emitted / sec, 1)
+                key = (graph_bucket(B), width)
+                res["plain_step_ms"] = round(replay_ms(lm._graphs[key]), 4)
+                plain_dev = torch.tensor([plain[i] + [3] * K for i in range(B)], dtype=torch.int64, device=dev)
+                offs = torch.arange(K, device=dev)[None]
+
+                def truth(batch, streams):  # the plain run's next K tokens of every request, gathered on the device
+                    at = torch.tensor([len(streams[r.id]) for r in batch.requests], device=dev)[:, None] + offs
+                    batch.spec_drafts = plain_dev.gather(1, at.clamp_(max=plain_dev.shape[1] - 1))
+                    batch.spec_hits = torch.ones_like(batch.spec_hits)
+                    batch.note_spec_hits(ones)
+
+                for name, force in (("accept_all", truth), ("accept_none", garbage)):
+                    (sec, steps, emitted, partings, worst), streams, d, _ = run(force, T, against=(plain, plain_logits))
+                    res[f"{name}_tokens_per_s"] = round(emitted / sec, 1)
+                    res[f"{name}_steps"] = steps
+                    res[f"{name}_tokens_per_step_and_request"] = round(emitted / max(1, steps) / B, 3)
+                    res[f"{name}_stats"] = {k: d[k] for k in ("verify_steps", "drafted", "accepted", "emitted")}
+                    res[f"{name}_ids_equal_plain"] = all(streams[i][:T] == plain[i][:T] for i in streams)
+                    # where a stream left the plain run's: how narrowly the plain run decided that token, and how far the
+                    # two launch forms' logits are apart there; and the largest such distance over the tokens that agreed
+                    res[f"{name}_partings"] = partings
+                    res[f"{name}_max_abs_logit_diff_where_equal"] = worst
+                res["verify_step_ms"] = round(replay_ms(lm._graphs[key + (K,)]), 4)
+            res["break_even_tokens_per_verify_step"] = round(res["verify_step_ms"] / res["plain_step_ms"], 3)
+            print(json.dumps(res), flush=True)
+        lm._graphs.clear()
+        del lm
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
