@@ -445,6 +445,30 @@ int tgis_spec_accept(const int64_t* argmax_ids, const float* argmax_logprobs, co
 int tgis_spec_propose(const int64_t* all_input_ids, int64_t ld_all, const int64_t* position_ids, int64_t K, int64_t N,
                       int64_t* drafts, int32_t* hits, int32_t* hits_copy, int64_t B, void* stream);
 
+/* ---- MLP speculator, the reference's drafter (models/paged_causal_lm.py:481-562, utils/paged.py:20-38,208) ------------
+ * Head i of K <= n_predict:  s = proj_i x + alpha emb_i[t];  x = gelu_erf(rmsln_i(s));  t = argmax(head_i x), starting from
+ * x = the post-final-norm hidden state behind a request's latest token t.  proj_i and head_i are tgis_dense_gemm on
+ * prepared images (head_i with out_f32 = 1), the argmax is tgis_argmax_logprob; these three entry points are the rest of
+ * the chain.  No allocation, no sync; B = 0 returns TGIS_OK. */
+/* The chain's input (paged_causal_lm.py:192,261 batch.embeds; :500-520 the rows kept behind a verify step).  hidden
+ * [B K1, E] model dtype, 1 <= K1 <= 8; request b takes row b K1 + clamp(n_emit[b], 1, K1) - 1 (n_emit int32 [B], NULL: row
+ * b K1).  out [B, E] and out_copy [B, E] (NULL: skip) receive the row, bit for bit, or with scale_input != 0 the row times
+ * rsqrt(mean(x^2) + eps) / sqrt(2) (fp32 statistics, one rounding).  E % 8 == 0. */
+int tgis_spec_mlp_input(const void* hidden, const int32_t* n_emit, int64_t K1, void* out, void* out_copy, int64_t B,
+                        int64_t E, int scale_input, float eps, int dtype, void* stream);
+/* Between the two GEMMs of a head (the speculator's emb + LayerNormParameterized + GELU).  proj_out [B, I] model dtype,
+ * tok int64 [B] (clamped to [0, V)), emb [V, I], ln_weight / ln_bias [I]:
+ *   s = proj_out[b] + alpha emb[tok[b]];  x_out[b] = gelu_erf(s rsqrt(mean(s^2) + eps) ln_weight + ln_bias)
+ * in fp32 with one rounding; no mean is subtracted.  One workgroup per row; I % 8 == 0, I <= 16384. */
+int tgis_spec_mlp_state(const void* proj_out, const int64_t* tok, const void* emb, int64_t V, const void* ln_weight,
+                        const void* ln_bias, float alpha, float eps, void* x_out, int64_t B, int64_t I, int dtype,
+                        void* stream);
+/* Behind the chain (utils/paged.py prepare_inputs_with_speculation takes the candidates request-major): toks [K, B] int64,
+ * row i written by the argmax of head i, into drafts [B, K] int64, 1 <= K <= 7; hits [B] int32 and hits_copy [B] (NULL:
+ * skip) are set to 1, the tgis_spec_propose convention for "this request has drafts". */
+int tgis_spec_mlp_drafts(const int64_t* toks, int64_t K, int64_t* drafts, int32_t* hits, int32_t* hits_copy, int64_t B,
+                         void* stream);
+
 /* ---- greedy sampling (Greedy + log_softmax + gather, utils/tokens.py:44-46,238-271,388-397) ------ */
 /* Per row: token = argmax (lowest id on ties), logprob = logit[token] - logsumexp(row).
  * logits [B,V] f32 (logits_f32 != 0) or model dtype. ids_out int64 [B], logprob_out f32 [B].

@@ -31,6 +31,7 @@ from tgis_amd.models.decode_graph import _DecodeGraph, _VerifyGraph, renew_unhel
 from tgis_amd.models.model import Model
 from tgis_amd.models.types import Batch, GenerateError
 from tgis_amd.pb import generate_pb2
+from tgis_amd.utils import mlp_speculator
 from tgis_amd.utils.kv_cache import (KV_SCALES_HEADROOM, PAGE, OutOfPages, PagedKVCache, agree_kv_cache_dtype,
                                      agree_kv_prefix_reuse, agree_kv_scales, kv_pool_dtype, kv_scales_stats,
                                      pages_for_budget, parse_kv_cache_dtype, parse_kv_prefix_reuse)
@@ -82,6 +83,10 @@ class FlashCausalLMBatch(Batch):
     spec_ngram: int = 0
     spec_drafts: Optional[torch.Tensor] = None
     spec_hits: Optional[torch.Tensor] = None
+    # an MLP drafter (utils/mlp_speculator.py) in place of the lookup: the speculator, and per request the post-norm hidden
+    # state that predicted its latest token [B, E] — the reference's `batch.embeds` (paged_causal_lm.py:192,261)
+    spec_model: Optional[Any] = None
+    spec_hidden: Optional[torch.Tensor] = None
 
     def get_id(self) -> int:
         return self.batch_id
@@ -157,17 +162,30 @@ class FlashCausalLMBatch(Batch):
 
     # ---- speculative decoding ---------------------------------------------------------------------
     def propose_drafts(self, hits_copy: Optional[torch.Tensor] = None):
-        """Drafts for the next step of every request, looked up in its own context (tgis_spec_propose): after the prefill,
-        after every greedy step, and after concatenate / prune rebuilt the tensors it reads.  A no-op with the option off."""
+        """Drafts for the next step of every request: after the prefill, after every greedy step, and after concatenate /
+        prune rebuilt the tensors the drafter reads.  Looked up in the request's own context (tgis_spec_propose), or, with
+        an MLP drafter, predicted from `spec_hidden` and the latest ids (`input_ids`).  A no-op with the option off."""
         if not self.spec_tokens:
             return
         B = len(self)
+        self.ensure_spec_buffers()
+        if self.spec_model is None:
+            native.spec_propose(self.all_input_ids_tensor, self.position_ids, self.spec_ngram, self.spec_drafts,
+                                self.spec_hits, hits_copy)
+        elif may_ever_verify(self.spec_tokens, graph_bucket(B)):  # (else the step rule answers `rows`: nobody reads drafts)
+            self.spec_model.draft(self.spec_hidden, self.input_ids, self.spec_drafts, self.spec_hits, hits_copy)
+        self.drafts_renewed()
+
+    def ensure_spec_buffers(self, emb_dim: int = 0, dtype=None):
+        """The batch's own `spec_drafts` / `spec_hits` for its present size (and `spec_hidden`, given its width)."""
+        B, dev = len(self), self.position_ids.device
         if self.spec_drafts is None or self.spec_drafts.shape[0] != B:
-            dev = self.position_ids.device
             self.spec_drafts = torch.zeros((B, self.spec_tokens), dtype=torch.int64, device=dev)
             self.spec_hits = torch.zeros(B, dtype=torch.int32, device=dev)
-        native.spec_propose(self.all_input_ids_tensor, self.position_ids, self.spec_ngram, self.spec_drafts, self.spec_hits,
-                            hits_copy)
+        if emb_dim and (self.spec_hidden is None or self.spec_hidden.shape[0] != B):
+            self.spec_hidden = torch.zeros((B, emb_dim), dtype=dtype, device=dev)
+
+    def drafts_renewed(self):
         self._spec_seen = None
         self._spec_stale = False
 
@@ -337,7 +355,9 @@ class FlashCausalLMBatch(Batch):
             max_seqlen=max_seqlen, past_key_values=None, input_lengths=input_lengths,
             total_lengths=total_lengths, all_input_ids_tensor=all_input_ids_tensor,
             next_token_chooser=next_token_chooser, pad_token_id=first.pad_token_id,
-            kv_cache=first.kv_cache, pages=None, spec_tokens=first.spec_tokens, spec_ngram=first.spec_ngram)
+            kv_cache=first.kv_cache, pages=None, spec_tokens=first.spec_tokens, spec_ngram=first.spec_ngram,
+            spec_model=first.spec_model,
+            spec_hidden=torch.cat([b.spec_hidden for b in batches]) if first.spec_model is not None else None)
         merged.pages = pages
         try:
             merged._rebuild_block_tables()
@@ -385,6 +405,8 @@ class FlashCausalLMBatch(Batch):
         batch.cu_seqlens_q = batch.cu_seqlens_q[:new_size + 1]
         batch._rebuild_block_tables()
         batch.spec_drafts = batch.spec_hits = None
+        if batch.spec_hidden is not None:
+            batch.spec_hidden = batch.spec_hidden[keep_indices]
         batch.propose_drafts()
         return batch
 
@@ -411,12 +433,16 @@ def graph_bucket(B: int) -> int:
 
 
 class FlashCausalLM(Model):
+    # the drafter of speculative decoding: the prompt lookup, or an MLP speculator on the device (set by the constructor)
+    spec_drafter = "lookup"
+    speculator = None
+
     def __init__(self, model_name: str, revision: Optional[str], deployment_framework: str, dtype: torch.dtype,
                  quantize: Optional[str], model_config: Union[Any] = None, auto_model_class=None,
                  max_sequence_length: Optional[int] = None, engine=None, kv_cache_pages: Optional[int] = None,
                  kv_cache_dtype: Optional[str] = None, kv_scales: Union[None, str, dict] = None,
                  kv_prefix_reuse: Optional[bool] = None, spec_tokens: Optional[int] = None,
-                 spec_ngram: Optional[int] = None):
+                 spec_ngram: Optional[int] = None, speculator: Union[None, str, Any] = None):
         # KV cache element: "auto" (the model dtype) or "fp8_e4m3" (one byte, utils/kv_cache.py); None reads
         # TGIS_KV_CACHE_DTYPE.  Checked before anything is loaded — except on a rank of a tensor-parallel group, which loads
         # its shard and then tells its peers (agree_kv_cache_dtype below): they sit in a collective only it can release.
@@ -431,6 +457,21 @@ class FlashCausalLM(Model):
         self.spec_tokens = parse_spec_tokens(spec_tokens)
         self.spec_ngram = parse_spec_ngram(spec_ngram)
         check_spec_world(self.spec_tokens, getattr(engine, "world_size", 1) or 1)
+        # speculator: the checkpoint directory of an MLP speculator (utils/mlp_speculator.py), the drafter in place of the
+        # lookup; None reads TGIS_SPECULATOR, unset = the lookup.  It needs spec_tokens in 1 .. min(n_predict, 7) and ignores
+        # spec_ngram.  Its config, tensor names and shapes are checked here, before any weight is on the device.
+        # (tools hand over a checkpoint they made in memory, a mlp_speculator.SpeculatorCheckpoint, in place of the directory)
+        spec_ckpt = speculator if isinstance(speculator, mlp_speculator.SpeculatorCheckpoint) else None
+        spec_path = mlp_speculator.parse_speculator(speculator) if spec_ckpt is None else None
+        if spec_path is not None:
+            spec_ckpt = mlp_speculator.open_checkpoint(spec_path)
+        if spec_ckpt is not None:
+            mlp_speculator.check_spec_tokens(spec_ckpt.cfg, self.spec_tokens)
+            base = getattr(engine, "_config", None)
+            if base is not None:  # (an engine built here is checked below, as soon as its config is read)
+                mlp_speculator.check_base(spec_ckpt.cfg, base.hidden_size, base.vocab_size)
+        self.spec_drafter = "lookup" if spec_ckpt is None else "mlp"
+        self.speculator = None
         # kv_scales: the calibrated per-layer scales of a one-byte cache, the contents of a kv_cache_scales.json or its path
         # (utils/kv_cache.py, resolve_kv_scales); None looks at TGIS_KV_SCALES, then next to the weights, else they stay 1.0
         if not torch.cuda.is_available():
@@ -468,6 +509,10 @@ class FlashCausalLM(Model):
         self.ranks = RankGroup(engine, self.device)
         check_spec_world(self.spec_tokens, self.ranks.world)
         self._spec_stats = new_stats()
+        if spec_ckpt is not None:
+            # before the pool is sized: the speculator's bytes come out of the page budget
+            mlp_speculator.check_base(spec_ckpt.cfg, self.config.hidden_size, self.config.vocab_size)
+            self.speculator = mlp_speculator.MLPSpeculator(spec_ckpt, self.spec_tokens, dtype, self.device)
         self.kv_cache_dtype = agree_kv_cache_dtype(self.ranks, kv_cache_dtype)
         self.kv_prefix_reuse = agree_kv_prefix_reuse(self.ranks, kv_prefix_reuse)
         if kv_cache_pages is None:
@@ -594,6 +639,8 @@ class FlashCausalLM(Model):
             batch.max_seqlen = max(batch.input_lengths)  # a verify step adds up to K + 1 tokens to a request
             if first:
                 batch.spec_tokens, batch.spec_ngram = self.spec_tokens, self.spec_ngram
+                if self.speculator is not None:
+                    batch.spec_model, batch.spec_hidden = self.speculator, self._prefill_hidden(batch)
                 batch.propose_drafts()
             if spec_before is not None:
                 after = self.spec_stats()
@@ -639,8 +686,25 @@ class FlashCausalLM(Model):
                     max_q_len=max_q, max_ctx=max_ctx,
                     num_splits=native.attn_num_splits(len(lens), self.num_kv_heads, self.num_heads, max_q, max_ctx),
                     past_lens=native.past_lens_tensor(hits, dev) if FRESH_PREFILL_KV else None)
-        return self.model.forward(batch.input_ids.index_select(0, up(take)), up(positions), cu_q, batch.max_seqlen, None,
-                                  kv, (cu_q[1:] - 1).long())
+        return self._forward_prefill(batch.input_ids.index_select(0, up(take)), up(positions), cu_q, batch.max_seqlen, None,
+                                     kv, (cu_q[1:] - 1).long())
+
+    def _forward_prefill(self, *args):
+        """The model's forward; with an MLP drafter it also keeps the rows that went into lm_head (`return_embeds`)."""
+        self._embeds = None
+        if self.speculator is None:
+            return self.model.forward(*args)
+        logits, self._embeds = self.model.forward(*args, return_embeds=True)
+        return logits
+
+    def _prefill_hidden(self, batch: FlashCausalLMBatch) -> torch.Tensor:
+        """[B, E]: the state behind each prompt's last token, the batch's own tensor (`batch.spec_hidden`)."""
+        embeds, self._embeds = self._embeds, None
+        if embeds.shape[0] != len(batch):  # details.input_toks: every prompt position went through lm_head
+            ends = np.cumsum([n - 1 for n in batch.input_lengths]) - 1  # (input_lengths count the generated token by now)
+            embeds = embeds.index_select(0, torch.from_numpy(ends).to(embeds.device))
+        out = torch.empty((len(batch), embeds.shape[1]), dtype=embeds.dtype, device=embeds.device)
+        return native.spec_mlp_input(embeds.contiguous(), None, 1, out)
 
     def _prefill_fresh_forward(self, batch: FlashCausalLMBatch):
         lens = batch.input_lengths
@@ -653,8 +717,8 @@ class FlashCausalLM(Model):
                     slots=torch.from_numpy(slots).to(dev, non_blocking=True),
                     max_q_len=max(lens), max_ctx=max(lens), num_splits=1, fresh_prefill=FRESH_PREFILL_KV)
         lm_head_indices = None if self._need_all_logits else (batch.cu_seqlens[1:] - 1).long()
-        return self.model.forward(batch.input_ids, batch.position_ids.to(torch.int32), batch.cu_seqlens,
-                                  batch.max_seqlen, batch.inputs_embeds, kv, lm_head_indices)
+        return self._forward_prefill(batch.input_ids, batch.position_ids.to(torch.int32), batch.cu_seqlens,
+                                     batch.max_seqlen, batch.inputs_embeds, kv, lm_head_indices)
 
     def _decode_forward(self, batch: FlashCausalLMBatch):
         verify = self.spec_tokens > 0 and self._grow_for_verify(batch)
@@ -758,6 +822,10 @@ class FlashCausalLM(Model):
             if graph is not None:
                 graph.staged_ids, graph.staged_pos = next_token_ids, batch.position_ids
             if self.spec_tokens:  # (a batch below its min_new_tokens turns plain greedy without being rebuilt)
+                if self.speculator is not None and graph is not None:
+                    # a step whose chooser samples (or reports details) still leaves the state behind its token
+                    batch.ensure_spec_buffers(graph.hidden.shape[1], graph.hidden.dtype)
+                    native.spec_mlp_input(graph.hidden, None, 1, batch.spec_hidden)
                 batch.drafts_are_stale()
 
         if read_host is not None:
@@ -800,7 +868,16 @@ class FlashCausalLM(Model):
             stage_ids=graph.input_ids[:B], stage_positions=graph.positions[:B])
         graph.staged_ids, graph.staged_pos = next_token_ids, batch.position_ids
         drafting = may_ever_verify(self.spec_tokens, graph_bucket(B))
-        if drafting:
+        if self.speculator is not None:
+            # the state behind each request's last emitted token and (a bucket that can verify) the next drafts; the chain
+            # reads the latest ids tgis_spec_accept just wrote
+            if drafting:
+                graph.draft_next(batch, next_token_ids)
+            else:
+                batch.ensure_spec_buffers(graph.hidden.shape[1], graph.hidden.dtype)
+                native.spec_mlp_input(graph.hidden, out.n_emit[:B], K1, batch.spec_hidden)
+                batch.drafts_are_stale()
+        elif drafting:
             batch.propose_drafts(hits_copy=out.hits[:B])
         else:
             batch.drafts_are_stale()

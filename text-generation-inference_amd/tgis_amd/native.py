@@ -113,6 +113,9 @@ SIGNATURES = {
     "tgis_spec_stage": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp]),
     "tgis_spec_accept": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp]),
     "tgis_spec_propose": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _c_i64, _vp]),
+    "tgis_spec_mlp_input": (_c_int, [_vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64, _c_int, _c_f, _c_int, _vp]),
+    "tgis_spec_mlp_state": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _c_f, _c_f, _vp, _c_i64, _c_i64, _c_int, _vp]),
+    "tgis_spec_mlp_drafts": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp]),
     "tgis_argmax_logprob": (_c_int, [_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _c_i64, _vp]),
     "tgis_argmax_scratch_bytes": (_c_i64, [_c_i64]),
     "tgis_warp_sample": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64,
@@ -967,6 +970,43 @@ def spec_propose(all_input_ids, position_ids, ngram: int, drafts, hits, hits_cop
     _check(
         load_library().tgis_spec_propose(_ptr(all_input_ids), all_input_ids.stride(0), _ptr(position_ids), K, ngram,
                                          _ptr(drafts), _ptr(hits), _ptr(hits_copy), B, _stream()), "tgis_spec_propose")
+
+
+def spec_mlp_input(hidden, n_emit, K1: int, out, out_copy=None, scale_input: bool = False, eps: float = 1e-6):
+    """The MLP speculator's input (tgis_spec_mlp_input): out[b] (and out_copy[b]) = row b K1 + clamp(n_emit[b], 1, K1) - 1 of
+    hidden [>= B K1, E] (n_emit None: row b K1), a bit-exact copy or, scale_input, its parameter-free RMS norm / sqrt(2)."""
+    B, E = out.shape
+    assert hidden.dim() == 2 and hidden.shape[1] == E and hidden.shape[0] >= B * K1 and hidden.is_contiguous()
+    assert out.dtype == hidden.dtype and out.is_contiguous()
+    assert n_emit is None or _is(n_emit, torch.int32, B)
+    assert out_copy is None or (out_copy.shape == (B, E) and out_copy.dtype == hidden.dtype and out_copy.is_contiguous())
+    _check(
+        load_library().tgis_spec_mlp_input(_ptr(hidden), _ptr(n_emit), K1, _ptr(out), _ptr(out_copy), B, E, int(scale_input),
+                                           float(eps), dtype_code(hidden.dtype), _stream()), "tgis_spec_mlp_input")
+    return out
+
+
+def spec_mlp_state(proj_out, tok, emb, ln_weight, ln_bias, alpha: float, x_out, eps: float = 1e-6):
+    """Between the GEMMs of a speculator head (tgis_spec_mlp_state): x_out[b] = gelu(rmsln(proj_out[b] + alpha emb[tok[b]]))."""
+    B, I = proj_out.shape
+    dt = proj_out.dtype
+    assert proj_out.is_contiguous() and _is(tok, torch.int64, B) and emb.dim() == 2 and emb.shape[1] == I
+    assert emb.is_contiguous() and emb.dtype == dt and _is(ln_weight, dt, I) and _is(ln_bias, dt, I)
+    assert x_out.shape == (B, I) and x_out.dtype == dt and x_out.is_contiguous()
+    _check(
+        load_library().tgis_spec_mlp_state(_ptr(proj_out), _ptr(tok), _ptr(emb), emb.shape[0], _ptr(ln_weight), _ptr(ln_bias),
+                                           float(alpha), float(eps), _ptr(x_out), B, I, dtype_code(dt), _stream()),
+        "tgis_spec_mlp_state")
+    return x_out
+
+
+def spec_mlp_drafts(toks, drafts, hits, hits_copy=None):
+    """Behind the speculator's chain (tgis_spec_mlp_drafts): toks [K, B] -> drafts [B, K]; hits (and hits_copy) = 1."""
+    B, K = drafts.shape
+    assert toks.shape == (K, B) and _is(toks, torch.int64, K * B) and _is(drafts, torch.int64, B * K)
+    assert _is(hits, torch.int32, B) and (hits_copy is None or _is(hits_copy, torch.int32, B))
+    _check(load_library().tgis_spec_mlp_drafts(_ptr(toks), K, _ptr(drafts), _ptr(hits), _ptr(hits_copy), B, _stream()),
+           "tgis_spec_mlp_drafts")
 
 
 def argmax_scratch(B: int, device) -> torch.Tensor:

@@ -17,7 +17,15 @@ step's|, and the largest such distance over all tokens on which the streams agre
 SYNTHETIC WEIGHTS SAY NOTHING ABOUT REAL ACCEPTANCE RATES: the forced runs bracket what the mechanism costs and can give; how
 often a lookup's drafts are right depends on the model and the prompts, and is not measured here.
 
-    python tools/spec_decode_bench.py [--config llama2-7b-gptq] [--tokens 32] > profiles/spec_decode_bench.json"""
+With --speculator E,I,P the drafter is a synthetic MLP speculator (utils/mlp_speculator.py; seeded random weights made in
+memory, E = the base model's hidden size) and K = min(P, 7).  Every greedy step of such a model is followed by the drafter's
+captured chain, so the figures are: `draft_chain_ms`, the chain alone (HIP events around replays of the chain behind the
+verify step; `draft_chain_after_plain_ms` the one behind the plain step); `break_even_tokens_per_verify_step` = (verify step
++ chain) / (plain step + chain); and the same three runs, whose `plain` one is the plain steps of the speculating model,
+chain included.  RANDOM SPECULATOR WEIGHTS DRAFT GARBAGE: acceptance on real text is not measured here.
+
+    python tools/spec_decode_bench.py [--config llama2-7b-gptq] [--tokens 32] > profiles/spec_decode_bench.json
+    python tools/spec_decode_bench.py --speculator 4096,4096,3 > profiles/spec_mlp_bench.json"""
 import argparse
 import json
 import os
@@ -36,6 +44,7 @@ from tgis_amd.inference_engine.synthetic import InferenceEngine, llama_tensors  
 from tgis_amd.models.custom_modeling.flash_llama_modeling import LlamaConfig  # noqa: E402
 from tgis_amd.models.flash_causal_lm import FlashCausalLM, graph_bucket  # noqa: E402
 from tgis_amd.pb import generate_pb2  # noqa: E402
+from tgis_amd.utils import mlp_speculator  # noqa: E402
 from tgis_amd.utils.kv_cache import PagedKVCache  # noqa: E402
 from tgis_amd.utils.spec_decode import MAX_VERIFY_ROWS  # noqa: E402
 
@@ -135,8 +144,29 @@ def replay_ms(g, n=30):
     return statistics.median(a.elapsed_time(b) for a, b in ev)
 
 
+def synthetic_speculator(E, I, P, V, dtype):
+    """A seeded random speculator as an in-memory checkpoint: unit-normal embeddings and heads, fan-in-scaled projections."""
+    cfg = mlp_speculator.SpeculatorConfig(E, I or E, V, P)
+    names = {mlp_speculator.TENSOR_NAMES[kind].format(i=i): (kind, i) for i in range(P) for kind in mlp_speculator.TENSOR_NAMES}
+
+    def load(name):
+        kind, i = names[name]
+        shape = cfg.shape_of(kind, i)
+        g = torch.Generator().manual_seed(1000 + 10 * i + sorted(mlp_speculator.TENSOR_NAMES).index(kind))
+        if kind == "ln_weight":
+            return torch.ones(shape, dtype=dtype)
+        if kind == "ln_bias":
+            return torch.zeros(shape, dtype=dtype)
+        t = torch.randn(shape, generator=g)
+        return (t / shape[1] ** 0.5 if kind == "proj" else t).to(dtype)
+
+    return mlp_speculator.SpeculatorCheckpoint(cfg, {n: cfg.shape_of(*ki) for n, ki in names.items()}, load)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--speculator", default=None, metavar="E,I,P",
+                    help="draft with a synthetic MLP speculator of these sizes (e.g. 4096,4096,3) instead of the lookup")
     ap.add_argument("--config", default="llama2-7b-gptq", choices=sorted(bench.CONFIGS))
     ap.add_argument("--tokens", type=int, default=32, help="tokens generated per request in the timed runs")
     args = ap.parse_args()
@@ -150,13 +180,22 @@ def main():
     max_new = T + 16  # every timed step keeps K + 1 tokens in hand
     pages = max(BS) * PagedKVCache.pages_for(CTX + max_new) + 8
     rng = np.random.default_rng(2025)
-    for K in KS:
-        lm = FlashCausalLM("synthetic", None, "synthetic", dtype, quantize, engine=eng, kv_cache_pages=pages, spec_tokens=K)
+    spec, ks = None, KS
+    if args.speculator:
+        E, I, P = (int(x) for x in args.speculator.split(","))
+        spec = synthetic_speculator(E, I, P, cfg.vocab_size, dtype)
+        ks = [min(P, 7)]
+    for K in ks:
+        lm = FlashCausalLM("synthetic", None, "synthetic", dtype, quantize, engine=eng, kv_cache_pages=pages, spec_tokens=K,
+                           speculator=spec)
         assert lm.use_graphs
         tap = Tap(lm)
         for B in BS:
             res = {"config": args.config, "ctx": CTX, "B": B, "K": K, "tokens_per_request": T,
                    "note": "synthetic weights: says nothing about real acceptance rates"}
+            if spec is not None:
+                res["drafter"] = f"mlp {args.speculator}"
+                res["speculator_bytes"] = lm.speculator.nbytes
             if graph_bucket(B) * (K + 1) > MAX_VERIFY_ROWS:
                 res["skipped"] = f"graph_bucket(B) * (K + 1) = {graph_bucket(B) * (K + 1)} > {MAX_VERIFY_ROWS}: such a batch never verifies"
                 print(json.dumps(res), flush=True)
@@ -214,7 +253,13 @@ def main():
                     res[f"{name}_partings"] = partings
                     res[f"{name}_max_abs_logit_diff_where_equal"] = worst
                 res["verify_step_ms"] = round(replay_ms(lm._graphs[key + (K,)]), 4)
-            res["break_even_tokens_per_verify_step"] = round(res["verify_step_ms"] / res["plain_step_ms"], 3)
+            if spec is None:
+                res["break_even_tokens_per_verify_step"] = round(res["verify_step_ms"] / res["plain_step_ms"], 3)
+            else:
+                res["draft_chain_ms"] = chain = round(replay_ms(lm._graphs[key + (K,)].chain), 4)
+                res["draft_chain_after_plain_ms"] = chain0 = round(replay_ms(lm._graphs[key].chain), 4)
+                res["break_even_tokens_per_verify_step"] = round(
+                    (res["verify_step_ms"] + chain) / (res["plain_step_ms"] + chain0), 3)
             print(json.dumps(res), flush=True)
         lm._graphs.clear()
         del lm
