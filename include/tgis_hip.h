@@ -436,6 +436,17 @@ int tgis_spec_accept(const int64_t* argmax_ids, const float* argmax_logprobs, co
                      int32_t* n_emit, int64_t* out_ids, float* out_logprobs, int64_t* latest_ids, int64_t* position_ids,
                      int64_t* all_input_ids, int64_t ld_all, int32_t* cu_seqlens, int64_t* stage_ids,
                      int32_t* stage_positions, int64_t B, void* stream);
+/* tgis_spec_accept behind a verify step whose rows were chosen by tgis_warp_sample_verify instead of the argmax
+ * (paged_causal_lm.py:630-641 is where the reference leaves sampled requests out of speculation; here they are verified).
+ * chosen_ids / chosen_logprobs [B, K + 1] stand where argmax_ids / argmax_logprobs stand above and every output is computed
+ * the same way by the same kernel.  In addition, do_sample int [B] (NULL: nothing more, the call equals tgis_spec_accept
+ * bit for bit) and rng [B, 2] uint64 (seed, offset), the streams of tgis_warp_sample: a request with do_sample[b] != 0 has
+ * rng[b].offset += n_emit[b], one draw per emitted token (utils/tokens.py:32-41 a Sampling draws once per token). */
+int tgis_spec_accept_sampled(const int64_t* chosen_ids, const float* chosen_logprobs, const int64_t* drafts, int64_t K,
+                             int32_t* n_emit, int64_t* out_ids, float* out_logprobs, int64_t* latest_ids,
+                             int64_t* position_ids, int64_t* all_input_ids, int64_t ld_all, int32_t* cu_seqlens,
+                             int64_t* stage_ids, int32_t* stage_positions, const int* do_sample, uint64_t* rng, int64_t B,
+                             void* stream);
 /* The drafter (stands where the reference calls its speculator, utils/paged.py prepare_inputs_with_speculation): prompt
  * lookup.  The context of request b is all_input_ids[b][0 .. len), len = position_ids[b] + 1 (clamped to [0, ld_all]).  For
  * n = N .. 1 (1 <= N <= 4): the largest j with j + n < len and tokens[j .. j + n) == tokens[len - n .. len); the first n
@@ -500,6 +511,26 @@ int tgis_warp_sample(const float* logits, int64_t ld_logits, float* scores, int6
                      int64_t ld_ids, int64_t L, int64_t exclude_id, const float* eos_adjust, int64_t eos_id,
                      const int* do_sample, uint64_t* rng, int64_t* next_ids, float* next_logprob, float* lse,
                      void* stream);
+/* The verify form of tgis_warp_sample: the chooser behind every row of a verify forward of speculative decoding
+ * (models/paged_causal_lm.py:481-562 the step; :630-641 the reference speculates for greedy requests only, this entry
+ * lets sampled and warped ones be verified by the draw their plain step would have made).  B requests, K drafts each,
+ * 0 <= K <= 7; logits / scores hold B (K + 1) rows, row r = b (K + 1) + j being request b's j-th verify row.
+ *   Row r takes request b's parameters from the same [B] arrays as above (temperature, top_k, top_p_cut, typical_p,
+ *   rep_penalty, do_sample): nothing is expanded on the host.
+ *   Repetition-penalty context of row (b, j): input_ids[b][0 .. L) as above (padding and exclude_id included), then
+ *   drafts[b][0 .. j) (drafts [B, K] int64; K = 0: may be NULL); out-of-range ids are skipped, duplicates penalised once.
+ *   eos_adjust [B, K + 1, 2]: (mode, factor) per row (utils/tokens.py:242-256 stepped once per row by the host).
+ *   A sampled row draws with (seed, offset + j) of rng[b]; rng [B, 2] is READ ONLY here (tgis_spec_accept_sampled
+ *   advances it by the tokens emitted).
+ * Outputs: next_ids int64, next_logprob f32, lse f32 [B, K + 1]; scores [B (K + 1), V].  Row (b, j) is, bit for bit, what
+ * tgis_warp_sample gives for a row with b's parameters, that context and the stream state (seed, offset + j); K = 0 is
+ * tgis_warp_sample except for the untouched rng.  No allocation, no sync; B = 0 returns TGIS_OK. */
+int tgis_warp_sample_verify(const float* logits, int64_t ld_logits, float* scores, int64_t ld_scores, int64_t B,
+                            int64_t K, int64_t V, const float* temperature, const int* top_k, const float* top_p_cut,
+                            const float* typical_p, const float* rep_penalty, const int64_t* input_ids, int64_t ld_ids,
+                            int64_t L, int64_t exclude_id, const int64_t* drafts, const float* eos_adjust, int64_t eos_id,
+                            const int* do_sample, const uint64_t* rng, int64_t* next_ids, float* next_logprob, float* lse,
+                            void* stream);
 
 #ifdef __cplusplus
 }

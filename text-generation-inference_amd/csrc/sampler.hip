@@ -24,6 +24,11 @@
 // Sampling is the exponential race the host path used (argmax p_i / E_i, E_i ~ Exp(1)) with a counter-based
 // generator: E_i = -log(u_i), u_i from Philox4x32-10 keyed by the request's seed with counter (i, draw offset).
 // A request's stream is (seed, offset): it survives concatenate / prune by copying two integers.
+//
+// The same two kernels serve the verify step of speculative decoding (tgis_warp_sample_verify): K + 1 rows per request,
+// each chosen as the plain step of its position would choose — the request's parameters, its context plus the drafts in
+// front of the row, the draw (seed, offset + j) — so that a draft is accepted exactly when the plain run would have emitted
+// it.  The row-to-request indirection is a template flag (struct Row); the plain instantiation is the code it was.
 #include "common.h"
 #include "rowwise_plan.h"
 
@@ -54,6 +59,28 @@ struct SampleArgs {
     int64_t* next_ids;
     float* next_logprob;
     float* lse;
+    // the verify form (tgis_warp_sample_verify): K1 = K + 1 rows per request, drafts [B, K]; unused by the plain form
+    int K1;
+    const int64_t* drafts;
+};
+
+// Which request a workgroup's row belongs to, and what differs between the two entry points.  Plain form: row = request.
+// Verify form: row r = b (K + 1) + j is request b's j-th verify row; it takes b's parameters, its own logits / scores /
+// eos_adjust / output entries, b's context extended by drafts[b][0 .. j), and the draw (seed, offset + j) of b's stream,
+// which it leaves as it found it (tgis_spec_accept_sampled advances it by what was emitted).
+template <bool VERIFY>
+struct Row {
+    int r, b, j;
+    __device__ explicit Row(const SampleArgs& a) {
+        r = blockIdx.x;
+        if (VERIFY) {
+            b = r / a.K1;
+            j = r - b * a.K1;
+        } else {
+            b = r;
+            j = 0;
+        }
+    }
 };
 
 __device__ __forceinline__ uint32_t order_key(float x) {  // unsigned order == float order
@@ -138,15 +165,17 @@ __device__ __forceinline__ uint32_t philox_u32(uint64_t seed, uint64_t offset, u
     return c[0];
 }
 
+template <bool VERIFY>
 __global__ __launch_bounds__(NT) void warp_sample_kernel(SampleArgs a) {
     __shared__ float fbuf[NW];
     __shared__ int ibuf[NW];
     __shared__ int hist[256];
     __shared__ uint32_t bc[2];
-    const int b = blockIdx.x, tid = threadIdx.x, V = a.V;
+    const Row<VERIFY> row(a);
+    const int r = row.r, b = row.b, tid = threadIdx.x, V = a.V;
     Block blk{fbuf, ibuf, tid & 63, tid >> 6};
-    const float* in = a.logits + (int64_t)b * a.ld_logits;
-    float* s = a.scores + (int64_t)b * a.ld_scores;
+    const float* in = a.logits + (int64_t)r * a.ld_logits;
+    float* s = a.scores + (int64_t)r * a.ld_scores;
     const float NEG_INF = -INFINITY;
 
     // ---- EOS adjustment, repetition penalty, temperature ---------------------------------------------------------
@@ -154,8 +183,8 @@ __global__ __launch_bounds__(NT) void warp_sample_kernel(SampleArgs a) {
     int eos_mode = 0;
     float eos_factor = 0.f;
     if (a.eos_adjust) {
-        eos_mode = (int)a.eos_adjust[2 * b];
-        eos_factor = a.eos_adjust[2 * b + 1];
+        eos_mode = (int)a.eos_adjust[2 * r];
+        eos_factor = a.eos_adjust[2 * r + 1];
     }
     auto adjusted = [&](int i) {
         float x = in[i];
@@ -167,8 +196,9 @@ __global__ __launch_bounds__(NT) void warp_sample_kernel(SampleArgs a) {
     if (pen != 1.0f && a.input_ids) {
         __syncthreads();
         const int64_t* ids = a.input_ids + (int64_t)b * a.ld_ids;
-        for (int j = tid; j < a.L; j += NT) {  // duplicates write the same value: each id is penalised once
-            int64_t id = ids[j];
+        const int n_ctx = a.L + row.j;  // the verify row's context ends with the drafts in front of it
+        for (int j = tid; j < n_ctx; j += NT) {  // duplicates write the same value: each id is penalised once
+            int64_t id = (!VERIFY || j < a.L) ? ids[j] : a.drafts[(int64_t)b * (a.K1 - 1) + (j - a.L)];
             if (id < 0 || id >= V || id == a.exclude_id) continue;
             float x = adjusted((int)id);
             x = x < 0.f ? x * pen : x / pen;
@@ -293,7 +323,7 @@ __global__ __launch_bounds__(NT) void warp_sample_kernel(SampleArgs a) {
     int chosen = mi;
     float chosen_score = m;
     if (a.do_sample && a.do_sample[b]) {
-        const uint64_t seed = a.rng[2 * b], offset = a.rng[2 * b + 1];
+        const uint64_t seed = a.rng[2 * b], offset = a.rng[2 * b + 1] + (uint64_t)row.j;
         float best = NEG_INF;
         int bi = 0x7fffffff;
         for (int i = tid; i < V; i += NT) {
@@ -311,12 +341,12 @@ __global__ __launch_bounds__(NT) void warp_sample_kernel(SampleArgs a) {
         if (bi >= V) bi = mi;
         chosen = bi;
         chosen_score = s[bi];
-        if (tid == 0) a.rng[2 * b + 1] = offset + 1;
+        if (!VERIFY && tid == 0) a.rng[2 * b + 1] = offset + 1;
     }
     if (tid == 0) {
-        a.next_ids[b] = chosen;
-        a.next_logprob[b] = chosen_score - log_z;
-        a.lse[b] = log_z;
+        a.next_ids[r] = chosen;
+        a.next_logprob[r] = chosen_score - log_z;
+        a.lse[r] = log_z;
     }
 }
 
@@ -327,24 +357,25 @@ __global__ __launch_bounds__(NT) void warp_sample_kernel(SampleArgs a) {
 // registers; the probabilities of the top-p / typical-p searches are computed once per search instead of once per bit.
 // Same per-thread element order, same expressions, same block reductions: bit-identical to warp_sample_kernel, which stays
 // for larger vocabularies.  (The global form re-read the 128 KB row from L2 ~80 times: 0.4 ms per step at V = 32000.)
-template <int NPT>
+template <int NPT, bool VERIFY>
 __global__ __launch_bounds__(NT) void warp_sample_reg_kernel(SampleArgs a) {
     __shared__ float fbuf[NW];
     __shared__ int ibuf[NW];
     __shared__ int hist[256];
     __shared__ uint32_t bc[2];
-    const int b = blockIdx.x, tid = threadIdx.x, V = a.V;
+    const Row<VERIFY> row(a);
+    const int r = row.r, b = row.b, tid = threadIdx.x, V = a.V;
     Block blk{fbuf, ibuf, tid & 63, tid >> 6};
-    const float* in = a.logits + (int64_t)b * a.ld_logits;
-    float* s = a.scores + (int64_t)b * a.ld_scores;
+    const float* in = a.logits + (int64_t)r * a.ld_logits;
+    float* s = a.scores + (int64_t)r * a.ld_scores;
     const float NEG_INF = -INFINITY;
 
     const float T = a.temperature ? a.temperature[b] : 1.0f;
     int eos_mode = 0;
     float eos_factor = 0.f;
     if (a.eos_adjust) {
-        eos_mode = (int)a.eos_adjust[2 * b];
-        eos_factor = a.eos_adjust[2 * b + 1];
+        eos_mode = (int)a.eos_adjust[2 * r];
+        eos_factor = a.eos_adjust[2 * r + 1];
     }
     auto adjusted = [&](int i) {
         float x = in[i];
@@ -368,8 +399,9 @@ __global__ __launch_bounds__(NT) void warp_sample_reg_kernel(SampleArgs a) {
         }
         __syncthreads();
         const int64_t* ids = a.input_ids + (int64_t)b * a.ld_ids;
-        for (int j = tid; j < a.L; j += NT) {  // duplicates write the same value: each id is penalised once
-            int64_t id = ids[j];
+        const int n_ctx = a.L + row.j;  // the verify row's context ends with the drafts in front of it
+        for (int j = tid; j < n_ctx; j += NT) {  // duplicates write the same value: each id is penalised once
+            int64_t id = (!VERIFY || j < a.L) ? ids[j] : a.drafts[(int64_t)b * (a.K1 - 1) + (j - a.L)];
             if (id < 0 || id >= V || id == a.exclude_id) continue;
             float v = adjusted((int)id);
             v = v < 0.f ? v * pen : v / pen;
@@ -527,7 +559,7 @@ __global__ __launch_bounds__(NT) void warp_sample_reg_kernel(SampleArgs a) {
     int chosen = mi;
     float chosen_score = m;
     if (a.do_sample && a.do_sample[b]) {
-        const uint64_t seed = a.rng[2 * b], offset = a.rng[2 * b + 1];
+        const uint64_t seed = a.rng[2 * b], offset = a.rng[2 * b + 1] + (uint64_t)row.j;
         float best = NEG_INF;
         int bi = 0x7fffffff;
 #pragma unroll
@@ -546,12 +578,12 @@ __global__ __launch_bounds__(NT) void warp_sample_reg_kernel(SampleArgs a) {
         if (bi >= V) bi = mi;
         chosen = bi;
         chosen_score = s[bi];
-        if (tid == 0) a.rng[2 * b + 1] = offset + 1;
+        if (!VERIFY && tid == 0) a.rng[2 * b + 1] = offset + 1;
     }
     if (tid == 0) {
-        a.next_ids[b] = chosen;
-        a.next_logprob[b] = chosen_score - log_z;
-        a.lse[b] = log_z;
+        a.next_ids[r] = chosen;
+        a.next_logprob[r] = chosen_score - log_z;
+        a.lse[r] = log_z;
     }
 }
 
@@ -562,6 +594,18 @@ SamplerPlan choose_sampler(int64_t V) {
     static const bool no_reg = getenv("TGIS_SAMPLER_GLOBAL_ROWS") != nullptr;  // A / B and test hook
     return {V <= 32 * NT && !no_reg};
 }
+
+namespace {
+
+template <bool VERIFY>
+void launch_sampler(const SampleArgs& a, int64_t rows, hipStream_t st) {
+    if (choose_sampler(a.V).reg)
+        hipLaunchKernelGGL((warp_sample_reg_kernel<32, VERIFY>), dim3((unsigned)rows), dim3(NT), 0, st, a);
+    else
+        hipLaunchKernelGGL((warp_sample_kernel<VERIFY>), dim3((unsigned)rows), dim3(NT), 0, st, a);
+}
+
+}  // namespace
 
 extern "C" int tgis_warp_sample(const float* logits, int64_t ld_logits, float* scores, int64_t ld_scores, int64_t B,
                                 int64_t V, const float* temperature, const int* top_k, const float* top_p_cut,
@@ -580,11 +624,37 @@ extern "C" int tgis_warp_sample(const float* logits, int64_t ld_logits, float* s
     TgisTimedScope timed(TGIS_OP_SAMPLE, st);
     SampleArgs a{logits, ld_logits, scores, ld_scores, (int)V, temperature, top_k, top_p_cut, typical_p, rep_penalty,
                  input_ids, ld_ids, (int)L, (int)exclude_id, eos_adjust, (int)eos_id, do_sample, rng, next_ids,
-                 next_logprob, lse};
-    if (choose_sampler(V).reg)
-        hipLaunchKernelGGL(warp_sample_reg_kernel<32>, dim3((unsigned)B), dim3(NT), 0, st, a);
-    else
-        hipLaunchKernelGGL(warp_sample_kernel, dim3((unsigned)B), dim3(NT), 0, st, a);
+                 next_logprob, lse, 1, nullptr};
+    launch_sampler<false>(a, B, st);
+    TGIS_CHECK_LAUNCH();
+    return TGIS_OK;
+}
+
+extern "C" int tgis_warp_sample_verify(const float* logits, int64_t ld_logits, float* scores, int64_t ld_scores, int64_t B,
+                                       int64_t K, int64_t V, const float* temperature, const int* top_k,
+                                       const float* top_p_cut, const float* typical_p, const float* rep_penalty,
+                                       const int64_t* input_ids, int64_t ld_ids, int64_t L, int64_t exclude_id,
+                                       const int64_t* drafts, const float* eos_adjust, int64_t eos_id, const int* do_sample,
+                                       const uint64_t* rng, int64_t* next_ids, float* next_logprob, float* lse,
+                                       void* stream) {
+    TGIS_CHECK_ARG(B == 0 || (logits && scores && next_ids && next_logprob && lse), "tgis_warp_sample_verify: null buffer");
+    TGIS_CHECK_ARG(V > 0 && V < (1ll << 31) && ld_logits >= V && ld_scores >= V,
+                   "tgis_warp_sample_verify: bad row geometry");
+    TGIS_CHECK_ARG(B >= 0 && K >= 0 && K <= 7 && (K == 0 || B == 0 || drafts) && B * (K + 1) < (1ll << 31),
+                   "tgis_warp_sample_verify: K drafts per request, 0 <= K <= 7");
+    TGIS_CHECK_ARG(!do_sample || rng, "tgis_warp_sample_verify: sampled rows need their (seed, offset) states");
+    TGIS_CHECK_ARG(!rep_penalty || (input_ids && L >= 0 && L < (1ll << 31) - 8 && ld_ids >= L),
+                   "tgis_warp_sample_verify: a repetition penalty needs the ids seen so far");
+    TGIS_CHECK_ARG(!eos_adjust || (eos_id >= 0 && eos_id < V),
+                   "tgis_warp_sample_verify: EOS adjustment without a valid EOS id");
+    if (B == 0) return TGIS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    TgisTimedScope timed(TGIS_OP_SAMPLE, st);
+    // (the kernels only read the states in this form: no row writes through the pointer)
+    SampleArgs a{logits, ld_logits, scores, ld_scores, (int)V, temperature, top_k, top_p_cut, typical_p, rep_penalty,
+                 input_ids, ld_ids, (int)L, (int)exclude_id, eos_adjust, (int)eos_id, do_sample, const_cast<uint64_t*>(rng),
+                 next_ids, next_logprob, lse, (int)K + 1, drafts};
+    launch_sampler<true>(a, B * (K + 1), st);
     TGIS_CHECK_LAUNCH();
     return TGIS_OK;
 }

@@ -27,13 +27,16 @@ __global__ void spec_stage_kernel(const int32_t* __restrict__ positions, const i
     if (j == 0) ctx[b] = pos + K1;
 }
 
+// am_ids / am_lps: the token chosen behind every verify row and its logprob — the argmax (tgis_spec_accept) or whatever
+// tgis_warp_sample_verify chose (tgis_spec_accept_sampled, which also passes the streams to advance; null: none).
 // One workgroup for the whole batch: the counts of all requests are B * K compares, so the block that needs their prefix
 // sums (cu_seqlens) recomputes nothing across workgroups and synchronises with nobody but itself.
 __global__ __launch_bounds__(256) void spec_accept_kernel(
     const int64_t* __restrict__ am_ids, const float* __restrict__ am_lps, const int64_t* __restrict__ drafts, int K,
     int32_t* __restrict__ n_emit, int64_t* __restrict__ out_ids, float* __restrict__ out_lps, int64_t* __restrict__ latest,
     int64_t* __restrict__ position_ids, int64_t* __restrict__ all_ids, int64_t ld_all, int32_t* __restrict__ cu_seqlens,
-    int64_t* __restrict__ stage_ids, int32_t* __restrict__ stage_pos, int64_t B) {
+    int64_t* __restrict__ stage_ids, int32_t* __restrict__ stage_pos, const int* __restrict__ do_sample,
+    uint64_t* __restrict__ rng, int64_t B) {
     const int K1 = K + 1;
     for (int64_t b = threadIdx.x; b < B; b += blockDim.x) {
         const int64_t* a = am_ids + b * K1;
@@ -43,6 +46,9 @@ __global__ __launch_bounds__(256) void spec_accept_kernel(
             ++n;
         }
         n_emit[b] = n;
+        // a sampled request drew once per emitted token (the rows behind the first miss drew for nothing: their draws are
+        // made again, at the same offsets, by the steps that emit those positions)
+        if (do_sample && do_sample[b]) rng[2 * b + 1] += (uint64_t)n;
         const int64_t pos = position_ids[b];
         for (int j = 0; j < K1; ++j) {
             const bool emit = j < n;
@@ -128,19 +134,43 @@ extern "C" int tgis_spec_stage(const int32_t* positions, const int64_t* latest_i
     return TGIS_OK;
 }
 
+namespace {
+
+int spec_accept(const char* what, const int64_t* ids, const float* logprobs, const int64_t* drafts, int64_t K, int32_t* n_emit,
+                int64_t* out_ids, float* out_logprobs, int64_t* latest_ids, int64_t* position_ids, int64_t* all_input_ids,
+                int64_t ld_all, int32_t* cu_seqlens, int64_t* stage_ids, int32_t* stage_positions, const int* do_sample,
+                uint64_t* rng, int64_t B, void* stream) {
+    // (an empty batch has no buffers to speak of: a tensor without elements hands over a null pointer)
+    TGIS_CHECK_ARG(B >= 0 && K >= 0 && K <= 7 &&
+                       (B == 0 || (ids && n_emit && position_ids && (K == 0 || drafts) && (!out_logprobs || logprobs) &&
+                                   (!all_input_ids || ld_all > 0) && (!do_sample || rng))),
+                   "%s: bad arguments", what);
+    if (B == 0) return TGIS_OK;
+    hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ids, logprobs, drafts, (int)K, n_emit,
+                       out_ids, out_logprobs, latest_ids, position_ids, all_input_ids, ld_all, cu_seqlens, stage_ids,
+                       stage_positions, do_sample, rng, B);
+    TGIS_CHECK_LAUNCH();
+    return TGIS_OK;
+}
+
+}  // namespace
+
 extern "C" int tgis_spec_accept(const int64_t* argmax_ids, const float* argmax_logprobs, const int64_t* drafts, int64_t K,
                                 int32_t* n_emit, int64_t* out_ids, float* out_logprobs, int64_t* latest_ids,
                                 int64_t* position_ids, int64_t* all_input_ids, int64_t ld_all, int32_t* cu_seqlens,
                                 int64_t* stage_ids, int32_t* stage_positions, int64_t B, void* stream) {
-    TGIS_CHECK_ARG(argmax_ids && n_emit && position_ids && B >= 0 && K >= 0 && K <= 7 && (K == 0 || drafts) &&
-                       (!out_logprobs || argmax_logprobs) && (!all_input_ids || ld_all > 0),
-                   "tgis_spec_accept: bad arguments");
-    if (B == 0) return TGIS_OK;
-    hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, argmax_ids, argmax_logprobs, drafts,
-                       (int)K, n_emit, out_ids, out_logprobs, latest_ids, position_ids, all_input_ids, ld_all, cu_seqlens,
-                       stage_ids, stage_positions, B);
-    TGIS_CHECK_LAUNCH();
-    return TGIS_OK;
+    return spec_accept("tgis_spec_accept", argmax_ids, argmax_logprobs, drafts, K, n_emit, out_ids, out_logprobs, latest_ids,
+                       position_ids, all_input_ids, ld_all, cu_seqlens, stage_ids, stage_positions, nullptr, nullptr, B, stream);
+}
+
+extern "C" int tgis_spec_accept_sampled(const int64_t* chosen_ids, const float* chosen_logprobs, const int64_t* drafts,
+                                        int64_t K, int32_t* n_emit, int64_t* out_ids, float* out_logprobs,
+                                        int64_t* latest_ids, int64_t* position_ids, int64_t* all_input_ids, int64_t ld_all,
+                                        int32_t* cu_seqlens, int64_t* stage_ids, int32_t* stage_positions,
+                                        const int* do_sample, uint64_t* rng, int64_t B, void* stream) {
+    return spec_accept("tgis_spec_accept_sampled", chosen_ids, chosen_logprobs, drafts, K, n_emit, out_ids, out_logprobs,
+                       latest_ids, position_ids, all_input_ids, ld_all, cu_seqlens, stage_ids, stage_positions, do_sample, rng,
+                       B, stream);
 }
 
 extern "C" int tgis_spec_propose(const int64_t* all_input_ids, int64_t ld_all, const int64_t* position_ids, int64_t K,

@@ -37,7 +37,7 @@ from tgis_amd.utils.kv_cache import (KV_SCALES_HEADROOM, PAGE, OutOfPages, Paged
                                      pages_for_budget, parse_kv_cache_dtype, parse_kv_prefix_reuse)
 from tgis_amd.utils.rank_group import RankGroup
 from tgis_amd.utils.spec_decode import (check_spec_world, fallback_cause, may_ever_verify, new_stats, parse_spec_ngram,
-                                        parse_spec_tokens)
+                                        parse_spec_sampling, parse_spec_tokens)
 from tgis_amd.utils.token_types import InputTokens, TokenInfo
 from tgis_amd.utils.tokens import HeterogeneousNextTokenChooser, get_input_tokens_info, get_token_info
 
@@ -436,13 +436,16 @@ class FlashCausalLM(Model):
     # the drafter of speculative decoding: the prompt lookup, or an MLP speculator on the device (set by the constructor)
     spec_drafter = "lookup"
     speculator = None
+    # whether batches that sample or carry processors verify drafts too (set by the constructor)
+    spec_sampling = False
 
     def __init__(self, model_name: str, revision: Optional[str], deployment_framework: str, dtype: torch.dtype,
                  quantize: Optional[str], model_config: Union[Any] = None, auto_model_class=None,
                  max_sequence_length: Optional[int] = None, engine=None, kv_cache_pages: Optional[int] = None,
                  kv_cache_dtype: Optional[str] = None, kv_scales: Union[None, str, dict] = None,
                  kv_prefix_reuse: Optional[bool] = None, spec_tokens: Optional[int] = None,
-                 spec_ngram: Optional[int] = None, speculator: Union[None, str, Any] = None):
+                 spec_ngram: Optional[int] = None, speculator: Union[None, str, Any] = None,
+                 spec_sampling: Optional[bool] = None):
         # KV cache element: "auto" (the model dtype) or "fp8_e4m3" (one byte, utils/kv_cache.py); None reads
         # TGIS_KV_CACHE_DTYPE.  Checked before anything is loaded — except on a rank of a tensor-parallel group, which loads
         # its shard and then tells its peers (agree_kv_cache_dtype below): they sit in a collective only it can release.
@@ -457,6 +460,10 @@ class FlashCausalLM(Model):
         self.spec_tokens = parse_spec_tokens(spec_tokens)
         self.spec_ngram = parse_spec_ngram(spec_ngram)
         check_spec_world(self.spec_tokens, getattr(engine, "world_size", 1) or 1)
+        # spec_sampling: batches that are not plain greedy (sampling, warpers, penalties, an unmet min_new_tokens) verify
+        # drafts as well, every row chosen by the fused chooser with the draw its plain step would have made; None reads
+        # TGIS_SPEC_SAMPLING (true / false, default false).  It means something only with spec_tokens > 0.
+        self.spec_sampling = parse_spec_sampling(spec_sampling) and self.spec_tokens > 0
         # speculator: the checkpoint directory of an MLP speculator (utils/mlp_speculator.py), the drafter in place of the
         # lookup; None reads TGIS_SPECULATOR, unset = the lookup.  It needs spec_tokens in 1 .. min(n_predict, 7) and ignores
         # spec_ngram.  Its config, tensor names and shapes are checked here, before any weight is on the device.
@@ -597,8 +604,9 @@ class FlashCausalLM(Model):
 
     def spec_stats(self) -> dict:
         """Counters of speculative decoding since construction (all zero with the option off): decode steps, those that
-        verified drafts, the plain steps of a speculating model by cause (utils/spec_decode.py FALLBACK_CAUSES), tokens
-        drafted, drafts accepted, tokens emitted by decode steps."""
+        verified drafts (and, of these, those of batches that are not plain greedy: spec_sampling), the plain steps of a
+        speculating model by cause (utils/spec_decode.py FALLBACK_CAUSES), tokens drafted, drafts accepted, tokens emitted by
+        decode steps."""
         return dict(self._spec_stats)
 
     def _default_kv_pages(self) -> int:
@@ -748,7 +756,10 @@ class FlashCausalLM(Model):
         K, st = self.spec_tokens, self._spec_stats
         st["decode_steps"] += 1
         ntc = batch.next_token_chooser
-        greedy = ntc.is_plain_greedy and batch.spec_hits is not None
+        plain_greedy = ntc.is_plain_greedy
+        # spec_sampling: what the step rule needs is a chooser for K + 1 rows per request on the device, and the fused one
+        # serves every batch (`_process_spec_tokens`); top-n tokens and ranks remain a cause of their own
+        greedy = (plain_greedy or self.spec_sampling) and batch.spec_hits is not None
         cause = fallback_cause(
             K, graph_bucket(len(batch)), greedy, any(r.details.top_n_toks or r.details.ranks for r in batch.requests),
             [t - n for t, n in zip(batch.total_lengths, batch.input_lengths)], batch.spec_hits_host)
@@ -761,6 +772,8 @@ class FlashCausalLM(Model):
             st["fallback_" + cause] += 1
             return False
         st["verify_steps"] += 1
+        if not plain_greedy:
+            st["verify_steps_sampled"] += 1
         return True
 
     def _process_prefill(self, batch: FlashCausalLMBatch, out):
@@ -791,12 +804,17 @@ class FlashCausalLM(Model):
             logits = out  # already one row per request
 
         ntc = batch.next_token_chooser
-        simple = ntc.is_plain_greedy and not any(r.details.top_n_toks or r.details.ranks for r in batch.requests)
+        details = any(r.details.top_n_toks or r.details.ranks for r in batch.requests)
+        simple = ntc.is_plain_greedy and not details
         graph = fused[2] if fused is not None else None
         if self.spec_tokens and not prefill:
             self._spec_stats["emitted"] += len(batch)  # (a verify step adds the drafts it accepted)
-            if simple and graph is not None and batch.spec_hits is not None:
-                return self._process_spec_tokens(batch, fused, generated_tokens, decode_errors)
+            if graph is not None and batch.spec_hits is not None:
+                if simple:
+                    return self._process_spec_tokens(batch, fused, generated_tokens, decode_errors)
+                if self.spec_sampling and not details:
+                    # verify or plain (K = 0): the fused chooser behind every row in place of the captured argmax
+                    return self._process_spec_tokens(batch, fused, generated_tokens, decode_errors, logits=logits)
         read_host = None
         if simple:
             # one kernel (already part of the decode graph), one device->host copy for the whole batch
@@ -855,17 +873,31 @@ class FlashCausalLM(Model):
         return next_token_ids
 
     def _process_spec_tokens(self, batch: FlashCausalLMBatch, fused, generated_tokens: List[TokenInfo],
-                             decode_errors: List[GenerateError]):
-        """What follows a greedy decode step of a speculating model, verify (K drafts per request) or plain (K = 0): one
-        launch accepts and does the bookkeeping of `_process_new_tokens` for up to K + 1 tokens per request
-        (tgis_spec_accept), one drafts the next step (tgis_spec_propose), one copy brings ids, logprobs, counts and the
-        lookup's hits to the host.  Request i contributes n_emit[i] TokenInfos, in order."""
+                             decode_errors: List[GenerateError], logits: Optional[torch.Tensor] = None):
+        """What follows a decode step of a speculating model, verify (K drafts per request) or plain (K = 0): one launch
+        accepts and does the bookkeeping of `_process_new_tokens` for up to K + 1 tokens per request (tgis_spec_accept),
+        one drafts the next step (tgis_spec_propose), one copy brings ids, logprobs, counts and the lookup's hits to the
+        host.  Request i contributes n_emit[i] TokenInfos, in order.
+        logits: None for a plain-greedy batch, whose rows the captured argmax chose.  Otherwise (spec_sampling) the step's
+        logits [B (K + 1), V]: the fused chooser chooses behind every row as the plain step of that position would
+        (tgis_warp_sample_verify: the request's parameters, its context plus the drafts in front of the row, the draw
+        (seed, offset + j)), a draft is accepted while the chosen token equals it — for a deterministic drafter the
+        rejection rule, accept with probability p(draft) — and tgis_spec_accept_sampled also advances each sampled
+        request's stream by what it emitted."""
         ids, lps, graph = fused
         B, K, K1, out = len(batch), graph.K, graph.K + 1, graph.spec_out
-        next_token_ids = native.spec_accept(
-            ids, lps, batch.spec_drafts if K else None, out.n_emit[:B], batch.position_ids, out_ids=out.ids[:B * K1],
-            out_logprobs=out.lps[:B * K1], all_input_ids=batch.all_input_ids_tensor, cu_seqlens=batch.cu_seqlens,
-            stage_ids=graph.input_ids[:B], stage_positions=graph.positions[:B])
+        ntc = batch.next_token_chooser
+        outputs = dict(out_ids=out.ids[:B * K1], out_logprobs=out.lps[:B * K1], all_input_ids=batch.all_input_ids_tensor,
+                       cu_seqlens=batch.cu_seqlens, stage_ids=graph.input_ids[:B], stage_positions=graph.positions[:B])
+        drafts = batch.spec_drafts if K else None
+        if logits is None:
+            next_token_ids = native.spec_accept(ids, lps, drafts, out.n_emit[:B], batch.position_ids, **outputs)
+        else:
+            ids, lps, _lse, _scores = ntc.choose_fused_verify(batch.all_input_ids_tensor[:, :batch.max_seqlen], logits,
+                                                              drafts, K)
+            do_sample, rng = ntc.fused_streams(logits.device)
+            next_token_ids = native.spec_accept_sampled(ids.view(-1), lps.view(-1), drafts, out.n_emit[:B],
+                                                        batch.position_ids, do_sample=do_sample, rng=rng, **outputs)
         graph.staged_ids, graph.staged_pos = next_token_ids, batch.position_ids
         drafting = may_ever_verify(self.spec_tokens, graph_bucket(B))
         if self.speculator is not None:
@@ -886,6 +918,8 @@ class FlashCausalLM(Model):
         ids_host, lps_host, n_emit, hits = out.read(B, want_lps)
         if drafting:
             batch.note_spec_hits(hits)
+        if logits is not None:
+            ntc.commit_verify(n_emit)
         for i, request in enumerate(batch.requests):
             for j in range(i * K1, i * K1 + n_emit[i]):
                 info = TokenInfo(request_id=request.id, token_id=ids_host[j])

@@ -112,6 +112,8 @@ SIGNATURES = {
     "tgis_decode_advance": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp]),
     "tgis_spec_stage": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp]),
     "tgis_spec_accept": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp]),
+    "tgis_spec_accept_sampled": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp,
+                                          _c_i64, _vp]),
     "tgis_spec_propose": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _c_i64, _vp]),
     "tgis_spec_mlp_input": (_c_int, [_vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64, _c_int, _c_f, _c_int, _vp]),
     "tgis_spec_mlp_state": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _c_f, _c_f, _vp, _c_i64, _c_i64, _c_int, _vp]),
@@ -120,6 +122,8 @@ SIGNATURES = {
     "tgis_argmax_scratch_bytes": (_c_i64, [_c_i64]),
     "tgis_warp_sample": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64,
                                   _c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tgis_warp_sample_verify": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
@@ -931,7 +935,7 @@ def spec_stage(positions, latest_ids, drafts, block_tables, input_ids, positions
 
 
 def spec_accept(argmax_ids, argmax_logprobs, drafts, n_emit, position_ids, out_ids=None, out_logprobs=None,
-                all_input_ids=None, cu_seqlens=None, stage_ids=None, stage_positions=None):
+                all_input_ids=None, cu_seqlens=None, stage_ids=None, stage_positions=None, _sampled=None):
     """After a verify step (tgis_spec_accept): request b emits the greedy ids behind its longest accepted draft prefix and
     the one that follows it; n_emit, the emitted ids / logprobs, position_ids += n_emit, the scatter into all_input_ids and
     the prefix sums onto cu_seqlens in one launch.  Returns the new latest ids.  drafts None (K = 0): decode_advance."""
@@ -951,12 +955,24 @@ def spec_accept(argmax_ids, argmax_logprobs, drafts, n_emit, position_ids, out_i
     assert stage_ids is None or _is(stage_ids, torch.int64, B)
     assert stage_positions is None or _is(stage_positions, torch.int32, B)
     latest = torch.empty(B, dtype=torch.int64, device=position_ids.device)
-    _check(
-        load_library().tgis_spec_accept(_ptr(argmax_ids), _ptr(argmax_logprobs), _ptr(drafts), K, _ptr(n_emit),
-                                        _ptr(out_ids), _ptr(out_logprobs), _ptr(latest), _ptr(position_ids),
-                                        _ptr(all_input_ids), ld, _ptr(cu_seqlens), _ptr(stage_ids), _ptr(stage_positions),
-                                        B, _stream()), "tgis_spec_accept")
+    args = (_ptr(argmax_ids), _ptr(argmax_logprobs), _ptr(drafts), K, _ptr(n_emit), _ptr(out_ids), _ptr(out_logprobs),
+            _ptr(latest), _ptr(position_ids), _ptr(all_input_ids), ld, _ptr(cu_seqlens), _ptr(stage_ids), _ptr(stage_positions))
+    if _sampled is None:
+        _check(load_library().tgis_spec_accept(*args, B, _stream()), "tgis_spec_accept")
+    else:
+        do_sample, rng = _sampled
+        _check(load_library().tgis_spec_accept_sampled(*args, _ptr(do_sample), _ptr(rng), B, _stream()),
+               "tgis_spec_accept_sampled")
     return latest
+
+
+def spec_accept_sampled(chosen_ids, chosen_logprobs, drafts, n_emit, position_ids, do_sample=None, rng=None, **outputs):
+    """tgis_spec_accept_sampled: spec_accept on the ids and logprobs warp_sample_verify chose, which also advances the
+    offset of rng [B, 2] by n_emit for the requests with do_sample [B] != 0 (do_sample None: spec_accept bit for bit)."""
+    B = position_ids.numel()
+    assert do_sample is None or (_is(do_sample, torch.int32, B) and rng is not None)
+    assert rng is None or (rng.dtype == torch.int64 and rng.shape == (B, 2) and rng.is_contiguous())
+    return spec_accept(chosen_ids, chosen_logprobs, drafts, n_emit, position_ids, _sampled=(do_sample, rng), **outputs)
 
 
 def spec_propose(all_input_ids, position_ids, ngram: int, drafts, hits, hits_copy=None):
@@ -1057,4 +1073,40 @@ def warp_sample(logits, temperature=None, top_k=None, top_p_cut=None, typical_p=
             _ptr(logits), logits.stride(0), _ptr(scores), V, B, V, _ptr(temperature), _ptr(top_k), _ptr(top_p_cut),
             _ptr(typical_p), _ptr(rep_penalty), _ptr(input_ids), ld_ids, L, exclude_id, _ptr(eos_adjust), eos_id,
             _ptr(do_sample), _ptr(rng), _ptr(ids), _ptr(lps), _ptr(lse), _stream()), "tgis_warp_sample")
+    return ids, lps, lse, scores
+
+
+def warp_sample_verify(logits, drafts, K: int, temperature=None, top_k=None, top_p_cut=None, typical_p=None,
+                       rep_penalty=None, input_ids=None, exclude_id: int = -1, eos_adjust=None, eos_id: int = -1,
+                       do_sample=None, rng=None):
+    """The chooser behind every row of a verify forward in one launch (tgis_warp_sample_verify): logits [B (K + 1), V], the
+    parameter arrays [B] of warp_sample, drafts [B, K] (K = 0: None), eos_adjust [B, K + 1, 2]; rng [B, 2] is only read.
+    Returns (next_ids int64 [B, K + 1], logprob f32 [B, K + 1], lse f32 [B, K + 1], warped scores f32 [B (K + 1), V])."""
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1
+    R, V = logits.shape
+    K1 = K + 1
+    assert 0 <= K <= 7 and R % K1 == 0
+    B = R // K1
+    dev = logits.device
+    for t, dt in ((temperature, torch.float32), (top_k, torch.int32), (top_p_cut, torch.float32),
+                  (typical_p, torch.float32), (rep_penalty, torch.float32), (do_sample, torch.int32)):
+        assert t is None or (t.dtype == dt and t.numel() == B and t.is_contiguous() and t.device == dev)
+    assert (drafts is None and K == 0) or (drafts.shape == (B, K) and _is(drafts, torch.int64, B * K))
+    assert rng is None or (rng.dtype == torch.int64 and rng.shape == (B, 2) and rng.is_contiguous())
+    assert eos_adjust is None or (eos_adjust.dtype == torch.float32 and eos_adjust.shape == (B, K1, 2)
+                                  and eos_adjust.is_contiguous())
+    L = ld_ids = 0
+    if input_ids is not None:
+        assert input_ids.dtype == torch.int64 and input_ids.dim() == 2 and input_ids.shape[0] == B
+        assert input_ids.stride(1) == 1
+        L, ld_ids = input_ids.shape[1], input_ids.stride(0)
+    scores = torch.empty((R, V), dtype=torch.float32, device=dev)
+    ids = torch.empty((B, K1), dtype=torch.int64, device=dev)
+    lps = torch.empty((B, K1), dtype=torch.float32, device=dev)
+    lse = torch.empty((B, K1), dtype=torch.float32, device=dev)
+    _check(
+        load_library().tgis_warp_sample_verify(
+            _ptr(logits), logits.stride(0), _ptr(scores), V, B, K, V, _ptr(temperature), _ptr(top_k), _ptr(top_p_cut),
+            _ptr(typical_p), _ptr(rep_penalty), _ptr(input_ids), ld_ids, L, exclude_id, _ptr(drafts), _ptr(eos_adjust),
+            eos_id, _ptr(do_sample), _ptr(rng), _ptr(ids), _ptr(lps), _ptr(lse), _stream()), "tgis_warp_sample_verify")
     return ids, lps, lse, scores

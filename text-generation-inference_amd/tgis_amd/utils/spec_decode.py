@@ -1,6 +1,8 @@
 """Prompt-lookup speculative decoding, the host rules: the options, which decode steps verify drafts, and the
 counters.  The kernels are tgis_spec_stage / tgis_spec_accept / tgis_spec_propose (csrc/spec_decode.hip); the captured
-verify step is models/decode_graph.py's _VerifyGraph.  Nothing here needs a GPU."""
+verify step is models/decode_graph.py's _VerifyGraph.  With spec_sampling, batches that sample or carry processors verify too:
+tgis_warp_sample_verify chooses behind every row, tgis_spec_accept_sampled accepts and advances the streams (utils/tokens.py
+choose_fused_verify / commit_verify).  Nothing here needs a GPU."""
 import os
 from typing import List, Optional
 
@@ -10,7 +12,8 @@ MAX_VERIFY_ROWS = 64  # what the decode GEMMs serve: graph_bucket(B) * (K + 1) r
 
 # why a decode step of a speculating model ran the plain step, one counter each (spec_stats()["fallback_" + cause])
 FALLBACK_CAUSES = ("not_greedy", "details", "rows", "remaining", "no_match", "pages")
-SPEC_STATS = ("decode_steps", "verify_steps") + tuple("fallback_" + c for c in FALLBACK_CAUSES) + (
+# verify_steps_sampled: those of `verify_steps` whose rows were chosen by the fused chooser (spec_sampling) and not the argmax
+SPEC_STATS = ("decode_steps", "verify_steps", "verify_steps_sampled") + tuple("fallback_" + c for c in FALLBACK_CAUSES) + (
     "drafted", "accepted", "emitted")
 
 
@@ -40,6 +43,20 @@ def parse_spec_ngram(value=None) -> int:
     return _parse_int(value, "TGIS_SPEC_NGRAM", 3, 1, MAX_SPEC_NGRAM, "spec_ngram (TGIS_SPEC_NGRAM)")
 
 
+def parse_spec_sampling(value=None) -> bool:
+    """Whether batches that are not plain greedy (sampling, warpers, penalties, an unmet min_new_tokens) verify drafts too:
+    the argument, else TGIS_SPEC_SAMPLING (unset: false).  A bool, "true" or "false"; anything else raises.  It means
+    something only with spec_tokens > 0."""
+    if value is None:
+        value = os.getenv("TGIS_SPEC_SAMPLING", "false")
+    if isinstance(value, bool):
+        return value
+    name = str(value).strip().lower()
+    if name not in ("true", "false"):
+        raise ValueError(f"spec_sampling (TGIS_SPEC_SAMPLING) {value!r} is not supported (true or false)")
+    return name == "true"
+
+
 def check_spec_world(spec_tokens: int, tp_world: int) -> None:
     if spec_tokens > 0 and tp_world > 1:
         raise NotImplementedError(
@@ -51,7 +68,9 @@ def fallback_cause(K: int, rows: int, plain_greedy: bool, details: bool, remaini
                    hits: List[int]) -> Optional[str]:
     """Why a decode step must not verify drafts, or None if it may (the page look-ahead is tried after this).
     rows: graph_bucket(batch size); remaining: total_length - input_length per request; hits: the lookups' results, or a
-    callable that fetches them — it is called only when nothing cheaper has decided the step."""
+    callable that fetches them — it is called only when nothing cheaper has decided the step.
+    plain_greedy: with spec_sampling on, the caller passes "the fused chooser can choose for this batch on the device" in its
+    place (always true for logits on the GPU), so that nothing answers `not_greedy`; details still keep the plain step."""
     if not plain_greedy:
         return "not_greedy"
     if details:  # top_n_toks / ranks are read from the warped scores of one row per request

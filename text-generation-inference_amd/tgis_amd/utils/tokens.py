@@ -8,7 +8,8 @@ choice, log-softmax only when some request wants logprobs), `HeterogeneousSampli
 Differences: when the whole batch is plain greedy with no processors, `choose_greedy_fused` runs one HIP
 kernel (argmax + logprob) and the caller does a single device->host copy instead of one `.item()` per request;
 for any other batch whose logits are on the GPU, `choose_fused` runs the whole chain (EOS mask / length penalty,
-repetition penalty, warpers, argmax or draw, log-softmax at the chosen id) as one launch of `tgis_warp_sample`.
+repetition penalty, warpers, argmax or draw, log-softmax at the chosen id) as one launch of `tgis_warp_sample`;
+`choose_fused_verify` / `commit_verify` are its form for the K + 1 rows per request of a speculative verify step.
 The torch processors below remain the definition of the semantics (pinned to HF's per-row processors on CPU) and
 the path for logits that live on the host."""
 import os
@@ -200,20 +201,38 @@ class HeterogeneousNextTokenChooser:
         logprobs = torch.log_softmax(scores, -1) if any(self.return_logprobs) else NONES
         return next_ids, scores, logprobs
 
+    @staticmethod
+    def _eos_rule(cur: int, min_new: int, lp):
+        """One step of tokens.py:242-256 for one request: ((mode, factor) or None, the counter afterwards).  The counter
+        only advances while the request is below min_new_tokens or has a length penalty."""
+        if cur < min_new:
+            return (1.0, 0.0), cur + 1
+        if lp is not None:
+            tokens_past = cur - lp[0]
+            return ((2.0, pow(lp[1], tokens_past) - 1) if tokens_past > 0 else None), cur + 1
+        return None, cur
+
     def _eos_adjustments(self):
         """{row: (mode, factor)} for this step — mode 1: EOS masked while the request is below min_new_tokens,
         mode 2: EOS score += |score| * factor (length penalty) — and the step bookkeeping of tokens.py:242-256."""
         rows = {}
         for idx in range(len(self.current_tokens)):
-            cur, lp = self.current_tokens[idx], self.length_penalty[idx]
-            if cur < self.min_new_tokens[idx]:
-                rows[idx] = (1.0, 0.0)
-                self.current_tokens[idx] += 1
-            elif lp is not None:
-                tokens_past = cur - lp[0]
-                if tokens_past > 0:
-                    rows[idx] = (2.0, pow(lp[1], tokens_past) - 1)
-                self.current_tokens[idx] += 1
+            adj, self.current_tokens[idx] = self._eos_rule(self.current_tokens[idx], self.min_new_tokens[idx],
+                                                           self.length_penalty[idx])
+            if adj is not None:
+                rows[idx] = adj
+        return rows
+
+    def _eos_adjustments_verify(self, K: int):
+        """{(request, verify row j): (mode, factor)}: what `_eos_adjustments` would answer on each of the next K + 1 steps,
+        from a copy of the counters — row j has j more tokens behind it than row 0.  The counters themselves move in
+        `commit_verify`, by what the step emitted."""
+        rows = {}
+        for idx, cur in enumerate(self.current_tokens):
+            for j in range(K + 1):
+                adj, cur = self._eos_rule(cur, self.min_new_tokens[idx], self.length_penalty[idx])
+                if adj is not None:
+                    rows[idx, j] = adj
         return rows
 
     def _fused_params(self, device):
@@ -272,6 +291,48 @@ class HeterogeneousNextTokenChooser:
             for s in self.choice.sampling_mapping.values():
                 s.offset += 1
         return out
+
+    def choose_fused_verify(self, input_ids: torch.Tensor, scores: torch.Tensor, drafts: Optional[torch.Tensor], K: int):
+        """The verify form of `choose_fused` (speculative decoding, utils/spec_decode.py): scores [B (K + 1), V] are the
+        logits behind each request's latest token and its K drafts [B, K]; row (b, j) is chosen exactly as `choose_fused`
+        would choose on the j-th step from now if drafts[b][:j] were the tokens emitted until then — request b's
+        parameters, its context plus those drafts, the EOS rule j steps on, the draw (seed, offset + j).  One launch of
+        tgis_warp_sample_verify; returns (ids [B, K + 1], logprobs [B, K + 1], lse [B, K + 1], warped scores).  Nothing
+        of the chooser's state moves: `commit_verify` does that once the accepted count is known."""
+        p = self._fused_params(scores.device)
+        adj = self._eos_adjustments_verify(K)
+        eos_adjust = None
+        if adj:
+            host = torch.zeros((len(self.do_sample), K + 1, 2), dtype=torch.float32)
+            for (idx, j), a in adj.items():
+                host[idx, j, 0], host[idx, j, 1] = a
+            eos_adjust = host.to(scores.device, non_blocking=True)
+        logits = scores if scores.dtype == torch.float32 else scores.float()
+        if logits.stride(-1) != 1:
+            logits = logits.contiguous()
+        return native.warp_sample_verify(
+            logits, drafts if K else None, K, temperature=p["temperature"], top_k=p["top_k"], top_p_cut=p["top_p_cut"],
+            typical_p=p["typical_p"], rep_penalty=p["rep_penalty"],
+            input_ids=input_ids if p["rep_penalty"] is not None else None, exclude_id=p["exclude_id"],
+            eos_adjust=eos_adjust, eos_id=self.eos_token_id if eos_adjust is not None else -1,
+            do_sample=p["do_sample"], rng=p["rng"])
+
+    def fused_streams(self, device):
+        """(do_sample int32 [B], rng int64 [B, 2]) on the device, or (None, None) for a batch without sampled requests:
+        what tgis_spec_accept_sampled advances behind `choose_fused_verify`."""
+        p = self._fused_params(device)
+        return p["do_sample"], p["rng"]
+
+    def commit_verify(self, n_emit: List[int]):
+        """After the accept of a verify step that gave request i n_emit[i] tokens: the EOS rule's counters take that many
+        steps, and the host mirror of each stream's offset follows the device (one draw per emitted token)."""
+        for idx, n in enumerate(n_emit):
+            for _ in range(n):
+                _, self.current_tokens[idx] = self._eos_rule(self.current_tokens[idx], self.min_new_tokens[idx],
+                                                             self.length_penalty[idx])
+        if isinstance(self.choice, HeterogeneousSampling):
+            for idx, s in self.choice.sampling_mapping.items():
+                s.offset += n_emit[idx]
 
     def choose_greedy_fused(self, scores: torch.Tensor):
         """(ids int64 [B], logprob f32 [B]) by one kernel; valid only when `is_plain_greedy`."""

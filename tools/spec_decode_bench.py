@@ -24,8 +24,16 @@ verify step; `draft_chain_after_plain_ms` the one behind the plain step); `break
 + chain) / (plain step + chain); and the same three runs, whose `plain` one is the plain steps of the speculating model,
 chain included.  RANDOM SPECULATOR WEIGHTS DRAFT GARBAGE: acceptance on real text is not measured here.
 
+With --sampled the requests sample (temperature 0.8 and top-p 0.9, seeded) and the speculating model has spec_sampling on:
+B = 8, K = 3.  One JSON line: ms per step through generate_token (host clock, device sync on both sides) of the plain
+sampled step of a model without speculation — the step as it was before the option existed — of the speculating model's
+plain (K = 0) step, and of its verify step with every draft forced right and with none; the same two verify runs for greedy
+requests on the same model (the captured argmax in place of the chooser); and the chooser's launch alone (HIP events) on
+B and on B (K + 1) rows.  Seeded streams are reproducible, so the forced drafts are the plain run's own tokens.
+
     python tools/spec_decode_bench.py [--config llama2-7b-gptq] [--tokens 32] > profiles/spec_decode_bench.json
-    python tools/spec_decode_bench.py --speculator 4096,4096,3 > profiles/spec_mlp_bench.json"""
+    python tools/spec_decode_bench.py --speculator 4096,4096,3 > profiles/spec_mlp_bench.json
+    python tools/spec_decode_bench.py --sampled > profiles/spec_sampled_bench.json"""
 import argparse
 import json
 import os
@@ -62,9 +70,11 @@ class IdTokenizer:
         return {"input_ids": [[int(w[1:]) for w in t.split()] for t in texts]}
 
 
-def prefill(lm, tok, prompts, max_new):
+def prefill(lm, tok, prompts, max_new, sampled=False):
     reqs = [generate_pb2.Request(id=i, inputs=" ".join(f"t{t}" for t in p), input_length=len(p), truncate=False,
                                  max_output_length=max_new) for i, p in enumerate(prompts)]
+    for i, r in enumerate(reqs if sampled else []):
+        r.parameters.temperature, r.parameters.top_p, r.parameters.seed = 0.8, 0.9, 100 + i
     batch, errs = lm.batch_type.from_pb(generate_pb2.Batch(id=0, requests=reqs), tok, lm.dtype, lm.device, lm.word_embeddings,
                                         None, True)
     assert not errs
@@ -163,10 +173,109 @@ def synthetic_speculator(E, I, P, V, dtype):
     return mlp_speculator.SpeculatorCheckpoint(cfg, {n: cfg.shape_of(*ki) for n, ki in names.items()}, load)
 
 
+def chooser_ms(V, B, K, dev, n=30):
+    """Median ms of the chooser's launch alone, temperature + top-p, every row sampled: (tgis_warp_sample on B rows,
+    tgis_warp_sample_verify on B (K + 1) rows)."""
+    from tgis_amd import native
+
+    g = torch.Generator().manual_seed(0)
+    logits = (torch.randn(B * (K + 1), V, generator=g) * 3).to(dev)
+    temp = torch.full((B,), 0.8, device=dev)
+    cut = torch.full((B,), float(np.float32(1) - np.float32(0.9)), device=dev)
+    flags = torch.ones(B, dtype=torch.int32, device=dev)
+    rng = torch.tensor([[100 + b, 0] for b in range(B)], dtype=torch.int64, device=dev)
+    drafts = torch.full((B, K), 3, dtype=torch.int64, device=dev)
+    calls = (lambda: native.warp_sample(logits[:B], temperature=temp, top_p_cut=cut, do_sample=flags, rng=rng),
+             lambda: native.warp_sample_verify(logits, drafts, K, temperature=temp, top_p_cut=cut, do_sample=flags, rng=rng))
+    out = []
+    for call in calls:
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+        for _ in range(3):
+            call()
+        for a, b in ev:
+            a.record()
+            call()
+            b.record()
+        torch.cuda.synchronize()
+        out.append(round(statistics.median(a.elapsed_time(b) for a, b in ev), 4))
+    return out
+
+
+def sampled_main(args, eng, cfg, dtype, quantize, tok, dev):
+    B, K, T = 8, 3, args.tokens
+    max_new = T + 16
+    pages = B * PagedKVCache.pages_for(CTX + max_new) + 8
+    prompts = [np.random.default_rng(2025).integers(3, cfg.vocab_size, size=CTX).tolist() for _ in range(B)]
+    ones, zeros = [1] * B, [0] * B
+    res = {"config": args.config, "ctx": CTX, "B": B, "K": K, "V": cfg.vocab_size, "tokens_per_request": T,
+           "sampling": "temperature 0.8, top_p 0.9, seeded",
+           "note": "synthetic weights: says nothing about real acceptance rates; ms per step through generate_token"}
+
+    def no_drafts(batch, streams):
+        batch.spec_hits = torch.zeros_like(batch.spec_hits)
+        batch.note_spec_hits(zeros)
+
+    def garbage(batch, streams):
+        batch.spec_drafts = torch.full_like(batch.spec_drafts, 3)
+        batch.spec_hits = torch.ones_like(batch.spec_hits)
+        batch.note_spec_hits(ones)
+
+    def run(lm, force, n, sampled):
+        for timed in (False, True):  # an untimed pass pays the captures
+            batch, streams = prefill(lm, tok, prompts, max_new, sampled=sampled)
+            before = lm.spec_stats()
+            sec, steps, emitted, _, _ = decode(lm, batch, streams, n if timed else 1 + 2 * (K + 1), force=force)
+            batch.release()
+        return sec, steps, emitted, streams, {k: v - before[k] for k, v in lm.spec_stats().items()}
+
+    def report(name, out, plain=None):
+        sec, steps, emitted, streams, d = out
+        res[f"{name}_ms_per_step"] = round(sec / steps * 1e3, 4)
+        res[f"{name}_tokens_per_s"] = round(emitted / sec, 1)
+        res[f"{name}_tokens_per_step_and_request"] = round(emitted / steps / B, 3)
+        if plain is not None:
+            res[f"{name}_stats"] = {k: d[k] for k in ("verify_steps", "verify_steps_sampled", "fallback_not_greedy", "drafted",
+                                                      "accepted")}
+            res[f"{name}_ids_equal_plain"] = all(streams[i][:T] == plain[i][:T] for i in streams)
+
+    lm0 = FlashCausalLM("synthetic", None, "synthetic", dtype, quantize, engine=eng, kv_cache_pages=pages)
+    with lm0.context_manager():
+        out = run(lm0, None, T + K, True)
+        report("plain_sampled_step_without_speculation", out)
+        plain_s = out[3]
+        out = run(lm0, None, T + K, False)
+        report("plain_greedy_step_without_speculation", out)
+        plain_g = out[3]
+    lm0._graphs.clear()
+    del lm0
+    torch.cuda.empty_cache()
+    lm = FlashCausalLM("synthetic", None, "synthetic", dtype, quantize, engine=eng, kv_cache_pages=pages, spec_tokens=K,
+                       spec_sampling=True)
+    offs = torch.arange(K, device=dev)[None]
+    with lm.context_manager():
+        for kind, sampled, plain in (("sampled", True, plain_s), ("greedy", False, plain_g)):
+            plain_dev = torch.tensor([plain[i] + [3] * K for i in range(B)], dtype=torch.int64, device=dev)
+
+            def truth(batch, streams):
+                at = torch.tensor([len(streams[r.id]) for r in batch.requests], device=dev)[:, None] + offs
+                batch.spec_drafts = plain_dev.gather(1, at.clamp_(max=plain_dev.shape[1] - 1))
+                batch.spec_hits = torch.ones_like(batch.spec_hits)
+                batch.note_spec_hits(ones)
+
+            report(f"{kind}_plain_step_of_the_speculating_model", run(lm, no_drafts, T, sampled), plain)
+            report(f"{kind}_verify_accept_all", run(lm, truth, T, sampled), plain)
+            report(f"{kind}_verify_accept_none", run(lm, garbage, T, sampled), plain)
+    res["chooser_ms_plain_B_rows"], res["chooser_ms_verify_B_K1_rows"] = chooser_ms(cfg.vocab_size, B, K, dev)
+    res["not_measured"] = "acceptance on real text; other B, K, V and warpers; the MLP drafter with sampled requests"
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--speculator", default=None, metavar="E,I,P",
                     help="draft with a synthetic MLP speculator of these sizes (e.g. 4096,4096,3) instead of the lookup")
+    ap.add_argument("--sampled", action="store_true",
+                    help="sampled requests (temperature + top-p) on a model with spec_sampling: B = 8, K = 3")
     ap.add_argument("--config", default="llama2-7b-gptq", choices=sorted(bench.CONFIGS))
     ap.add_argument("--tokens", type=int, default=32, help="tokens generated per request in the timed runs")
     args = ap.parse_args()
@@ -176,6 +285,8 @@ def main():
     tok = IdTokenizer(cfg.vocab_size)
     eng = InferenceEngine(tensors, cfg, dtype, quantize, tokenizer=tok)
     del tensors
+    if args.sampled:
+        return sampled_main(args, eng, cfg, dtype, quantize, tok, dev)
     T = args.tokens
     max_new = T + 16  # every timed step keeps K + 1 tokens in hand
     pages = max(BS) * PagedKVCache.pages_for(CTX + max_new) + 8
