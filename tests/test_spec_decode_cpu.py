@@ -172,7 +172,7 @@ def _host_lm(K, N=3):
 def _spec_batch(lens, K, hits, cache, max_new=40):
     b = _batch(lens, max_new)
     _after_prefill(b, cache)
-    b.spec_tokens, b.spec_ngram = K, 3
+    b.spec_tokens = K
     b.spec_drafts = torch.zeros((len(lens), K), dtype=torch.int64)
     b.spec_hits = torch.tensor(hits, dtype=torch.int32)
     return b
@@ -230,6 +230,96 @@ def test_a_sampling_request_keeps_the_batch_on_the_plain_step():
     assert lm._grow_for_verify(s) is False and lm.spec_stats()["fallback_not_greedy"] == 1
     b.release()
     s.release()
+
+
+# ---- the batch and its drafter ------------------------------------------------------------------------------------------------
+class _RecordingDrafter:
+    """The three methods of a drafter (models/speculation.py); `redraft` records what the batch looked like when called and
+    drafts the way a drafter must: the batch's own buffers, and renewed."""
+
+    def __init__(self):
+        self.calls = []
+
+    def redraft(self, batch):
+        self.calls.append((batch, batch.spec_drafts, batch.spec_hits))
+        batch.ensure_spec_buffers()
+        batch.drafts_renewed()
+
+
+class _CountedHits:
+    """A `spec_hits` stand-in that counts how often the batch reads it to the host."""
+
+    def __init__(self, hits):
+        self.hits, self.reads = hits, 0
+
+    def tolist(self):
+        self.reads += 1
+        return list(self.hits)
+
+
+def _decode_form(b):
+    """What the prefill's bookkeeping leaves: one id, one position per request."""
+    B = len(b)
+    b.cu_seqlens_q = torch.arange(B + 1, dtype=torch.int32)
+    b.position_ids = torch.tensor([n - 1 for n in b.input_lengths])
+    b.input_ids = torch.arange(B, dtype=torch.int64) + 7
+    return b
+
+
+def _drafted_batch(cache, drafter, hidden=None, first_id=0):
+    b = _decode_form(_spec_batch([30, 12], 3, [0, 0], cache))
+    for i, r in enumerate(b.requests):
+        r.id = first_id + i
+    b.spec_model, b.spec_hidden = drafter, hidden
+    return b
+
+
+def test_stale_drafts_are_drafted_anew_once_when_the_hits_are_asked_for():
+    c = PagedKVCache(1, 1, 64, 8, torch.float16, CPU)
+    d = _RecordingDrafter()
+    b = _drafted_batch(c, d)
+    first = b.spec_hits = _CountedHits([0, 2])
+    b.drafts_are_stale()
+    assert d.calls == [] and first.reads == 0, "marking drafts stale drafts nothing"
+    assert b.spec_hits_host() == [0, 2] and len(d.calls) == 1 and d.calls[0][0] is b
+    assert b.spec_hits_host() == [0, 2] and len(d.calls) == 1 and first.reads == 1, "neither drafted nor read twice"
+    second = b.spec_hits = _CountedHits([3, 0])
+    assert b.spec_hits_host() == [3, 0] and b.spec_hits_host() == [3, 0]
+    assert second.reads == 1 and first.reads == 1 and len(d.calls) == 1, "a new tensor is read again, once, without a redraft"
+    b.release()
+
+
+def test_prune_drafts_anew_on_dropped_buffers_and_keeps_the_kept_rows_state():
+    c = PagedKVCache(1, 1, 64, 8, torch.float16, CPU)
+    d = _RecordingDrafter()
+    hidden = torch.arange(8, dtype=torch.float16).reshape(2, 4)
+    b = _drafted_batch(c, d, hidden.clone())
+    kept = FlashCausalLMBatch.prune(b, [0])
+    assert kept is b and [r.id for r in b.requests] == [1]
+    assert len(d.calls) == 1 and d.calls[0] == (b, None, None), "one redraft, on a batch whose drafts and hits were dropped"
+    assert b.spec_drafts.shape == (1, 3) and b.spec_hits.shape == (1,)
+    assert torch.equal(b.spec_hidden, hidden[1:2]), "the kept request's state is carried over"
+    # the lookup's batches have no state to carry
+    b2 = _drafted_batch(c, d, None, first_id=2)
+    FlashCausalLMBatch.prune(b2, [3])
+    assert len(d.calls) == 2 and d.calls[1] == (b2, None, None) and b2.spec_hidden is None
+    b.release()
+    b2.release()
+    assert c.free_pages == c.num_pages
+
+
+def test_concatenate_drafts_anew_once_on_the_merged_batch():
+    c = PagedKVCache(1, 1, 64, 8, torch.float16, CPU)
+    d = _RecordingDrafter()
+    ha, hb = torch.arange(8, dtype=torch.float16).reshape(2, 4), 10 + torch.arange(8, dtype=torch.float16).reshape(2, 4)
+    a, b = _drafted_batch(c, d, ha.clone()), _drafted_batch(c, d, hb.clone(), first_id=2)
+    m = FlashCausalLMBatch.concatenate([a, b])
+    assert len(d.calls) == 1 and d.calls[0] == (m, None, None), "one redraft, on the merged batch"
+    assert [r.id for r in m.requests] == [0, 1, 2, 3] and m.spec_tokens == 3 and m.spec_model is d
+    assert torch.equal(m.spec_hidden, torch.cat([ha, hb])), "the states in request order"
+    assert m.spec_drafts.shape == (4, 3) and m.spec_hits.shape == (4,)
+    m.release()
+    assert c.free_pages == c.num_pages
 
 
 # ---- the restatement, on cases written out by hand ----------------------------------------------------------------------------

@@ -459,3 +459,30 @@ def test_lookups_alone_speed_a_repeating_request_up(gpu_device):
     assert run.ids[3] == want[3] == [21] * 6
     st = lm.spec_stats()
     assert st["verify_steps"] >= 1 and st["accepted"] >= 1 and st["decode_steps"] < 5, st
+
+
+def test_stale_lookups_are_drafted_anew_once_the_batch_turns_greedy(gpu_device):
+    """The same request with min_new_tokens = 3: below it the EOS mask keeps the batch off the plain-greedy path, the steps
+    are plain and leave the drafts stale; the first greedy step drafts anew from the context before it looks at the hits,
+    and the cycle is verified as above.  Every id and logprob is the one the option off gives.
+    The request may have 3 + K + 1 = 7 tokens, one more than the fixture's 6: with 6, the first greedy step has K tokens
+    left, one short of what a verify step needs (`fallback_remaining`), and no request of that fixture could verify."""
+    meta, _steps = load_fixture("llama_dense_ragged")
+    cfg = _fixture_cfg(meta)
+    tensors = tiny_llama_tensors(cfg, seed=meta["seed"], quantize=None, groupsize=meta["groupsize"])
+    runs = []
+    for spec in (0, K):
+        lm, tok = _llama(tensors, cfg, None, spec, ngram=1)
+        request = _request(3, meta["prompts"][3], 3 + K + 1)
+        request.parameters.min_new_tokens = 3
+        run = Runner(lm, tok)
+        run.run(run.batch([request]))
+        runs.append((lm, run))
+    (lm0, off), (lm, on) = runs
+    print(f"\n[stale then redraft] ids {on.ids[3]} / {off.ids[3]}, max |logprob on - off| = "
+          f"{max(abs(a - b) for a, b in zip(on.lps[3], off.lps[3])):.3g}, {lm.spec_stats()}")
+    assert on.ids == off.ids and on.lps == off.lps and on.ids[3][:6] == [21] * 6
+    assert lm0.spec_stats() == dict.fromkeys(lm0.spec_stats(), 0)
+    st = lm.spec_stats()
+    assert st["fallback_not_greedy"] >= 1, st
+    assert st["verify_steps"] >= 1 and st["accepted"] >= 1, st

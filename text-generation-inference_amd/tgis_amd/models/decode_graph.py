@@ -1,6 +1,7 @@
 """The captured decode step of FlashCausalLM: static buffers + HIP graph per (batch-size bucket, table width), the choice
 between one graph and a chain of segments under tensor parallelism, and the memory pool the captures share.  With
-speculative decoding on (utils/spec_decode.py) the verify step is captured the same way, per (bucket, table width, K).
+speculative decoding on (utils/spec_decode.py) the verify step is captured the same way, per (bucket, table width, K); what
+drafts and what follows such a step is models/speculation.py.
 
 The state stays on the model, where bench.py, the tests and tools/ read and set it: `lm._graphs`, `lm.graph_captures`,
 `lm.use_graphs`, `lm.max_graphs`, `lm.graph_mode`, `lm.graph_pool`, `lm.tp_world`, `lm.ranks` (utils/rank_group.py)."""
@@ -92,52 +93,6 @@ class _SpecOut:
                 hits[:n].tolist())
 
 
-class _DraftChain:
-    """The MLP drafter's launches behind one captured step, as a captured graph of their own: it reads that step's static
-    `hidden`, `spec_out.n_emit` and `input_ids` (where tgis_spec_accept left the new latest ids) and writes buffers of its
-    own, for every row of the bucket.  A row past the batch drafts from what the inactive row computed and token 0; nobody
-    reads its drafts.  The chain belongs to its step graph: it is no key of `lm._graphs`, it goes when that graph is
-    evicted, and its capture time is added to that graph's `graph_captures` entry."""
-
-    def __init__(self, g):
-        spec = g.lm.speculator
-        dev = g.lm.device
-        self.g = g
-        self.bufs = spec.buffers(g.rows)
-        self.raw = torch.zeros((g.rows, spec.cfg.emb_dim), dtype=g.hidden.dtype, device=dev)
-        self.drafts = torch.zeros((g.rows, spec.K), dtype=torch.int64, device=dev)
-        self.hits = torch.zeros(g.rows, dtype=torch.int32, device=dev)
-        self.graph = None
-
-    def _launch(self):
-        g = self.g
-        native.spec_mlp_input(g.hidden, g.spec_out.n_emit, g.K + 1, self.raw)
-        g.lm.speculator.draft(self.raw, g.input_ids, self.drafts, self.hits, hits_copy=g.spec_out.hits, bufs=self.bufs)
-
-    def run(self, batch):
-        g, lm = self.g, self.g.lm
-        if self.graph is None:
-            t_capture = time.perf_counter()
-            self._launch()  # warm-up: sizes the GEMM workspace outside the capture (and drafts for real, once)
-            torch.cuda.current_stream().synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with no_gc_during_capture(), torch.cuda.graph(graph, pool=lm.graph_pool):
-                self._launch()
-            self.graph = graph
-            caps, ms = lm.graph_captures, (time.perf_counter() - t_capture) * 1e3
-            for i in range(len(caps) - 1, -1, -1):
-                if caps[i] is g._capture_entry:
-                    r, w, t, k = caps[i]
-                    caps[i] = g._capture_entry = (r, w, t + ms, k)
-                    break
-        self.graph.replay()
-        B = len(batch)
-        # the batch's own tensors: another batch may run this graph next
-        batch.spec_drafts.copy_(self.drafts[:B])
-        batch.spec_hits.copy_(self.hits[:B])
-        batch.spec_hidden.copy_(self.raw[:B])
-
-
 class _DecodeGraph:
     """Static buffers + captured HIP graph of one decode step for a (batch-size bucket, table width) pair."""
 
@@ -150,7 +105,7 @@ class _DecodeGraph:
         self.cu_q = torch.arange(B + 1, dtype=torch.int32, device=dev)
         self.num_splits = native.attn_num_splits(B, lm.num_kv_heads, lm.num_heads, 1, self.max_ctx)
         # a speculating model's plain steps report through tgis_spec_accept (K = 0) too: the next lookup's hits ride along
-        self.spec_out = _SpecOut(B, 0, dev) if getattr(lm, "spec_tokens", 0) else None
+        self.spec_out = _SpecOut(B, 0, dev) if lm.spec_tokens else None
 
     def _init_buffers(self, lm, B: int, width: int, R: int):
         """What the plain and the verify step share: the per-request inputs, and R rows of slots and greedy outputs."""
@@ -175,32 +130,17 @@ class _DecodeGraph:
         # whose next-step inputs the static buffers already hold (tgis_decode_advance wrote them): identity of the
         # batch's tensors, so that a pruned / concatenated / other batch always stages its own
         self.staged_ids = self.staged_pos = self.staged_bt = None
-        # an MLP drafter (utils/mlp_speculator.py) reads the rows that went into lm_head: `hidden` [R, E] is what the latest
-        # step left there, `_static_hidden` the tensor the captured step writes; `chain` drafts behind this step
+        # a drafter that needs them (models/speculation.py) reads the rows that went into lm_head: `hidden` [R, E] is what the
+        # latest step left there, `_static_hidden` the tensor the captured step writes; `chain` is the drafter's, its launches
+        # behind this step as a captured graph that goes with this one
         self.hidden = self._static_hidden = self.chain = self._capture_entry = None
 
     def _forward(self, ids, positions, kv):
         lm = self.lm
-        if getattr(lm, "speculator", None) is None:
+        if lm.drafter is None or not lm.drafter.needs_hidden:
             return lm.model.forward(ids, positions, self.cu_q, self.max_ctx, None, kv)
         logits, self.hidden = lm.model.forward(ids, positions, self.cu_q, self.max_ctx, None, kv, return_embeds=True)
         return logits
-
-    def draft_next(self, batch, latest_ids):
-        """MLP drafter, behind tgis_spec_accept of this step: the state behind each request's last emitted token into
-        `batch.spec_hidden`, the next step's drafts into `batch.spec_drafts`, ones into `batch.spec_hits` and the hits
-        that travel to the host.  Captured with the step it follows, launched one by one otherwise."""
-        lm, B = self.lm, len(batch)
-        batch.ensure_spec_buffers(lm.speculator.cfg.emb_dim, self.hidden.dtype)
-        if lm.use_graphs and self.graph is not None:
-            if self.chain is None:
-                self.chain = _DraftChain(self)
-            self.chain.run(batch)
-        else:
-            out = self.spec_out
-            native.spec_mlp_input(self.hidden, out.n_emit[:B], self.K + 1, batch.spec_hidden)
-            lm.speculator.draft(batch.spec_hidden, latest_ids, batch.spec_drafts, batch.spec_hits, hits_copy=out.hits[:B])
-        batch.drafts_renewed()
 
     def fetch_greedy(self):
         """ids and logprobs of the step that just ran, as host lists: one device->host copy, one wait."""

@@ -18,7 +18,7 @@ import logging
 import os
 import time
 from collections import OrderedDict, deque
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from operator import itemgetter
 from typing import Any, List, Optional, Tuple, Type, Union
 
@@ -29,6 +29,7 @@ from tgis_amd import native
 from tgis_amd.models.custom_modeling.flash_common import KVArgs
 from tgis_amd.models.decode_graph import _DecodeGraph, _VerifyGraph, renew_unheld_pool
 from tgis_amd.models.model import Model
+from tgis_amd.models.speculation import LookupDrafter, MLPDrafter, spec_step
 from tgis_amd.models.types import Batch, GenerateError
 from tgis_amd.pb import generate_pb2
 from tgis_amd.utils import mlp_speculator
@@ -77,16 +78,21 @@ class FlashCausalLMBatch(Batch):
     # only consumer; and, from `allocate_pages`, how many leading tokens of each request sit on pages it shares
     prompt_token_ids: Optional[List[List[int]]] = None
     reused_lengths: Optional[List[int]] = None
-    # speculative decoding (utils/spec_decode.py), set by the prefill of a model that has it on: K and N, and on the device
-    # the K tokens drafted for each request's next step [B, K] and the suffix length their lookup matched [B] (0 = none)
+    # speculative decoding (models/speculation.py), set by the prefill of a model that has it on: K, the model's drafter, and
+    # on the device the K tokens drafted for each request's next step [B, K] and the suffix length their lookup matched [B]
+    # (0 = none; an MLP drafter's are all ones)
     spec_tokens: int = 0
-    spec_ngram: int = 0
+    spec_model: Optional[Any] = None
     spec_drafts: Optional[torch.Tensor] = None
     spec_hits: Optional[torch.Tensor] = None
-    # an MLP drafter (utils/mlp_speculator.py) in place of the lookup: the speculator, and per request the post-norm hidden
-    # state that predicted its latest token [B, E] — the reference's `batch.embeds` (paged_causal_lm.py:192,261)
-    spec_model: Optional[Any] = None
+    # with a drafter that needs it (the MLP speculator): per request the post-norm hidden state that predicted its latest
+    # token [B, E] — the reference's `batch.embeds` (paged_causal_lm.py:192,261)
     spec_hidden: Optional[torch.Tensor] = None
+    # (spec_hits, its host list) as last read or noted, and whether a step left the drafts stale (`spec_hits_host`)
+    _spec_seen: Optional[tuple] = field(default=None, repr=False)
+    _spec_stale: bool = field(default=False, repr=False)
+    # the host copy of `block_tables` (`_rebuild_block_tables`), which `grow_pages` edits and uploads again
+    _bt_host: Optional[np.ndarray] = field(default=None, repr=False)
 
     def get_id(self) -> int:
         return self.batch_id
@@ -152,7 +158,7 @@ class FlashCausalLMBatch(Batch):
         for i in short:
             self.pages[i].extend(next(flat) for _ in range(need[i]))
         width = self.block_tables.shape[1]
-        if max(len(self.pages[i]) for i in short) > width or getattr(self, "_bt_host", None) is None:
+        if max(len(self.pages[i]) for i in short) > width or self._bt_host is None:
             self._rebuild_block_tables()
         else:  # edit the host copy and upload the few KB again (the same copy the prefill made: nothing new to load)
             for i in short:
@@ -161,20 +167,15 @@ class FlashCausalLMBatch(Batch):
             self.block_tables = torch.from_numpy(self._bt_host).to(self.block_tables.device, non_blocking=True)
 
     # ---- speculative decoding ---------------------------------------------------------------------
-    def propose_drafts(self, hits_copy: Optional[torch.Tensor] = None):
-        """Drafts for the next step of every request: after the prefill, after every greedy step, and after concatenate /
-        prune rebuilt the tensors the drafter reads.  Looked up in the request's own context (tgis_spec_propose), or, with
-        an MLP drafter, predicted from `spec_hidden` and the latest ids (`input_ids`).  A no-op with the option off."""
-        if not self.spec_tokens:
-            return
-        B = len(self)
-        self.ensure_spec_buffers()
-        if self.spec_model is None:
-            native.spec_propose(self.all_input_ids_tensor, self.position_ids, self.spec_ngram, self.spec_drafts,
-                                self.spec_hits, hits_copy)
-        elif may_ever_verify(self.spec_tokens, graph_bucket(B)):  # (else the step rule answers `rows`: nobody reads drafts)
-            self.spec_model.draft(self.spec_hidden, self.input_ids, self.spec_drafts, self.spec_hits, hits_copy)
-        self.drafts_renewed()
+    def redraft(self):
+        """Drafts anew from the batch's own tensors: concatenate and prune rebuilt what the drafter reads, or a step left
+        the drafts stale.  A no-op with the option off."""
+        if self.spec_tokens:
+            self.spec_model.redraft(self)
+
+    def can_verify(self) -> bool:
+        """Whether a batch of this size can verify at all (its bucket times K + 1 rows): if not, nobody drafts for it."""
+        return may_ever_verify(self.spec_tokens, graph_bucket(len(self)))
 
     def ensure_spec_buffers(self, emb_dim: int = 0, dtype=None):
         """The batch's own `spec_drafts` / `spec_hits` for its present size (and `spec_hidden`, given its width)."""
@@ -198,10 +199,10 @@ class FlashCausalLMBatch(Batch):
         """`spec_hits` on the host.  A greedy step brings them along in its one copy (`note_spec_hits`); only a tensor the
         batch has not seen yet is fetched: after a prefill, concatenate or prune, or one a caller put in its place (whoever
         wants other drafts verified assigns new `spec_drafts` / `spec_hits` tensors rather than writing into these)."""
-        if getattr(self, "_spec_stale", False):
-            self.propose_drafts()
+        if self._spec_stale:
+            self.redraft()
         t = self.spec_hits
-        seen = getattr(self, "_spec_seen", None)
+        seen = self._spec_seen
         if seen is None or seen[0] is not t:
             seen = self._spec_seen = (t, t.tolist())
         return seen[1]
@@ -355,9 +356,8 @@ class FlashCausalLMBatch(Batch):
             max_seqlen=max_seqlen, past_key_values=None, input_lengths=input_lengths,
             total_lengths=total_lengths, all_input_ids_tensor=all_input_ids_tensor,
             next_token_chooser=next_token_chooser, pad_token_id=first.pad_token_id,
-            kv_cache=first.kv_cache, pages=None, spec_tokens=first.spec_tokens, spec_ngram=first.spec_ngram,
-            spec_model=first.spec_model,
-            spec_hidden=torch.cat([b.spec_hidden for b in batches]) if first.spec_model is not None else None)
+            kv_cache=first.kv_cache, pages=None, spec_tokens=first.spec_tokens, spec_model=first.spec_model,
+            spec_hidden=torch.cat([b.spec_hidden for b in batches]) if first.spec_hidden is not None else None)
         merged.pages = pages
         try:
             merged._rebuild_block_tables()
@@ -367,7 +367,7 @@ class FlashCausalLMBatch(Batch):
         for batch in batches:
             batch.pages = None
             batch.block_tables = None
-        merged.propose_drafts()
+        merged.redraft()
         return merged
 
     @classmethod
@@ -407,7 +407,7 @@ class FlashCausalLMBatch(Batch):
         batch.spec_drafts = batch.spec_hits = None
         if batch.spec_hidden is not None:
             batch.spec_hidden = batch.spec_hidden[keep_indices]
-        batch.propose_drafts()
+        batch.redraft()
         return batch
 
 
@@ -433,9 +433,10 @@ def graph_bucket(B: int) -> int:
 
 
 class FlashCausalLM(Model):
-    # the drafter of speculative decoding: the prompt lookup, or an MLP speculator on the device (set by the constructor)
+    # the drafter of speculative decoding (models/speculation.py; set by the constructor): None with the option off, else the
+    # prompt lookup or the MLP speculator on the device, which is then `speculator` too
     spec_drafter = "lookup"
-    speculator = None
+    drafter = speculator = None
     # whether batches that sample or carry processors verify drafts too (set by the constructor)
     spec_sampling = False
 
@@ -468,17 +469,9 @@ class FlashCausalLM(Model):
         # lookup; None reads TGIS_SPECULATOR, unset = the lookup.  It needs spec_tokens in 1 .. min(n_predict, 7) and ignores
         # spec_ngram.  Its config, tensor names and shapes are checked here, before any weight is on the device.
         # (tools hand over a checkpoint they made in memory, a mlp_speculator.SpeculatorCheckpoint, in place of the directory)
-        spec_ckpt = speculator if isinstance(speculator, mlp_speculator.SpeculatorCheckpoint) else None
-        spec_path = mlp_speculator.parse_speculator(speculator) if spec_ckpt is None else None
-        if spec_path is not None:
-            spec_ckpt = mlp_speculator.open_checkpoint(spec_path)
-        if spec_ckpt is not None:
-            mlp_speculator.check_spec_tokens(spec_ckpt.cfg, self.spec_tokens)
-            base = getattr(engine, "_config", None)
-            if base is not None:  # (an engine built here is checked below, as soon as its config is read)
-                mlp_speculator.check_base(spec_ckpt.cfg, base.hidden_size, base.vocab_size)
+        # (an engine built here is checked against the base model below, as soon as its config is read)
+        spec_ckpt = mlp_speculator.checked_checkpoint(speculator, self.spec_tokens, getattr(engine, "_config", None))
         self.spec_drafter = "lookup" if spec_ckpt is None else "mlp"
-        self.speculator = None
         # kv_scales: the calibrated per-layer scales of a one-byte cache, the contents of a kv_cache_scales.json or its path
         # (utils/kv_cache.py, resolve_kv_scales); None looks at TGIS_KV_SCALES, then next to the weights, else they stay 1.0
         if not torch.cuda.is_available():
@@ -519,7 +512,9 @@ class FlashCausalLM(Model):
         if spec_ckpt is not None:
             # before the pool is sized: the speculator's bytes come out of the page budget
             mlp_speculator.check_base(spec_ckpt.cfg, self.config.hidden_size, self.config.vocab_size)
-            self.speculator = mlp_speculator.MLPSpeculator(spec_ckpt, self.spec_tokens, dtype, self.device)
+            self.drafter = self.speculator = MLPDrafter(spec_ckpt, self.spec_tokens, dtype, self.device)
+        elif self.spec_tokens:
+            self.drafter = LookupDrafter(self.spec_tokens, self.spec_ngram)
         self.kv_cache_dtype = agree_kv_cache_dtype(self.ranks, kv_cache_dtype)
         self.kv_prefix_reuse = agree_kv_prefix_reuse(self.ranks, kv_prefix_reuse)
         if kv_cache_pages is None:
@@ -627,7 +622,7 @@ class FlashCausalLM(Model):
         if self.spec_tokens and not first and logging.getLogger().isEnabledFor(logging.DEBUG):
             spec_before = self.spec_stats()
         if first:
-            out, fused = self._prefill_forward(batch), None
+            (out, embeds), fused = self._prefill(batch), None
         else:
             out, fused = self._decode_forward(batch)
         forward_time_ns = time.time_ns() - start_time
@@ -642,21 +637,21 @@ class FlashCausalLM(Model):
         # addition on the device already (tgis_decode_advance)
         if first:
             batch.cu_seqlens.add_(batch.cu_seqlens_q)
-        batch.max_seqlen += 1
-        if self.spec_tokens:
-            batch.max_seqlen = max(batch.input_lengths)  # a verify step adds up to K + 1 tokens to a request
-            if first:
-                batch.spec_tokens, batch.spec_ngram = self.spec_tokens, self.spec_ngram
-                if self.speculator is not None:
-                    batch.spec_model, batch.spec_hidden = self.speculator, self._prefill_hidden(batch)
-                batch.propose_drafts()
-            if spec_before is not None:
-                after = self.spec_stats()
-                logging.debug("speculative decoding, batch %s: %s", batch.batch_id,
-                              {k: after[k] - spec_before[k] for k in after})
+        batch.max_seqlen = max(batch.input_lengths)  # one more token; a verify step adds up to K + 1 to a request
+        if first and self.spec_tokens:
+            self.drafter.start(batch, embeds)
+        if spec_before is not None:
+            after = self.spec_stats()
+            logging.debug("speculative decoding, batch %s: %s", batch.batch_id,
+                          {k: after[k] - spec_before[k] for k in after})
         return generated_tokens, input_token_infos, decode_errors, forward_time_ns
 
     def _prefill_forward(self, batch: FlashCausalLMBatch):
+        """The prompts' logits alone."""
+        return self._prefill(batch)[0]
+
+    def _prefill(self, batch: FlashCausalLMBatch):
+        """(logits, the rows that went into lm_head if the drafter needs them, else None) of the batch's prompts."""
         before = self.kv_cache.reuse_stats() if self.kv_prefix_reuse else None
         batch.allocate_pages(self.kv_cache)
         self._need_all_logits = any(r.details.input_toks for r in batch.requests)
@@ -698,21 +693,11 @@ class FlashCausalLM(Model):
                                      kv, (cu_q[1:] - 1).long())
 
     def _forward_prefill(self, *args):
-        """The model's forward; with an MLP drafter it also keeps the rows that went into lm_head (`return_embeds`)."""
-        self._embeds = None
-        if self.speculator is None:
-            return self.model.forward(*args)
-        logits, self._embeds = self.model.forward(*args, return_embeds=True)
-        return logits
-
-    def _prefill_hidden(self, batch: FlashCausalLMBatch) -> torch.Tensor:
-        """[B, E]: the state behind each prompt's last token, the batch's own tensor (`batch.spec_hidden`)."""
-        embeds, self._embeds = self._embeds, None
-        if embeds.shape[0] != len(batch):  # details.input_toks: every prompt position went through lm_head
-            ends = np.cumsum([n - 1 for n in batch.input_lengths]) - 1  # (input_lengths count the generated token by now)
-            embeds = embeds.index_select(0, torch.from_numpy(ends).to(embeds.device))
-        out = torch.empty((len(batch), embeds.shape[1]), dtype=embeds.dtype, device=embeds.device)
-        return native.spec_mlp_input(embeds.contiguous(), None, 1, out)
+        """(logits, hidden rows or None): the model's forward; a drafter that needs them also gets the rows that went into
+        lm_head (`return_embeds`)."""
+        if self.drafter is not None and self.drafter.needs_hidden:
+            return self.model.forward(*args, return_embeds=True)
+        return self.model.forward(*args), None
 
     def _prefill_fresh_forward(self, batch: FlashCausalLMBatch):
         lens = batch.input_lengths
@@ -805,27 +790,26 @@ class FlashCausalLM(Model):
 
         ntc = batch.next_token_chooser
         details = any(r.details.top_n_toks or r.details.ranks for r in batch.requests)
-        simple = ntc.is_plain_greedy and not details
-        graph = fused[2] if fused is not None else None
+        plain_greedy = ntc.is_plain_greedy
+        simple = plain_greedy and not details
+        graph = None if prefill else fused[2]  # the prefill is the one caller without a captured step
         if self.spec_tokens and not prefill:
             self._spec_stats["emitted"] += len(batch)  # (a verify step adds the drafts it accepted)
-            if graph is not None and batch.spec_hits is not None:
-                if simple:
-                    return self._process_spec_tokens(batch, fused, generated_tokens, decode_errors)
-                if self.spec_sampling and not details:
-                    # verify or plain (K = 0): the fused chooser behind every row in place of the captured argmax
-                    return self._process_spec_tokens(batch, fused, generated_tokens, decode_errors, logits=logits)
+            if batch.spec_hits is not None and not details and (plain_greedy or self.spec_sampling):
+                # verify or plain (K = 0).  spec_sampling: the fused chooser behind every row in place of the captured argmax
+                return spec_step(self, batch, fused, generated_tokens, logits=None if plain_greedy else logits)
         read_host = None
-        if simple:
-            # one kernel (already part of the decode graph), one device->host copy for the whole batch
-            next_token_ids, next_logprobs = fused[:2] if fused is not None else ntc.choose_greedy_fused(logits)
-            if graph is not None:
-                read_host = graph.fetch_greedy()  # the copy is on its way while the bookkeeping launch below runs
-        else:
+        if not simple:
             # EOS mask / length penalty, repetition penalty, warpers, argmax or draw, log-softmax at the chosen id:
             # one launch (tgis_warp_sample) and, below, one device->host copy for the whole batch
             next_token_ids, next_logprobs, lse, next_token_scores = ntc.choose_fused(
                 batch.all_input_ids_tensor[:, :batch.max_seqlen], logits)
+        elif prefill:
+            next_token_ids, next_logprobs = ntc.choose_greedy_fused(logits)
+        else:
+            # one kernel (already part of the decode graph), one device->host copy for the whole batch
+            next_token_ids, next_logprobs = fused[:2]
+            read_host = graph.fetch_greedy()  # the copy is on its way while the bookkeeping launch below runs
 
         if prefill:
             batch.all_input_ids_tensor.scatter_(dim=1, index=batch.position_ids[:, None], src=next_token_ids[:, None])
@@ -835,16 +819,10 @@ class FlashCausalLM(Model):
             # buffers of the graph that will run it
             next_token_ids = native.decode_advance(
                 next_token_ids, batch.position_ids, batch.all_input_ids_tensor, batch.cu_seqlens, batch.cu_seqlens_q,
-                stage_ids=graph.input_ids[:len(batch)] if graph is not None else None,
-                stage_positions=graph.positions[:len(batch)] if graph is not None else None)
-            if graph is not None:
-                graph.staged_ids, graph.staged_pos = next_token_ids, batch.position_ids
+                stage_ids=graph.input_ids[:len(batch)], stage_positions=graph.positions[:len(batch)])
+            graph.staged_ids, graph.staged_pos = next_token_ids, batch.position_ids
             if self.spec_tokens:  # (a batch below its min_new_tokens turns plain greedy without being rebuilt)
-                if self.speculator is not None and graph is not None:
-                    # a step whose chooser samples (or reports details) still leaves the state behind its token
-                    batch.ensure_spec_buffers(graph.hidden.shape[1], graph.hidden.dtype)
-                    native.spec_mlp_input(graph.hidden, None, 1, batch.spec_hidden)
-                batch.drafts_are_stale()
+                self.drafter.after_step(batch, graph, next_token_ids, None, 1, None, False)
 
         if read_host is not None:
             ids_host, lps_host = read_host(any(ntc.return_logprobs))
@@ -870,68 +848,6 @@ class FlashCausalLM(Model):
                 decode_errors.append(GenerateError(request_id=request.id,
                                                    message=f"Token decoding error: {str(e)}"))
             batch.input_lengths[i] += 1
-        return next_token_ids
-
-    def _process_spec_tokens(self, batch: FlashCausalLMBatch, fused, generated_tokens: List[TokenInfo],
-                             decode_errors: List[GenerateError], logits: Optional[torch.Tensor] = None):
-        """What follows a decode step of a speculating model, verify (K drafts per request) or plain (K = 0): one launch
-        accepts and does the bookkeeping of `_process_new_tokens` for up to K + 1 tokens per request (tgis_spec_accept),
-        one drafts the next step (tgis_spec_propose), one copy brings ids, logprobs, counts and the lookup's hits to the
-        host.  Request i contributes n_emit[i] TokenInfos, in order.
-        logits: None for a plain-greedy batch, whose rows the captured argmax chose.  Otherwise (spec_sampling) the step's
-        logits [B (K + 1), V]: the fused chooser chooses behind every row as the plain step of that position would
-        (tgis_warp_sample_verify: the request's parameters, its context plus the drafts in front of the row, the draw
-        (seed, offset + j)), a draft is accepted while the chosen token equals it — for a deterministic drafter the
-        rejection rule, accept with probability p(draft) — and tgis_spec_accept_sampled also advances each sampled
-        request's stream by what it emitted."""
-        ids, lps, graph = fused
-        B, K, K1, out = len(batch), graph.K, graph.K + 1, graph.spec_out
-        ntc = batch.next_token_chooser
-        outputs = dict(out_ids=out.ids[:B * K1], out_logprobs=out.lps[:B * K1], all_input_ids=batch.all_input_ids_tensor,
-                       cu_seqlens=batch.cu_seqlens, stage_ids=graph.input_ids[:B], stage_positions=graph.positions[:B])
-        drafts = batch.spec_drafts if K else None
-        if logits is None:
-            next_token_ids = native.spec_accept(ids, lps, drafts, out.n_emit[:B], batch.position_ids, **outputs)
-        else:
-            ids, lps, _lse, _scores = ntc.choose_fused_verify(batch.all_input_ids_tensor[:, :batch.max_seqlen], logits,
-                                                              drafts, K)
-            do_sample, rng = ntc.fused_streams(logits.device)
-            next_token_ids = native.spec_accept_sampled(ids.view(-1), lps.view(-1), drafts, out.n_emit[:B],
-                                                        batch.position_ids, do_sample=do_sample, rng=rng, **outputs)
-        graph.staged_ids, graph.staged_pos = next_token_ids, batch.position_ids
-        drafting = may_ever_verify(self.spec_tokens, graph_bucket(B))
-        if self.speculator is not None:
-            # the state behind each request's last emitted token and (a bucket that can verify) the next drafts; the chain
-            # reads the latest ids tgis_spec_accept just wrote
-            if drafting:
-                graph.draft_next(batch, next_token_ids)
-            else:
-                batch.ensure_spec_buffers(graph.hidden.shape[1], graph.hidden.dtype)
-                native.spec_mlp_input(graph.hidden, out.n_emit[:B], K1, batch.spec_hidden)
-                batch.drafts_are_stale()
-        elif drafting:
-            batch.propose_drafts(hits_copy=out.hits[:B])
-        else:
-            batch.drafts_are_stale()
-        out.fetch()
-        want_lps = any(batch.next_token_chooser.return_logprobs)
-        ids_host, lps_host, n_emit, hits = out.read(B, want_lps)
-        if drafting:
-            batch.note_spec_hits(hits)
-        if logits is not None:
-            ntc.commit_verify(n_emit)
-        for i, request in enumerate(batch.requests):
-            for j in range(i * K1, i * K1 + n_emit[i]):
-                info = TokenInfo(request_id=request.id, token_id=ids_host[j])
-                if lps_host is not None and request.details.logprobs:
-                    info.logprob = lps_host[j]
-                generated_tokens.append(info)
-            batch.input_lengths[i] += n_emit[i]
-        if K:
-            st = self._spec_stats
-            st["drafted"] += K * B  # every request's K draft rows are verified, the zero drafts of a lookup that missed too
-            st["accepted"] += sum(n_emit) - B
-            st["emitted"] += sum(n_emit) - B
         return next_token_ids
 
     @staticmethod

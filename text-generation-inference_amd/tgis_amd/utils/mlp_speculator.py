@@ -172,6 +172,22 @@ def open_checkpoint(path: str) -> SpeculatorCheckpoint:
     return SpeculatorCheckpoint(cfg, shapes, load)
 
 
+def checked_checkpoint(speculator=None, spec_tokens: int = 0, base_config=None) -> Optional[SpeculatorCheckpoint]:
+    """The model's `speculator` option as a checked checkpoint, or None for the lookup: a checkpoint directory, a
+    SpeculatorCheckpoint made in memory (tools), or None, which reads TGIS_SPECULATOR.  Its config, tensor names and shapes,
+    spec_tokens and, given the base model's config, that model's sizes are checked; no tensor is loaded."""
+    ckpt = speculator if isinstance(speculator, SpeculatorCheckpoint) else None
+    if ckpt is None:
+        path = parse_speculator(speculator)
+        if path is None:
+            return None
+        ckpt = open_checkpoint(path)
+    check_spec_tokens(ckpt.cfg, spec_tokens)
+    if base_config is not None:
+        check_base(ckpt.cfg, base_config.hidden_size, base_config.vocab_size)
+    return ckpt
+
+
 @dataclass
 class _Head:
     proj: object   # native.DenseWeight [I, E or I]

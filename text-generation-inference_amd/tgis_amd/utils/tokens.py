@@ -267,27 +267,31 @@ class HeterogeneousNextTokenChooser:
         self._fused = p
         return p
 
-    def choose_fused(self, input_ids: torch.Tensor, scores: torch.Tensor):
-        """(ids int64 [B], logprob f32 [B] of the chosen id under the warped scores, lse f32 [B], warped scores
-        f32 [B, V]) by one launch of tgis_warp_sample; log_softmax(warped)[b] = warped[b] - lse[b]."""
+    def _fused_args(self, input_ids: torch.Tensor, scores: torch.Tensor, adj: dict, rows: Tuple[int, ...]):
+        """(fp32 contiguous logits, the keyword arguments) of a fused chooser launch: the processors' parameters and
+        `adj`, the EOS rule's {index into `rows`: (mode, factor)}, uploaded as eos_adjust f32 [*rows, 2] if there is any."""
         p = self._fused_params(scores.device)
-        adj = self._eos_adjustments()
         eos_adjust = None
         if adj:
-            host = torch.zeros((len(self.do_sample), 2), dtype=torch.float32)
+            host = torch.zeros(rows + (2,), dtype=torch.float32)
             for idx, a in adj.items():
-                host[idx, 0], host[idx, 1] = a
+                host[idx] = host.new_tensor(a)
             eos_adjust = host.to(scores.device, non_blocking=True)
         logits = scores if scores.dtype == torch.float32 else scores.float()
         if logits.stride(-1) != 1:
             logits = logits.contiguous()
-        out = native.warp_sample(
-            logits, temperature=p["temperature"], top_k=p["top_k"], top_p_cut=p["top_p_cut"],
-            typical_p=p["typical_p"], rep_penalty=p["rep_penalty"],
-            input_ids=input_ids if p["rep_penalty"] is not None else None, exclude_id=p["exclude_id"],
-            eos_adjust=eos_adjust, eos_id=self.eos_token_id if eos_adjust is not None else -1,
+        return logits, dict(
+            temperature=p["temperature"], top_k=p["top_k"], top_p_cut=p["top_p_cut"], typical_p=p["typical_p"],
+            rep_penalty=p["rep_penalty"], input_ids=input_ids if p["rep_penalty"] is not None else None,
+            exclude_id=p["exclude_id"], eos_adjust=eos_adjust, eos_id=self.eos_token_id if eos_adjust is not None else -1,
             do_sample=p["do_sample"], rng=p["rng"])
-        if p["rng"] is not None:  # host mirror of the offsets the kernel advanced
+
+    def choose_fused(self, input_ids: torch.Tensor, scores: torch.Tensor):
+        """(ids int64 [B], logprob f32 [B] of the chosen id under the warped scores, lse f32 [B], warped scores
+        f32 [B, V]) by one launch of tgis_warp_sample; log_softmax(warped)[b] = warped[b] - lse[b]."""
+        logits, kw = self._fused_args(input_ids, scores, self._eos_adjustments(), (len(self.do_sample),))
+        out = native.warp_sample(logits, **kw)
+        if kw["rng"] is not None:  # host mirror of the offsets the kernel advanced
             for s in self.choice.sampling_mapping.values():
                 s.offset += 1
         return out
@@ -299,23 +303,8 @@ class HeterogeneousNextTokenChooser:
         parameters, its context plus those drafts, the EOS rule j steps on, the draw (seed, offset + j).  One launch of
         tgis_warp_sample_verify; returns (ids [B, K + 1], logprobs [B, K + 1], lse [B, K + 1], warped scores).  Nothing
         of the chooser's state moves: `commit_verify` does that once the accepted count is known."""
-        p = self._fused_params(scores.device)
-        adj = self._eos_adjustments_verify(K)
-        eos_adjust = None
-        if adj:
-            host = torch.zeros((len(self.do_sample), K + 1, 2), dtype=torch.float32)
-            for (idx, j), a in adj.items():
-                host[idx, j, 0], host[idx, j, 1] = a
-            eos_adjust = host.to(scores.device, non_blocking=True)
-        logits = scores if scores.dtype == torch.float32 else scores.float()
-        if logits.stride(-1) != 1:
-            logits = logits.contiguous()
-        return native.warp_sample_verify(
-            logits, drafts if K else None, K, temperature=p["temperature"], top_k=p["top_k"], top_p_cut=p["top_p_cut"],
-            typical_p=p["typical_p"], rep_penalty=p["rep_penalty"],
-            input_ids=input_ids if p["rep_penalty"] is not None else None, exclude_id=p["exclude_id"],
-            eos_adjust=eos_adjust, eos_id=self.eos_token_id if eos_adjust is not None else -1,
-            do_sample=p["do_sample"], rng=p["rng"])
+        logits, kw = self._fused_args(input_ids, scores, self._eos_adjustments_verify(K), (len(self.do_sample), K + 1))
+        return native.warp_sample_verify(logits, drafts if K else None, K, **kw)
 
     def fused_streams(self, device):
         """(do_sample int32 [B], rng int64 [B, 2]) on the device, or (None, None) for a batch without sampled requests:
