@@ -69,9 +69,54 @@ def test_get_linear_dispatches_on_bits():
                   torch.ones((1, N), dtype=torch.float16), None, bits, K, bits == 4)
         lin = get_linear(bundle, None, "gptq")
         assert type(lin) is cls and (lin.height, lin.width) == (K, N)
-    lin8 = lin
-    # the models' duck typing must take the generic paths for 8 bits
-    assert not any(hasattr(lin8, a) for a in ("gate_up", "rope_heads", "wants_fragments")) and hasattr(lin8, "post_init")
+
+
+def _linear(kind, K=128, N=192):
+    from tgis_amd.utils.layers import get_linear
+
+    if kind == "dense":
+        return get_linear(torch.zeros((N, K), dtype=torch.float16), None, None)
+    bits = {"int4": 4, "int8": 8}[kind]
+    bundle = (torch.zeros((K * bits // 32, N), dtype=torch.int32), torch.zeros((1, N * bits // 32), dtype=torch.int32),
+              torch.ones((1, N), dtype=torch.float16), None, bits, K, bits == 4)
+    return get_linear(bundle, None, "gptq")
+
+
+def test_8bit_linears_offer_none_of_the_fused_forms(monkeypatch):
+    """The models must take their generic paths for 8 bits: through the Linear protocol an 8-bit linear refuses every fused
+    form.  The same questions to an int4 and a dense linear (kernels replaced by tests/cpu_backend.py, and a library that
+    would serve fragments) are answered with yes, so the refusals are the 8-bit class's own."""
+    from tests import cpu_backend
+    from tgis_amd import native
+    from tgis_amd.utils.layers import Linear
+
+    cpu_backend.install(monkeypatch)
+    monkeypatch.setattr(native, "gptq_fragments_ok", lambda M, w, act=0: True)
+    cases = [(rows, act) for rows in (1, 32, 64) for act in (0, 2, 3)]
+
+    lin8 = _linear("int8")
+    assert isinstance(lin8, Linear) and callable(lin8.post_init)
+    assert lin8.fuse_gate_up() is False
+    lin8.declare_rope_heads(1, 1, 64)
+    assert lin8.rope_handle is None and not any(lin8.rope_serves(rows) for rows in (1, 32, 64))
+    assert all(lin8.wants_fragments(rows, act) is False for rows, act in cases)
+    assert lin8.q_handle is None  # none of the questions needed the image
+
+    lin4 = _linear("int4")
+    assert lin4.fuse_gate_up() is True
+    lin4.declare_rope_heads(1, 1, 64)
+    lin4.post_init()
+    lin4.post_init()  # idempotent: the checkpoint tensors are gone after the first
+    assert lin4.rope_handle is not None and all(lin4.rope_serves(rows) for rows in (1, 32, 64))
+    assert not lin4.rope_serves(65)
+    assert all(lin4.wants_fragments(rows, act) is True for rows, act in cases) and not lin4.wants_fragments(65)
+
+    dense = _linear("dense")
+    assert dense.fuse_gate_up() is True and dense.prepared.flags == 1
+    dense.declare_rope_heads(1, 1, 64)
+    dense.post_init()
+    assert dense.rope_handle is not None and dense.rope_serves(32) and not dense.rope_serves(65)
+    assert all(dense.wants_fragments(rows, act) is False for rows, act in cases)  # fragment order is an int4 operand layout
 
 
 def _free_port():

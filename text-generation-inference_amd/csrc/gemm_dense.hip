@@ -9,6 +9,7 @@
 #include <type_traits>
 #include "common.h"
 #include "dispatch.h"
+#include "host_helpers.h"
 #include "dense_gemm_body.h"
 
 namespace {
@@ -269,7 +270,7 @@ extern "C" int tgis_dense_rope_ok(int64_t M, int64_t K, int64_t N, int64_t D) {
     // as tgis_gptq_rope_ok: the unsplit plan must still cover the chip — from 64 blocks on when they are one-tile blocks
     const DensePlan pl = plan_dense_rope(K, N, M);
     const int64_t blocks = cdiv64(cdiv64(N, 32), pl.TN);
-    static const int64_t min_blocks = getenv("TGIS_ROPE_MIN_BLOCKS") ? atoll(getenv("TGIS_ROPE_MIN_BLOCKS")) : 128;
+    const int64_t min_blocks = rope_min_blocks_env();
     return blocks >= (pl.TN == 1 ? std::min<int64_t>(min_blocks, 64) : min_blocks) ? 1 : 0;
 }
 

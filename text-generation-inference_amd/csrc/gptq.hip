@@ -13,11 +13,10 @@
 // Rows are pre-permuted by the act-order permutation when g_idx is not trivial.
 #include <stdlib.h>
 #include <algorithm>
-#include <numeric>
-#include <vector>
 #include <mutex>
 #include "common.h"
 #include "dispatch.h"
+#include "host_helpers.h"
 #include "gptq_gemm_body.h"
 #include "gptq_wide_body.h"
 
@@ -438,23 +437,8 @@ extern "C" int tgis_gptq_prepare(const int32_t* qweight, const int32_t* qzeros, 
     hipStream_t st = (hipStream_t)stream;
     const int32_t* perm_dev = nullptr;
     if (g_idx_host) {
-        bool trivial = true;
-        for (int64_t k = 0; k < K; ++k)
-            if (g_idx_host[k] != (int32_t)(k / gs)) { trivial = false; break; }
-        if (!trivial) {
-            TGIS_CHECK_ARG(perm_out, "tgis_gptq_prepare: act-order g_idx needs perm_out");
-            std::vector<int32_t> perm(K);
-            std::iota(perm.begin(), perm.end(), 0);
-            std::stable_sort(perm.begin(), perm.end(),
-                             [&](int32_t a, int32_t b) { return g_idx_host[a] < g_idx_host[b]; });
-            // every group must own exactly gs rows (true for GPTQ act-order checkpoints)
-            for (int64_t k = 0; k < K; ++k)
-                TGIS_CHECK_ARG(g_idx_host[perm[k]] == (int32_t)(k / gs),
-                               "tgis_gptq_prepare: g_idx groups are not of uniform size");
-            TGIS_CHECK_HIP(hipStreamSynchronize(st));
-            TGIS_CHECK_HIP(hipMemcpy(perm_out, perm.data(), K * sizeof(int32_t), hipMemcpyHostToDevice));
-            perm_dev = perm_out;
-        }
+        const int rc = gptq_act_order_perm("tgis_gptq_prepare", g_idx_host, perm_out, K, gs, st, &perm_dev);
+        if (rc != TGIS_OK) return rc;
     }
     PrepLayout p = prep_layout(K, N, groups);
     uint8_t* base = (uint8_t*)prepared;
@@ -842,8 +826,7 @@ extern "C" int tgis_gptq_gemm_f16(const void* x, int64_t ldx, const void* prepar
 
 // ---- qkv projection with the rotary embedding and the cache write in its epilogue ------------------------------------
 static int64_t rope_min_blocks(int64_t M) {
-    static const int64_t min_blocks = getenv("TGIS_ROPE_MIN_BLOCKS") ? atoll(getenv("TGIS_ROPE_MIN_BLOCKS")) : 128;
-    return M <= 32 ? std::min<int64_t>(min_blocks, 48) : min_blocks;
+    return M <= 32 ? std::min<int64_t>(rope_min_blocks_env(), 48) : rope_min_blocks_env();
 }
 
 extern "C" int tgis_gptq_rope_ok(int64_t M, int64_t K, int64_t N, int64_t groups, int act_order, int64_t D) {

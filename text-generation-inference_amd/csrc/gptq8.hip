@@ -3,10 +3,9 @@
 //
 // Replaces the Triton QuantLinear the reference gives 8-bit checkpoints (utils/gptq/quant_linear.py:130-192,259).
 #include <algorithm>
-#include <numeric>
-#include <vector>
 #include "common.h"
 #include "dispatch.h"
+#include "host_helpers.h"
 #include "gptq8_gemm_body.h"
 
 namespace gptq {
@@ -137,21 +136,8 @@ extern "C" int tgis_gptq8_prepare(const int32_t* qweight, const int32_t* qzeros,
     hipStream_t st = (hipStream_t)stream;
     const int32_t* perm_dev = nullptr;
     if (g_idx_host) {
-        bool trivial = true;
-        for (int64_t k = 0; k < K; ++k)
-            if (g_idx_host[k] != (int32_t)(k / gs)) { trivial = false; break; }
-        if (!trivial) {
-            TGIS_CHECK_ARG(perm_out, "tgis_gptq8_prepare: act-order g_idx needs perm_out");
-            std::vector<int32_t> perm(K);
-            std::iota(perm.begin(), perm.end(), 0);
-            std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return g_idx_host[a] < g_idx_host[b]; });
-            // every group must own exactly gs rows (true for GPTQ act-order checkpoints)
-            for (int64_t k = 0; k < K; ++k)
-                TGIS_CHECK_ARG(g_idx_host[perm[k]] == (int32_t)(k / gs), "tgis_gptq8_prepare: g_idx groups are not of uniform size");
-            TGIS_CHECK_HIP(hipStreamSynchronize(st));
-            TGIS_CHECK_HIP(hipMemcpy(perm_out, perm.data(), K * sizeof(int32_t), hipMemcpyHostToDevice));
-            perm_dev = perm_out;
-        }
+        const int prc = gptq_act_order_perm("tgis_gptq8_prepare", g_idx_host, perm_out, K, gs, st, &perm_dev);
+        if (prc != TGIS_OK) return prc;
     }
     const PrepLayout p = prep_layout(K, N, groups);
     uint8_t* base = (uint8_t*)prepared;

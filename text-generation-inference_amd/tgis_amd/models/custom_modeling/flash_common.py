@@ -93,14 +93,18 @@ def grow_max_positions(config, max_positions: int, max_s: int) -> int:
 
 
 class FlashForCausalLM:
-    """Tail of the three `*ForCausalLM` classes: `self.model` is the decoder stack, `self.lm_head` the output head and
-    `self.gptq_linears` the linears that are repacked after loading."""
+    """Tail of the three `*ForCausalLM` classes: `self.model` is the decoder stack, `self.lm_head` the output head,
+    `self.linears` the projections of the layers and `self.gptq_linears` the quantised ones among them."""
+
+    def collect_linears(self, layers):
+        """`layers`: per decoder layer, its projections (the tensor-parallel wrappers of utils/layers.py)."""
+        self.linears = [proj.linear for projections in layers for proj in projections]
+        self.gptq_linears = [lin for lin in self.linears if lin.quantized]
 
     def post_init(self):
-        """Repack every GPTQ linear for the kernels (the reference does this in serve(), server.py:334-358)."""
-        for lin in self.gptq_linears:
-            if lin.q_handle is None:
-                lin.post_init()
+        """Repack every linear for the kernels (the reference does this in serve(), server.py:334-358)."""
+        for lin in self.linears:
+            lin.post_init()
 
     @property
     def num_layers(self):

@@ -68,9 +68,8 @@ class LlamaConfig:
 
 
 def frag_rows(linear, rows: int, kv: "KVArgs", act: int = 0) -> bool:
-    """Decode step of <= 64 rows in front of an int4 linear that takes its operand in fragment order (native.FragAct)."""
-    return (kv.max_q_len == 1 and not kv.fresh_prefill and rows <= 64 and hasattr(linear, "wants_fragments")
-            and linear.wants_fragments(rows, act))
+    """Decode step of <= 64 rows in front of a linear that takes its operand in fragment order (native.FragAct)."""
+    return kv.max_q_len == 1 and not kv.fresh_prefill and rows <= 64 and linear.wants_fragments(rows, act)
 
 
 class LlamaRMSNorm:
@@ -124,24 +123,19 @@ class FlashLlamaAttention:
             bias=config.attention_bias)
         self.o_proj = TensorParallelRowLinear.load(config, prefix=f"{prefix}.o_proj", weights=weights,
                                                    bias=config.attention_bias)
-        # int4 qkv: decode steps of up to 64 rows rotate q / k and write the cache in the GEMM epilogue
-        if hasattr(self.query_key_value.linear, "rope_heads"):
-            self.query_key_value.linear.rope_heads = (self.num_heads, self.num_key_value_heads, self.head_size)
+        # where the linear has that launch, decode steps of up to 64 rows rotate q / k and write the cache in the GEMM epilogue
+        self.query_key_value.declare_rope_heads(self.num_heads, self.num_key_value_heads, self.head_size)
 
     def project_qkv(self, hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id: int, kv: KVArgs):
         """qkv GEMM, rotation of q and k in place, k and v scattered to their page slots (reference :251-268,282)."""
         H, Hkv, D = self.num_heads, self.num_key_value_heads, self.head_size
-        lin = self.query_key_value.linear
-        rope_w = getattr(lin, "rope_handle", None)
         if isinstance(hidden_states, native.FragAct) or (
-                rope_w is not None and kv.slots is not None and not kv.fresh_prefill and kv.max_q_len == 1
-                and hidden_states.shape[0] <= 64 and cos.shape[1] * 2 == D
-                and native.rope_gemm_ok(hidden_states.shape[0], rope_w, D)):
-            # one launch: GEMM + rotary embedding + cache write (native.gptq_gemm_rope / native.dense_gemm_rope)
-            fused = native.gptq_gemm_rope if isinstance(rope_w, native.GptqWeight) else native.dense_gemm_rope
+                kv.slots is not None and not kv.fresh_prefill and kv.max_q_len == 1 and cos.shape[1] * 2 == D
+                and self.query_key_value.rope_serves(hidden_states.shape[0])):
+            # one launch: GEMM + rotary embedding + cache write
             k_pool, v_pool, scales = layer_pools(kv, layer_id)
-            return fused(hidden_states, rope_w, lin.bias, cos, sin, position_ids, kv.slots, k_pool, v_pool, H, Hkv, D,
-                         **scales)
+            return self.query_key_value.forward_rope(hidden_states, cos, sin, position_ids, kv.slots, k_pool, v_pool,
+                                                     **scales)
         # [T, (H + 2 Hkv) D]; at decode sizes the split-K sum of the GPTQ GEMM is finished inside the rope kernel
         qkv = self.query_key_value(hidden_states, partial=True)
         return write_kv(qkv, kv, layer_id, H, Hkv, D, D, cos, sin, position_ids, cu_seqlens_q)
@@ -150,7 +144,7 @@ class FlashLlamaAttention:
         """Attention of the rotated q over the layer's cache pages (reference :271-295): [T, H D]."""
         # decode: the o_proj GEMM reads its operand in fragment order
         return attend(qkv, kv, layer_id, self.num_heads, self.num_key_value_heads, self.head_size, self.softmax_scale,
-                      cu_seqlens_q, frag_out=frag_rows(self.o_proj.linear, qkv.shape[0], kv))
+                      cu_seqlens_q, frag_out=frag_rows(self.o_proj, qkv.shape[0], kv))
 
     def forward(self, hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id: int, kv: KVArgs):
         qkv = self.project_qkv(hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id, kv)
@@ -173,15 +167,13 @@ class LlamaMLP:
         self.intermediate_size = config.intermediate_size // weights.process_group.size()
         # GPTQ: SiLU(gate)*up runs in the gate_up GEMM epilogue (columns interleaved at prepare time);
         # dense: it runs while down_proj stages its operand.  Reference: eager ops at :332-335.
-        self.fused_epilogue = hasattr(self.gate_up_proj.linear, "gate_up") and self.intermediate_size % 16 == 0
-        if self.fused_epilogue:
-            self.gate_up_proj.linear.gate_up = True
+        self.fused_epilogue = self.intermediate_size % 16 == 0 and self.gate_up_proj.fuse_gate_up()
 
     def forward(self, hidden_states):
         if self.fused_epilogue:
             if isinstance(hidden_states, native.FragAct):  # decode: SiLU * up leaves in the layout down_proj reads
                 rows = hidden_states.shape[0]
-                act = self.gate_up_proj(hidden_states, out_frag=self.down_proj.linear.wants_fragments(rows))
+                act = self.gate_up_proj(hidden_states, out_frag=self.down_proj.wants_fragments(rows))
                 return self.down_proj(act, partial=True)
             act = self.gate_up_proj(hidden_states)  # [T, I], already silu(gate) * up
             return self.down_proj(act, partial=True)
@@ -208,10 +200,10 @@ class FlashLlamaLayer:
         # decode steps of <= 64 rows hand the int4 GEMMs their operands in fragment order (native.FragAct): the qkv + rotary
         # launch when it serves the step, the MLP when the SiLU * up epilogue does
         qkv_frag = (kv.slots is not None and cos.shape[1] * 2 == att.head_size
-                    and frag_rows(att.query_key_value.linear, rows, kv, act=3))
+                    and frag_rows(att.query_key_value, rows, kv, act=3))
         normed_hidden_states, res = self.input_layernorm(hidden_states, residual, frag=qkv_frag)
         attn_output = att(normed_hidden_states, cos, sin, position_ids, cu_seqlens_q, self.layer_id, kv)
-        mlp_frag = self.mlp.fused_epilogue and frag_rows(self.mlp.gate_up_proj.linear, rows, kv, act=2)
+        mlp_frag = self.mlp.fused_epilogue and frag_rows(self.mlp.gate_up_proj, rows, kv, act=2)
         normed_attn_res_output, attn_res = self.post_attention_layernorm(attn_output, res, frag=mlp_frag)
         mlp_output = self.mlp(normed_attn_res_output)
         return mlp_output, attn_res
@@ -254,12 +246,8 @@ class FlashLlamaForCausalLM(FlashForCausalLM):
         self.config = config
         self.model = FlashLlamaModel(config, weights)
         self.lm_head = TensorParallelHead.load(config, prefix="lm_head", weights=weights)
-        self.gptq_linears = []
-        for layer in self.model.layers:
-            for lin in (layer.self_attn.query_key_value.linear, layer.self_attn.o_proj.linear,
-                        layer.mlp.gate_up_proj.linear, layer.mlp.down_proj.linear):
-                if hasattr(lin, "post_init"):
-                    self.gptq_linears.append(lin)
+        self.collect_linears((layer.self_attn.query_key_value, layer.self_attn.o_proj, layer.mlp.gate_up_proj,
+                              layer.mlp.down_proj) for layer in self.model.layers)
 
     def get_input_embeddings(self):
         return self.model.embed_tokens

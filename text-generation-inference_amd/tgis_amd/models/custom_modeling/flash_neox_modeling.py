@@ -169,7 +169,7 @@ class FlashMLP:
 
     def forward(self, hidden_states, partial: bool):
         # GELU (act 4 erf / act 5 tanh) where the GEMM finishes its output
-        h = self.dense_h_to_4h(hidden_states, gelu=self.tanh)
+        h = self.dense_h_to_4h.forward_gelu(hidden_states, self.tanh)
         return self.dense_4h_to_h(h, partial=partial)
 
     __call__ = forward

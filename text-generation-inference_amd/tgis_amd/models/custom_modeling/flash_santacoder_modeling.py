@@ -9,11 +9,9 @@ tgis_rope_kv_write runs with cos = NULL and only scatters k/v into their page sl
 import torch
 import torch.distributed
 
-from tgis_amd import native
 from tgis_amd.utils.graph_segments import collective
 from tgis_amd.models.custom_modeling.flash_common import FastLayerNorm, FlashForCausalLM, KVArgs, attend, write_kv
 from tgis_amd.utils.layers import (
-    FastLinear,
     TensorParallelColumnLinear,
     TensorParallelEmbedding,
     TensorParallelHead,
@@ -127,10 +125,7 @@ class MLP:
         self.c_proj = load_row(config, prefix=f"{prefix}.c_proj", weights=weights, bias=True)
 
     def forward(self, hidden_states):
-        if isinstance(self.c_fc.linear, FastLinear):
-            h = self.c_fc(hidden_states, gelu=self.tanh)  # GELU where the decode GEMM finishes its output
-        else:
-            h = native.gelu(self.c_fc(hidden_states), self.tanh)
+        h = self.c_fc.forward_gelu(hidden_states, self.tanh)  # dense: GELU where the decode GEMM finishes its output
         return self.c_proj(h, partial=True)  # summed by the next block's add + LayerNorm
 
     __call__ = forward
@@ -189,11 +184,7 @@ class FlashSantacoderForCausalLM(FlashForCausalLM):
         self.config = config
         self.transformer = FlashSantacoderModel(config, weights)
         self.lm_head = TensorParallelHead.load(config, prefix="transformer.wte", weights=weights)  # tied
-        self.gptq_linears = []
-        for blk in self.transformer.h:
-            for lin in (blk.attn.c_attn.linear, blk.attn.c_proj.linear, blk.mlp.c_fc.linear, blk.mlp.c_proj.linear):
-                if hasattr(lin, "post_init"):
-                    self.gptq_linears.append(lin)
+        self.collect_linears((blk.attn.c_attn, blk.attn.c_proj, blk.mlp.c_fc, blk.mlp.c_proj) for blk in self.transformer.h)
 
     @property
     def model(self):

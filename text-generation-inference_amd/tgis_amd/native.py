@@ -291,18 +291,64 @@ class FragAct:
         return self.buf.view(rb, K // 64, 4, 2, 32, 8).permute(0, 4, 1, 3, 2, 5).reshape(rb * 32, K)[:self.M].contiguous()
 
 
-def gptq_fragments_ok(M: int, w: "GptqWeight", act: int = 0) -> bool:
-    """Should an M-row activation reach this int4 GEMM in fragment order (tgis_gptq_fragments_ok)?  act 3 = the rope image."""
-    key = ("frag_ok", M, act)
-    cache = w.__dict__.setdefault("_frag_ok", {})
-    got = cache.get(key)
+def _asked_once(w, key, ask):
+    """A host-only answer of the library about the prepared weight `w`, asked on first use and kept on the weight: an eager
+    decode step (tensor parallelism without graphs) would otherwise make these ctypes calls for every layer."""
+    got = w.answers.get(key)
     if got is None:
-        got = cache[key] = bool(load_library().tgis_gptq_fragments_ok(M, w.K, w.N, w.groups, int(w.perm is not None), act))
+        got = w.answers[key] = ask()
     return got
 
 
+def gptq_fragments_ok(M: int, w: "GptqWeight", act: int = 0) -> bool:
+    """Should an M-row activation reach this int4 GEMM in fragment order (tgis_gptq_fragments_ok)?  act 3 = the rope image."""
+    return _asked_once(w, ("frag_ok", M, act), lambda: bool(
+        load_library().tgis_gptq_fragments_ok(M, w.K, w.N, w.groups, int(w.perm is not None), act)))
+
+
 # ---- GPTQ ------------------------------------------------------------------------------------------
-class GptqWeight:
+class _GptqImage:
+    """What the prepared 4- and 8-bit GPTQ matrices share: the repack launch, the activation permutation and its three
+    sources.  g_idx is None, a [K] tensor (act-order when not trivial: the library then fills `perm`), or ("perm", gather
+    index [K] with -1 = zero, activation columns) for rows that are already in image order (act-order row shards)."""
+
+    def _prepare(self, bits: int, qweight, qzeros, scales, g_idx, flags: int):
+        lib = load_library()
+        entry = "tgis_gptq_" if bits == 4 else "tgis_gptq8_"
+        self.K = qweight.shape[0] * (32 // bits)
+        self.N = qweight.shape[1]
+        self.groups = qzeros.shape[0]
+        self.answers = {}  # see _asked_once
+        dev = qweight.device
+        self.image = torch.empty(getattr(lib, entry + "prepared_bytes")(self.K, self.N, self.groups), dtype=torch.uint8,
+                                 device=dev)
+        qweight = qweight.contiguous()
+        qzeros = qzeros.contiguous()
+        scales = scales.to(torch.float16).contiguous()
+        self.perm = None
+        self.in_features = self.K  # columns of the activation (differs from K only for padded act-order row shards)
+        gi = perm_buf = explicit = None
+        if isinstance(g_idx, tuple):
+            _, explicit, self.in_features = g_idx
+            assert explicit.numel() == self.K
+        elif g_idx is not None:
+            assert g_idx.numel() == self.K
+            gi = g_idx.to("cpu", torch.int32).contiguous()
+            perm_buf = torch.empty(self.K, dtype=torch.int32, device=dev)
+        _check(
+            getattr(lib, entry + "prepare")(
+                _ptr(qweight), _ptr(qzeros), _ptr(scales), gi.data_ptr() if gi is not None else None, _ptr(perm_buf),
+                self.K, self.N, self.groups, flags, _ptr(self.image), _stream()), entry + "prepare")
+        if gi is not None:
+            gs = self.K // self.groups
+            if not bool((gi == (torch.arange(self.K, dtype=torch.int32) // gs)).all()):
+                self.perm = perm_buf
+        if explicit is not None:
+            self.perm = explicit.to(dev, torch.int32).contiguous()
+        torch.cuda.current_stream().synchronize()  # qweight/qzeros/scales may be freed by the caller
+
+
+class GptqWeight(_GptqImage):
     """Prepared (repacked) GPTQ matrix; owner of the device image. Mirrors the q_handle of
     Ex4bitLinearV2.post_init (utils/gptq/exllamav2.py:124-137)."""
 
@@ -317,50 +363,17 @@ class GptqWeight:
         if bits != 4:
             raise TgisHipError(f"GPTQ is supported at 4 and 8 bits, not {bits}; this is the 4-bit image (exllamav2.py:105), "
                                "8 bits take Gptq8Weight")
-        lib = load_library()
-        self.K = qweight.shape[0] * 8
-        self.N = qweight.shape[1]
-        self.groups = qzeros.shape[0]
-        if self.K % 32 or self.N % 32:
+        if qweight.shape[0] * 8 % 32 or qweight.shape[1] % 32:
             raise TgisHipError("GPTQ height and width must be multiples of 32 (exllamav2.py:118-119)")
-        dev = qweight.device
-        nbytes = lib.tgis_gptq_prepared_bytes(self.K, self.N, self.groups)
-        self.image = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        qweight = qweight.contiguous()
-        qzeros = qzeros.contiguous()
-        scales = scales.to(torch.float16).contiguous()
-        self.perm = None
-        self.in_features = self.K  # columns of the activation (differs from K only for padded act-order row shards)
-        gi = None
-        perm_buf = None
-        explicit = None
-        if isinstance(g_idx, tuple):  # ("perm", gather index [K] with -1 = zero, activation columns): rows are in image order
-            _, explicit, self.in_features = g_idx
-            assert explicit.numel() == self.K
-            g_idx = None
-        if g_idx is not None:
-            gi = g_idx.to("cpu", torch.int32).contiguous()
-            perm_buf = torch.empty(self.K, dtype=torch.int32, device=dev)
-        _check(
-            lib.tgis_gptq_prepare(
-                _ptr(qweight), _ptr(qzeros), _ptr(scales), gi.data_ptr() if gi is not None else None,
-                _ptr(perm_buf), self.K, self.N, self.groups, self.flags, _ptr(self.image), _stream()),
-            "tgis_gptq_prepare")
-        if gi is not None:
-            gs = self.K // self.groups
-            trivial = bool((gi == (torch.arange(self.K, dtype=torch.int32) // gs)).all())
-            if not trivial:
-                self.perm = perm_buf
-        if explicit is not None:
-            self.perm = explicit.to(dev, torch.int32).contiguous()
-        torch.cuda.current_stream().synchronize()  # qweight/qzeros/scales may be freed by the caller
+        self._prepare(4, qweight, qzeros, scales, g_idx, self.flags)
 
     def workspace_bytes(self, M: int) -> int:
         return load_library().tgis_gptq_gemm_workspace_bytes(M, self.K, self.N)
 
     def fused_rows(self, act: int = 0) -> int:
         """Largest M the fused kernels of tgis_gptq_gemm_f16 should be given (beyond: dequantise + library GEMM)."""
-        return load_library().tgis_gptq_gemm_fused_rows(self.K, self.groups, int(self.perm is not None), act)
+        return _asked_once(self, ("fused_rows", act), lambda: load_library().tgis_gptq_gemm_fused_rows(
+            self.K, self.groups, int(self.perm is not None), act))
 
 
 def gptq_gemm(x, w: GptqWeight, ws: Workspace, bias=None, act: int = 0, out=None, out_frag: bool = False):
@@ -370,33 +383,26 @@ def gptq_gemm(x, w: GptqWeight, ws: Workspace, bias=None, act: int = 0, out=None
     assert act != 2 or w.flags & 1, "act=2 needs a weight prepared with gate_up=True"
     if isinstance(x, FragAct):
         assert x.K == w.K and act in (0, 2) and w.perm is None
-        M = x.M
-        if out_frag:
-            assert act == 2 and out is None
-            res = FragAct.empty(M, w.N // 2, x.device)
-            optr, ldo = _ptr(res.buf), LD_FRAGMENTS
-        else:
-            res = out if out is not None else torch.empty((M, w.N // 2 if act == 2 else w.N), dtype=torch.float16,
-                                                          device=x.device)
-            optr, ldo = _ptr(res), res.stride(0)
-        ws.ensure(w.workspace_bytes(M))
-        _check(
-            load_library().tgis_gptq_gemm_f16(_ptr(x.buf), LD_FRAGMENTS, _ptr(w.image), _ptr(bias), None, optr, ldo, M, w.K,
-                                              w.N, w.groups, act, ws.ptr, ws.nbytes, _stream()), "tgis_gptq_gemm_f16")
-        return res
-    assert not out_frag, "a fragment-order output needs a fragment-order activation"
-    assert x.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1
-    M = x.shape[0]
-    assert x.shape[1] == (2 * w.in_features if act == 1 else w.in_features), (x.shape, w.in_features, act)
-    assert act != 1 or w.in_features == w.K
-    if out is None:
-        out = torch.empty((M, w.N // 2 if act == 2 else w.N), dtype=torch.float16, device=x.device)
+        M, xp, ldx = x.M, _ptr(x.buf), LD_FRAGMENTS
+    else:
+        assert not out_frag, "a fragment-order output needs a fragment-order activation"
+        assert x.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1
+        M, xp, ldx = x.shape[0], _ptr(x), x.stride(0)
+        assert x.shape[1] == (2 * w.in_features if act == 1 else w.in_features), (x.shape, w.in_features, act)
+        assert act != 1 or w.in_features == w.K
+    if out_frag:
+        assert act == 2 and out is None
+        res = FragAct.empty(M, w.N // 2, x.device)
+        optr, ldo = _ptr(res.buf), LD_FRAGMENTS
+    else:
+        res = out if out is not None else torch.empty((M, w.N // 2 if act == 2 else w.N), dtype=torch.float16,
+                                                      device=x.device)
+        optr, ldo = _ptr(res), res.stride(0)
     ws.ensure(w.workspace_bytes(M))
     _check(
-        load_library().tgis_gptq_gemm_f16(_ptr(x), x.stride(0), _ptr(w.image), _ptr(bias), _ptr(w.perm), _ptr(out),
-                                          out.stride(0), M, w.K, w.N, w.groups, act, ws.ptr, ws.nbytes, _stream()),
-        "tgis_gptq_gemm_f16")
-    return out
+        load_library().tgis_gptq_gemm_f16(xp, ldx, _ptr(w.image), _ptr(bias), _ptr(w.perm), optr, ldo, M, w.K, w.N,
+                                          w.groups, act, ws.ptr, ws.nbytes, _stream()), "tgis_gptq_gemm_f16")
+    return res
 
 
 class Partial:
@@ -430,23 +436,17 @@ def gptq_gemm_partial(x: torch.Tensor, w: GptqWeight, bias=None, act: int = 0) -
         key, xp, ldx = ((M + 63) // 64 if M > 32 else 0), _ptr(x), x.stride(0)  # plan depends on M through its pass count
     plan = w.partial_plan.get(key)  # (slab bytes, S, ld): asked from the library once per weight and pass count
     if plan is None:
-        nbytes = lib.tgis_gptq_gemm_partial_bytes(M, w.K, w.N)
-        slabs = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
-        S = _c_int()
-        ld = _c_i64()
-        _check(
-            lib.tgis_gptq_gemm_f16_partial(xp, ldx, _ptr(w.image), _ptr(w.perm), M, w.K, w.N,
-                                           w.groups, act, _ptr(slabs), nbytes, ctypes.byref(S), ctypes.byref(ld),
-                                           _stream()), "tgis_gptq_gemm_f16_partial")
-        w.partial_plan[key] = (nbytes, S.value, ld.value)
-        return Partial(slabs, S.value, ld.value, M, w.N, bias)
-    nbytes, S, ld = plan
+        nbytes, S, ld = lib.tgis_gptq_gemm_partial_bytes(M, w.K, w.N), _c_int(), _c_i64()
+        ask = (ctypes.byref(S), ctypes.byref(ld))
+    else:
+        nbytes, ask = plan[0], (None, None)
     slabs = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
     _check(
-        lib.tgis_gptq_gemm_f16_partial(xp, ldx, _ptr(w.image), _ptr(w.perm), M, w.K, w.N,
-                                       w.groups, act, _ptr(slabs), nbytes, None, None, _stream()),
-        "tgis_gptq_gemm_f16_partial")
-    return Partial(slabs, S, ld, M, w.N, bias)
+        lib.tgis_gptq_gemm_f16_partial(xp, ldx, _ptr(w.image), _ptr(w.perm), M, w.K, w.N, w.groups, act, _ptr(slabs),
+                                       nbytes, *ask, _stream()), "tgis_gptq_gemm_f16_partial")
+    if plan is None:
+        plan = w.partial_plan[key] = (nbytes, S.value, ld.value)
+    return Partial(slabs, plan[1], plan[2], M, w.N, bias)
 
 
 def gptq_rope_ok(M: int, w: GptqWeight, D: int) -> bool:
@@ -455,16 +455,9 @@ def gptq_rope_ok(M: int, w: GptqWeight, D: int) -> bool:
 
 def rope_gemm_ok(M: int, w, D: int) -> bool:
     """Whether the fused qkv + rotary + cache-write launch should serve M rows of this weight (int4 or dense image)."""
-    key = ("rope_ok", M)
-    cache = w.__dict__.setdefault("_rope_ok", {})
-    got = cache.get(key)
-    if got is None:
-        if isinstance(w, GptqWeight):
-            got = gptq_rope_ok(M, w, D)
-        else:
-            got = bool(load_library().tgis_dense_rope_ok(M, w.K, w.N, D))
-        cache[key] = got
-    return got
+    if isinstance(w, GptqWeight):
+        return _asked_once(w, ("rope_ok", M), lambda: gptq_rope_ok(M, w, D))
+    return _asked_once(w, ("rope_ok", M), lambda: bool(load_library().tgis_dense_rope_ok(M, w.K, w.N, D)))
 
 
 def gptq_gemm_rope(x: torch.Tensor, w: GptqWeight, bias, cos, sin, positions, slots, k_pool, v_pool, H: int, Hkv: int,
@@ -490,9 +483,11 @@ def gptq_gemm_rope(x: torch.Tensor, w: GptqWeight, bias, cos, sin, positions, sl
     return out
 
 
-def gptq_dequant(w: GptqWeight) -> torch.Tensor:
+def gptq_dequant(w: GptqWeight, out=None) -> torch.Tensor:
     """Dense f16 [K,N] (rows in the prepared order: permuted by w.perm for act-order matrices)."""
-    out = torch.empty((w.K, w.N), dtype=torch.float16, device=w.image.device)
+    if out is None:
+        out = torch.empty((w.K, w.N), dtype=torch.float16, device=w.image.device)
+    assert out.shape == (w.K, w.N) and out.dtype == torch.float16 and out.is_contiguous()
     _check(load_library().tgis_gptq_dequant_f16(_ptr(w.image), _ptr(out), w.K, w.N, w.groups, w.flags, _stream()),
            "tgis_gptq_dequant_f16")
     return out
@@ -502,45 +497,14 @@ def gptq_dequant(w: GptqWeight) -> torch.Tensor:
 GPTQ8_MAX_M = 64  # rows the fused 8-bit kernel serves (above: gptq8_dequant + a library GEMM)
 
 
-class Gptq8Weight:
+class Gptq8Weight(_GptqImage):
     """Prepared 8-bit GPTQ matrix (csrc/gptq8_gemm_body.h); what QuantLinear holds for bits = 8
-    (utils/gptq/quant_linear.py:259).  Takes the g_idx forms of GptqWeight: None, a [K] tensor (act-order when not
-    trivial), or ("perm", gather index [K] with -1 = zero, activation columns) for rows already in image order."""
+    (utils/gptq/quant_linear.py:259).  Takes the g_idx forms of GptqWeight."""
 
     def __init__(self, qweight, qzeros, scales, g_idx, bits: int, groupsize: int):
         if bits != 8:
             raise TgisHipError(f"Gptq8Weight is the 8-bit image, not {bits} bits")
-        lib = load_library()
-        self.K = qweight.shape[0] * 4
-        self.N = qweight.shape[1]
-        self.groups = qzeros.shape[0]
-        dev = qweight.device
-        qweight = qweight.contiguous()
-        qzeros = qzeros.contiguous()
-        scales = scales.to(torch.float16).contiguous()
-        self.perm = None
-        self.in_features = self.K  # columns of the activation (differs from K only for padded act-order row shards)
-        gi = perm_buf = explicit = None
-        if isinstance(g_idx, tuple):
-            _, explicit, self.in_features = g_idx
-            assert explicit.numel() == self.K
-            g_idx = None
-        if g_idx is not None:
-            assert g_idx.numel() == self.K
-            gi = g_idx.to("cpu", torch.int32).contiguous()
-            perm_buf = torch.empty(self.K, dtype=torch.int32, device=dev)
-        self.image = torch.empty(lib.tgis_gptq8_prepared_bytes(self.K, self.N, self.groups), dtype=torch.uint8, device=dev)
-        _check(
-            lib.tgis_gptq8_prepare(_ptr(qweight), _ptr(qzeros), _ptr(scales), gi.data_ptr() if gi is not None else None,
-                                   _ptr(perm_buf), self.K, self.N, self.groups, 0, _ptr(self.image), _stream()),
-            "tgis_gptq8_prepare")
-        if gi is not None:
-            gs = self.K // self.groups
-            if not bool((gi == (torch.arange(self.K, dtype=torch.int32) // gs)).all()):
-                self.perm = perm_buf
-        if explicit is not None:
-            self.perm = explicit.to(dev, torch.int32).contiguous()
-        torch.cuda.current_stream().synchronize()  # qweight/qzeros/scales may be freed by the caller
+        self._prepare(8, qweight, qzeros, scales, g_idx, 0)
 
     def workspace_bytes(self, M: int) -> int:
         return load_library().tgis_gptq8_gemm_workspace_bytes(M, self.K, self.N)
@@ -582,6 +546,7 @@ class DenseWeight:
         assert weight.dim() == 2
         self.N, self.K = weight.shape
         self.dtype = weight.dtype
+        self.answers = {}  # see _asked_once
         self.flags = 1 if gate_up else 0
         if rope is not None:  # (D, rotated heads): the image of a fused qkv projection for dense_gemm_rope
             assert not gate_up

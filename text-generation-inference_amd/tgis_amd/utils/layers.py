@@ -7,7 +7,6 @@ Mirrors utils/layers.py of the reference: `FastLinear` (:104-111), the `get_line
 `QuantLinear` of 8-bit checkpoints (utils/gptq/quant_linear.py:259).
 Every forward runs a kernel of libtgis_hip.so (decode-sized M) or, for prefill-sized M, a library GEMM
 on the same device; there is no CPU path."""
-import math
 from typing import List, Optional
 
 import torch
@@ -42,57 +41,98 @@ def workspace(device) -> native.Workspace:
     return ws
 
 
-class FastLinear:
+class Linear:
+    """What the models may ask of a projection, whatever its weight format.  Each capability has a default that means "not
+    offered"; a new weight format derives from this class and overrides what it can serve.  `rope_handle` is the weight image
+    of the fused qkv + rotary + cache-write launch (None: there is none)."""
+    bias = None
+    gate_up = False
+    rope_heads = None
+    rope_handle = None
+    quantized = False  # a GPTQ linear, with a `q_handle` image and (height, width)
+
+    def forward(self, x, act: int = 0, partial: bool = False, out_frag: bool = False, out_f32: bool = False):
+        """x @ W (+ bias).  act 1: x is [M, 2 K] and SiLU(x[:, :K]) * x[:, K:] is the operand.  partial (decode-sized M): the
+        result may be a native.Partial whose split-K sum the consumer kernel finishes.  x may be a native.FragAct where
+        `wants_fragments` said so, and out_frag then asks for one back.  out_f32: fp32 output (the head)."""
+        raise NotImplementedError
+
+    def forward_gelu(self, x, tanh: bool):
+        """GELU(forward(x)): the exact erf form, or the tanh approximation."""
+        return native.gelu(self.forward(x), tanh)
+
+    def fuse_gate_up(self) -> bool:
+        """Asked once by LlamaMLP of its [gate | up] projection, before the first forward.  True: from now on `forward`
+        returns SiLU(gate) * up [M, I] from its own epilogue; False: not offered, it keeps returning [M, 2 I]."""
+        return False
+
+    def declare_rope_heads(self, H: int, Hkv: int, D: int) -> None:
+        """Told once by FlashLlamaAttention to its fused qkv projection: the (query heads, kv heads, head size) of this shard.
+        A class with a fused qkv + rotary + cache-write launch builds its `rope_handle` from this (here or in post_init)."""
+        self.rope_heads = (H, Hkv, D)
+
+    def rope_serves(self, rows: int) -> bool:
+        """Whether `forward_rope` should serve a decode step of `rows` rows."""
+        return (self.rope_handle is not None and rows <= 64
+                and native.rope_gemm_ok(rows, self.rope_handle, self.rope_heads[2]))
+
+    def forward_rope(self, x, cos, sin, positions, slots, k_pool, v_pool, **kv_scales):
+        """qkv projection + rotary embedding + cache write in one launch: [M, (H + 2 Hkv) D] whose first H D columns hold
+        the rotated q (k and v went straight into their cache pages)."""
+        raise NotImplementedError
+
+    def wants_fragments(self, rows: int, act: int = 0) -> bool:
+        """Should the producer of this linear's operand write it in fragment order (native.FragAct) for `rows` decode
+        rows?  act: 0 plain / partial, 2 the SiLU * up image, 3 the rope image (the fused qkv + rotary launch)."""
+        return False
+
+    def post_init(self) -> None:
+        """Repack the checkpoint tensors for the kernels, once (nothing to do where that happens at construction)."""
+
+
+class FastLinear(Linear):
     def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor]):
         self.weight = weight
         self.bias = bias
         self.prepared = native.DenseWeight(weight)
         self.out_features, self.in_features = weight.shape
-        self._gate_up = False
-        self._rope_heads = None
-        self.rope_handle: Optional[native.DenseWeight] = None
 
-    @property
-    def gate_up(self) -> bool:
-        return self._gate_up
+    def fuse_gate_up(self) -> bool:
+        """SiLU(gate)*up then runs in the GEMM epilogue (the image is rebuilt with interleaved pairs; the checkpoint-layout
+        weight stays for the large-M library path)."""
+        if not self.gate_up:
+            self.gate_up = True
+            self.prepared = native.DenseWeight(self.weight, gate_up=True)
+        return True
 
-    @gate_up.setter
-    def gate_up(self, on: bool):
-        """Set by LlamaMLP on the fused [gate | up] projection: SiLU(gate)*up then runs in the GEMM epilogue (the image
-        is rebuilt with interleaved pairs; the checkpoint-layout weight stays for the large-M library path)."""
-        if bool(on) != self._gate_up:
-            self._gate_up = bool(on)
-            self.prepared = native.DenseWeight(self.weight, gate_up=self._gate_up)
-
-    @property
-    def rope_heads(self):
-        return self._rope_heads
-
-    @rope_heads.setter
-    def rope_heads(self, heads):
-        """Set by FlashLlamaAttention on the fused qkv projection: (H, Hkv, D) of this shard.  Builds the rope image (a
-        second copy of the weight with rotation pairs inside each tile) for native.dense_gemm_rope."""
-        self._rope_heads = heads
-        self.rope_handle = None
-        if heads is not None and FUSED_ROPE_GEMM and heads[2] % 32 == 0:
-            H, Hkv, D = heads
+    def declare_rope_heads(self, H: int, Hkv: int, D: int) -> None:
+        """Builds the rope image (a second copy of the weight with rotation pairs inside each tile) for
+        native.dense_gemm_rope."""
+        self.rope_heads = (H, Hkv, D)
+        if FUSED_ROPE_GEMM and D % 32 == 0:
             # the image is a second copy of the weight: only build it where the fused launch will serve some decode batch
             # (tgis_dense_rope_ok asks for >= TGIS_ROPE_MIN_BLOCKS workgroups in the unsplit plan — TinyLlama has 40, a
             # 70B shard at TP = 8 has 20), as Ex4bitLinearV2.post_init does for the int4 image
             if any(native.rope_gemm_ok(m, self.prepared, D) for m in (1, 32, 64)):
                 self.rope_handle = native.DenseWeight(self.weight, rope=(D, H + Hkv))
 
-    def forward(self, x: torch.Tensor, act: int = 0, out_f32: bool = False, partial: bool = False,
-                gelu: Optional[bool] = None) -> torch.Tensor:
-        """`gelu` (None / False: exact erf form / True: tanh approximation): the activation behind this projection
-        (santacoder's `c_fc`, flash_santacoder_modeling.py:303-305) — applied where the decode GEMM finishes its output
-        instead of by a launch of its own; same bits as the two steps."""
-        if gelu is not None:
-            assert act == 0 and not out_f32 and not partial and not self._gate_up
-            if x.shape[0] <= SKINNY_MAX_M and FUSED_GELU_GEMM:
-                return native.dense_gemm(x, self.prepared, workspace(x.device), bias=self.bias, act=5 if gelu else 4)
-            return native.gelu(self.forward(x), gelu)
-        if self._gate_up:
+    def forward_rope(self, x, cos, sin, positions, slots, k_pool, v_pool, **kv_scales):
+        return native.dense_gemm_rope(x, self.rope_handle, self.bias, cos, sin, positions, slots, k_pool, v_pool,
+                                      *self.rope_heads, **kv_scales)
+
+    def forward_gelu(self, x: torch.Tensor, tanh: bool) -> torch.Tensor:
+        """The activation behind this projection (santacoder's `c_fc`, flash_santacoder_modeling.py:303-305) — applied where
+        the decode GEMM finishes its output (act 4: erf form / act 5: tanh approximation) instead of by a launch of its
+        own; same bits as the two steps."""
+        assert not self.gate_up
+        if x.shape[0] <= SKINNY_MAX_M and FUSED_GELU_GEMM:
+            return native.dense_gemm(x, self.prepared, workspace(x.device), bias=self.bias, act=5 if tanh else 4)
+        return native.gelu(self.forward(x), tanh)
+
+    def forward(self, x: torch.Tensor, act: int = 0, partial: bool = False, out_frag: bool = False,
+                out_f32: bool = False) -> torch.Tensor:
+        assert not out_frag, "dense linears take and give row-major activations"
+        if self.gate_up:
             # output is the activated [M, I] tensor
             if x.shape[0] <= SKINNY_MAX_M:
                 return native.dense_gemm(x, self.prepared, workspace(x.device), bias=self.bias, act=2)
@@ -132,53 +172,77 @@ def _gather_columns(x: torch.Tensor, q_handle) -> torch.Tensor:
     return x.index_select(1, perm)
 
 
-class Ex4bitLinearV2:
-    """4-bit GPTQ linear.  Construction keeps the checkpoint tensors; `post_init` repacks them for the
-    kernels (the reference defers this the same way, server.py:347-354)."""
+class GptqLinear(Linear):
+    """What the GPTQ linears of both widths share.  Construction keeps the checkpoint tensors; `post_init` repacks them for
+    the kernels (the reference defers this the same way, server.py:347-354) and runs by itself before the first forward.
+    A width adds `_prepare()`, which returns its native image of the checkpoint tensors, `_dequant(out)`, which writes that
+    image as a dense f16 [K, N] matrix, and `forward`."""
+    quantized = True
+
     def __init__(self, qweight, qzeros, scales, g_idx, bias, bits, groupsize):
-        assert bits == 4
+        if bits != self.BITS:
+            raise NotImplementedError(f"{type(self).__name__} is the {self.BITS}-bit linear.")
         self.device = qweight.device
         self.qweight, self.qzeros, self.scales = qweight, qzeros, scales
         # ("perm", gather index, x columns): an explicit activation permutation (act-order row shards, utils/weights.py)
         self.g_idx = g_idx if isinstance(g_idx, tuple) else (g_idx.cpu() if g_idx is not None else None)
         self.bias = bias
         self.bits, self.groupsize = bits, groupsize
-        self.height = qweight.shape[0] * 8
+        self.height = qweight.shape[0] * (32 // bits)
         self.width = qweight.shape[1]
-        # (no device check here: native.GptqWeight refuses tensors that are not on the GPU — server.py:290-291)
-        assert self.height % 32 == 0 and self.width % 32 == 0
-        self.q_handle: Optional[native.GptqWeight] = None
-        # set by LlamaMLP on the fused [gate | up] projection: SiLU(gate)*up runs in the GEMM epilogue
-        self.gate_up = False
-        # set by FlashLlamaAttention on the fused qkv projection: (H, Hkv, D) of this shard -> post_init also builds the
-        # rope image (a second copy of the int4 matrix with rotation pairs inside each tile, +K*N/2 bytes) for
-        # native.gptq_gemm_rope, the decode launch that rotates q / k and writes the cache in its epilogue
-        self.rope_heads = None
-        self.rope_handle: Optional[native.GptqWeight] = None
-        self._fused = {}  # act -> rows up to which the library's fused kernels are used
+        # (no device check here: the native weight classes refuse tensors that are not on the GPU — server.py:290-291)
+        self.q_handle = None
 
     def post_init(self):
-        self.q_handle = native.GptqWeight(self.qweight, self.qzeros, self.scales, self.g_idx, self.bits,
-                                          self.groupsize, gate_up=self.gate_up)
+        if self.q_handle is None:
+            self.q_handle = self._prepare()
+            self.qweight = self.qzeros = self.scales = None  # the prepared image replaces them
+
+    def large_m(self, x: torch.Tensor) -> torch.Tensor:
+        """prefill-sized M: dequantise once into scratch, then a library GEMM (exllamav2.py:87 "M > 50")."""
+        if self.q_handle.perm is not None:
+            x = _gather_columns(x, self.q_handle)
+        out = torch.matmul(x, self._dequant(_dequant_scratch(self.device, self.height, self.width)))
+        if self.bias is not None:
+            out.add_(self.bias)
+        return out
+
+
+class Ex4bitLinearV2(GptqLinear):
+    """4-bit GPTQ linear: adds the fused forms of the int4 kernels (SiLU * up epilogue, qkv + rotary + cache write,
+    deferred split-K sums, fragment-order operands)."""
+    BITS = 4
+
+    def __init__(self, qweight, qzeros, scales, g_idx, bias, bits, groupsize):
+        super().__init__(qweight, qzeros, scales, g_idx, bias, bits, groupsize)
+        assert self.height % 32 == 0 and self.width % 32 == 0
+
+    def fuse_gate_up(self) -> bool:
+        assert self.q_handle is None, "the [gate | up] image is chosen before post_init"
+        self.gate_up = True
+        return True
+
+    def _prepare(self):
+        q_handle = native.GptqWeight(self.qweight, self.qzeros, self.scales, self.g_idx, self.bits, self.groupsize,
+                                     gate_up=self.gate_up)
+        # a declared qkv projection also gets the rope image (a second copy of the int4 matrix with rotation pairs inside
+        # each tile, +K*N/2 bytes) for native.gptq_gemm_rope, the decode launch that rotates q / k and writes the cache in
+        # its epilogue
         if self.rope_heads is not None and FUSED_ROPE_GEMM:
             H, Hkv, D = self.rope_heads
-            if self.q_handle.perm is None and any(native.gptq_rope_ok(m, self.q_handle, D) for m in (1, 32, 64)):
+            if q_handle.perm is None and any(native.gptq_rope_ok(m, q_handle, D) for m in (1, 32, 64)):
                 self.rope_handle = native.GptqWeight(self.qweight, self.qzeros, self.scales, None, self.bits,
                                                      self.groupsize, rope=(D, H + Hkv))
-        self.qweight = self.qzeros = self.scales = None  # the prepared image replaces them
+        return q_handle
 
-    def _fused_rows(self, act: int) -> int:
-        got = self._fused.get(act)
-        if got is None:
-            got = self._fused[act] = self.q_handle.fused_rows(act)
-        return got
+    def _dequant(self, out):
+        return native.gptq_dequant(self.q_handle, out=out)
 
-    def _dequant_scratch(self) -> torch.Tensor:
-        return _dequant_scratch(self.device, self.height, self.width)
+    def forward_rope(self, x, cos, sin, positions, slots, k_pool, v_pool, **kv_scales):
+        return native.gptq_gemm_rope(x, self.rope_handle, self.bias, cos, sin, positions, slots, k_pool, v_pool,
+                                     *self.rope_heads, **kv_scales)
 
     def wants_fragments(self, rows: int, act: int = 0) -> bool:
-        """Should the producer of this linear's operand write it in fragment order (native.FragAct) for `rows` decode
-        rows?  act: 0 plain / partial, 2 the SiLU * up image, 3 the rope image (the fused qkv + rotary launch)."""
         if self.q_handle is None:
             self.post_init()
         if act == 2 and not self.gate_up:
@@ -186,71 +250,48 @@ class Ex4bitLinearV2:
         w = self.rope_handle if act == 3 else self.q_handle
         return w is not None and rows <= 64 and native.gptq_fragments_ok(rows, w, act)
 
-    def forward(self, x, act: int = 0, partial: bool = False, out_frag: bool = False):
-        """partial=True (decode-sized M only): return native.Partial — the consumer kernel finishes the split-K sum.
-        x may be a native.FragAct (decode, <= 32 rows; see wants_fragments); out_frag: the SiLU * up output leaves as one."""
+    def forward(self, x, act: int = 0, partial: bool = False, out_frag: bool = False, out_f32: bool = False):
+        """x may be a native.FragAct (decode, <= 64 rows; see wants_fragments): the fused kernels serve it whatever their
+        row limits say.  out_frag: the SiLU * up output leaves as one."""
+        assert not out_f32, "GPTQ linears give f16"
         if self.q_handle is None:
             self.post_init()
-        if isinstance(x, native.FragAct):
-            if self.gate_up:
-                return native.gptq_gemm(x, self.q_handle, workspace(x.device), bias=self.bias, act=2, out_frag=out_frag)
-            assert act == 0
-            if partial and DEFER_REDUCE:
-                return native.gptq_gemm_partial(x, self.q_handle, bias=self.bias)
-            return native.gptq_gemm(x, self.q_handle, workspace(x.device), bias=self.bias)
+        q, rows, frag = self.q_handle, x.shape[0], isinstance(x, native.FragAct)
         if self.gate_up:
             # output is the activated [M, I] tensor
-            if x.shape[0] <= self._fused_rows(2):
-                return native.gptq_gemm(x, self.q_handle, workspace(x.device), bias=self.bias, act=2)
-            return native.act_mul(self._large_m(x), self.width // 2)
-        if partial and x.shape[0] <= native.PARTIAL_MAX_M and DEFER_REDUCE:
-            return native.gptq_gemm_partial(x, self.q_handle, bias=self.bias, act=act)
-        if x.shape[0] <= self._fused_rows(act):
-            return native.gptq_gemm(x, self.q_handle, workspace(x.device), bias=self.bias, act=act)
+            if frag:
+                return native.gptq_gemm(x, q, workspace(x.device), bias=self.bias, act=2, out_frag=out_frag)
+            if rows <= q.fused_rows(2):
+                return native.gptq_gemm(x, q, workspace(x.device), bias=self.bias, act=2)
+            return native.act_mul(self.large_m(x), self.width // 2)
+        assert act == 0 or not frag
+        if partial and rows <= native.PARTIAL_MAX_M and DEFER_REDUCE:
+            return native.gptq_gemm_partial(x, q, bias=self.bias, act=act)
+        if frag or rows <= q.fused_rows(act):
+            return native.gptq_gemm(x, q, workspace(x.device), bias=self.bias, act=act)
         if act:
             x = native.act_mul(x, self.height)
-        return self._large_m(x)
-
-    def _large_m(self, x: torch.Tensor) -> torch.Tensor:
-        """prefill-sized M: dequantise once into scratch, then a library GEMM (exllamav2.py:87 "M > 50")."""
-        if self.q_handle.perm is not None:
-            x = _gather_columns(x, self.q_handle)
-        w = self._dequant_scratch()
-        native._check(native.load_library().tgis_gptq_dequant_f16(
-            self.q_handle.image.data_ptr(), w.data_ptr(), self.height, self.width, self.q_handle.groups,
-            self.q_handle.flags, native._stream()), "tgis_gptq_dequant_f16")
-        out = torch.matmul(x, w)
-        if self.bias is not None:
-            out.add_(self.bias)
-        return out
+        return self.large_m(x)
 
     __call__ = forward
 
 
-class Gptq8Linear:
+class Gptq8Linear(GptqLinear):
     """8-bit GPTQ linear: the QuantLinear the reference builds for bits = 8 (utils/layers.py:184-199,
-    utils/gptq/quant_linear.py:259).  Deliberately without the gate_up / rope_heads / wants_fragments attributes of
-    Ex4bitLinearV2: the models' duck typing then takes their generic paths (separate rope + cache write,
-    down_proj(act=1), a reduced f16 tensor where partial=True is asked)."""
+    utils/gptq/quant_linear.py:259).  The 8-bit kernel has none of the fused forms, so every capability of `Linear` keeps its
+    default: the models then run rotary + cache write as a launch of their own, down_proj(act=1), and get a reduced f16
+    tensor where they ask for partial=True."""
+    BITS = 8
 
-    def __init__(self, qweight, qzeros, scales, g_idx, bias, bits, groupsize):
-        if bits != 8:
-            raise NotImplementedError("Gptq8Linear is the 8-bit linear.")
-        self.device = qweight.device
-        self.qweight, self.qzeros, self.scales = qweight, qzeros, scales
-        self.g_idx = g_idx if isinstance(g_idx, tuple) else (g_idx.cpu() if g_idx is not None else None)
-        self.bias = bias
-        self.bits, self.groupsize = bits, groupsize
-        self.height = qweight.shape[0] * 4
-        self.width = qweight.shape[1]
-        self.q_handle: Optional[native.Gptq8Weight] = None
+    def _prepare(self):
+        return native.Gptq8Weight(self.qweight, self.qzeros, self.scales, self.g_idx, self.bits, self.groupsize)
 
-    def post_init(self):
-        self.q_handle = native.Gptq8Weight(self.qweight, self.qzeros, self.scales, self.g_idx, self.bits, self.groupsize)
-        self.qweight = self.qzeros = self.scales = None  # the prepared image replaces them
+    def _dequant(self, out):
+        return native.gptq8_dequant(self.q_handle, out=out)
 
-    def forward(self, x, act: int = 0, partial: bool = False, out_frag: bool = False):
+    def forward(self, x, act: int = 0, partial: bool = False, out_frag: bool = False, out_f32: bool = False):
         """Always the reduced f16 tensor: `partial` is accepted and not honoured (no deferred-reduce form at 8 bits)."""
+        assert not out_f32, "GPTQ linears give f16"
         assert not out_frag and not isinstance(x, native.FragAct), "8-bit linears take and give row-major activations"
         if self.q_handle is None:
             self.post_init()
@@ -260,16 +301,9 @@ class Gptq8Linear:
             x, act = native.act_mul(x, self.q_handle.in_features), 0
         if x.shape[0] <= native.GPTQ8_MAX_M:
             return native.gptq8_gemm(x, self.q_handle, workspace(x.device), bias=self.bias, act=act)
-        # the reference's own M > 50 path (exllamav2.py:87): dequantise once into the shared scratch, then a library GEMM
         if act:
             x = native.act_mul(x, self.q_handle.in_features)
-        if self.q_handle.perm is not None:
-            x = _gather_columns(x, self.q_handle)
-        w = native.gptq8_dequant(self.q_handle, out=_dequant_scratch(self.device, self.height, self.width))
-        out = torch.matmul(x, w)
-        if self.bias is not None:
-            out.add_(self.bias)
-        return out
+        return self.large_m(x)
 
     __call__ = forward
 
@@ -291,8 +325,17 @@ def get_linear(weight, bias, quantize):
 
 
 class SuperLayer:
+    """A linear in its tensor-parallel role.  What the `Linear` protocol offers besides `forward` passes through unchanged
+    (the linear's own bound methods: no frame in between on the decode path)."""
+
     def __init__(self, linear):
         self.linear = linear
+        self.forward_gelu = linear.forward_gelu
+        self.fuse_gate_up = linear.fuse_gate_up
+        self.declare_rope_heads = linear.declare_rope_heads
+        self.rope_serves = linear.rope_serves
+        self.forward_rope = linear.forward_rope
+        self.wants_fragments = linear.wants_fragments
 
     def forward(self, x, **kw):
         return self.linear.forward(x, **kw)

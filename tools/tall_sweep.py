@@ -20,13 +20,14 @@ for (K, N, act) in [(4096, 12288, 0), (4096, 4096, 0), (4096, 22016, 2), (11008,
         qz = torch.randint(-2**31, 2**31 - 1, (G, N // 8), dtype=torch.int32, device=dev)
         sc = (torch.rand(G, N, device=dev) * 0.002 + 0.001).half()
         l = layers.Ex4bitLinearV2(qw, qz, sc, None, None, 4, 128)
-        l.gate_up = act == 2
+        if act == 2:
+            l.fuse_gate_up()
         l.post_init()
         lin.append(l)
     for M in [int(m) for m in sys.argv[2].split(",")]:
         x = torch.randn(M, K, device=dev).half()
-        if mode == "lib":  # (TGIS_TALL_MAX_M=0 in the environment: _large_m never routes back to the tall kernel)
-            f = lambda i: (nat.act_mul(lin[i]._large_m(x), N // 2) if act == 2 else lin[i]._large_m(x))
+        if mode == "lib":  # (TGIS_TALL_MAX_M=0 in the environment: large_m never routes back to the tall kernel)
+            f = lambda i: (nat.act_mul(lin[i].large_m(x), N // 2) if act == 2 else lin[i].large_m(x))
         else:
             ws = nat.Workspace(lin[0].q_handle.workspace_bytes(M), dev)
             f = lambda i: nat.gptq_gemm(x, lin[i].q_handle, ws, act=act)
