@@ -350,7 +350,14 @@ int tgis_rope_kv_write_prefill_at_kv8(void* qkv, int64_t ld_qkv, const void* cos
  *      utils/flash_attn.py:43-78) ---------------------------------------------------------------- */
 /* Number of key-range splits the launcher will use for this shape (so callers can size workspace). */
 int tgis_attn_num_splits(int64_t B, int Hkv, int H, int64_t max_q_len, int64_t max_ctx);
-/* head_dim D of tgis_attn_paged: 64, 96 or 128. */
+/* Key splits for a launch of up to max_q_len q tokens per sequence over a long cached context: the verify step of
+ * speculative decoding (K + 1 rows per request, models/decode_graph.py _VerifyGraph) and the suffix prefill behind reused
+ * prefix pages (models/flash_causal_lm.py _prefill_suffix_forward), both through the attention() call site of
+ * utils/flash_attn.py:43-78.  max_q_len == 1: exactly
+ * tgis_attn_num_splits; the prefill form (max_q_len * next_pow2(min(H / Hkv, 16)) > 64): 1; max_ctx < 1024
+ * (so anything below 32 pages): 1.  Host only. */
+int tgis_attn_num_splits_q(int64_t B, int Hkv, int H, int64_t max_q_len, int64_t max_ctx);
+/* Bytes of split workspace for total_q_tokens = B * max_q_len q rows (covers ragged cu_seqlens_q below that).  head_dim D of tgis_attn_paged: 64, 96 or 128. */
 int64_t tgis_attn_workspace_bytes(int64_t total_q_tokens, int H, int Hkv, int D, int num_splits);
 /* Causal softmax(q k^T * scale) v over the paged cache.
  *   q: [total_q, H, D] with token stride ld_q (elements); out: [total_q, H*D] contiguous (ld_out = 0 or

@@ -476,11 +476,15 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(AttnArgs a) {
 template <typename T, int D, int MAXS>
 __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restrict__ ws_o,
                                                            const float* __restrict__ ws_ml, T* __restrict__ out,
-                                                           int NS, int H, int out_frag, int64_t rows) {
+                                                           int NS, int H, int out_frag, int64_t rows,
+                                                           const int32_t* __restrict__ q_end) {
     // lane covers columns i 64 + lane; a D that is not a multiple of 64 (96) leaves the top lanes of its last slice idle
     constexpr int DL = (D + 63) / 64;
     const int64_t th = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // tok*H + head
     if (th >= rows) return;
+    // q_len > 1: the grid covers B * max_q_len rows, the sequences may hold fewer (ragged cu_seqlens_q).  Rows from
+    // cu_seqlens_q[B] on have no records and no place in `out`; *q_end is that entry (null at q_len 1: rows is exact).
+    if (q_end && th >= (int64_t)*q_end * H) return;
     const int lane = threadIdx.x & 63;
     auto in_row = [&](int i) { return D % 64 == 0 || i * 64 + lane < D; };
     float mstar = NEG_BIG;
@@ -586,7 +590,8 @@ static void launch_attn_one(const AttnArgs& a, dim3 grid, hipStream_t st) {
 }
 
 template <typename T, typename KV, int D>
-static int launch_attn(const AttnArgs& a, dim3 grid, int64_t total_q, hipStream_t st, int nw, int ch) {
+static int launch_attn(const AttnArgs& a, dim3 grid, int64_t total_q, const int32_t* q_end, hipStream_t st, int nw,
+                       int ch) {
     const int rc = by_int<1, 2, 3>(ch, "tgis_attn_paged: chunks per block", [&](auto chc) {
         constexpr int CH = decltype(chc)::value;
         auto one = [&](auto nwc) {
@@ -604,10 +609,10 @@ static int launch_attn(const AttnArgs& a, dim3 grid, int64_t total_q, hipStream_
         const int64_t rows = total_q * a.H;
         if (a.NS <= 8)
             hipLaunchKernelGGL((attn_combine_kernel<T, D, 8>), dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, st, a.ws_o,
-                               a.ws_ml, (T*)a.out, a.NS, a.H, a.out_frag, rows);
+                               a.ws_ml, (T*)a.out, a.NS, a.H, a.out_frag, rows, q_end);
         else
             hipLaunchKernelGGL((attn_combine_kernel<T, D, 0>), dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, st, a.ws_o,
-                               a.ws_ml, (T*)a.out, a.NS, a.H, a.out_frag, rows);
+                               a.ws_ml, (T*)a.out, a.NS, a.H, a.out_frag, rows, q_end);
         TGIS_CHECK_LAUNCH();
     }
     return TGIS_OK;
@@ -659,11 +664,38 @@ extern "C" int tgis_attn_num_splits(int64_t B, int Hkv, int H, int64_t max_q_len
     return (int)ns;
 }
 
-// records of the fused combine: [group = (sequence, kv head, chunk block)][chunk][16 columns][split]
-static int64_t fused_records(int64_t B, int H, int Hkv, int num_splits) {
+// Key splits of any decode-form launch: tgis_attn_num_splits at q_len 1, 1 for the prefill form, and for a few q tokens per
+// sequence (a verify step of speculative decoding, a short suffix behind reused prefix pages) the rule below.
+extern "C" int tgis_attn_num_splits_q(int64_t B, int Hkv, int H, int64_t max_q_len, int64_t max_ctx) {
+    if (max_q_len == 1) return tgis_attn_num_splits(B, Hkv, H, max_q_len, max_ctx);
+    if (B <= 0 || Hkv <= 0 || H <= 0 || H % Hkv != 0 || max_q_len < 1) return 1;
     AttnGeom g = geom(H, Hkv);
-    const int ch = chunks_per_block(g.HC, 1);
-    return B * Hkv * cdiv64(g.HC, ch) * ch * 16 * num_splits;
+    if (max_q_len * g.Gp > 64) return 1;  // the prefill form takes no key splits
+    const int64_t pages = cdiv64(std::max<int64_t>(max_ctx, 1), 32);
+    if (max_ctx < 1024) return 1;  // below 1024 keys (32 pages) every q_len > 1 launch stays the one it was
+    // One-chunk blocks of 4 waves, one per (sequence, kv head, 16-head chunk, q tile) and split.  Fitted to
+    // profiles/attn_qsplit_sweep.log (us per launch, D 128):
+    //  - one round of <= 256 blocks (the floor: 11 splits of 24 groups are 264 blocks, 36.9 us where 8 take 30.7), >= 16 pages
+    //    per block;
+    //  - short contexts: up to 8 splits of >= 4 pages, one per wave (7B B 1 q 4 ctx 1024: 19.9 unsplit, 15.4 at 2, 11.8 at 8;
+    //    GQA 8:1 B 1 q 2 ctx 2048: 13.5 at 8, 15.1 at 16);
+    //  - 64 - 255 groups: a second round of blocks pays from 32 pages per block on (7B B 4 q 4 ctx 8192: 91.6 at 2, 86.3 at 4;
+    //    GQA 8:1 B 4 q 4 ctx 32768: 177.2 at 4, 168.3 at 8); fewer groups lose to the merge (GQA 8:1 B 1 q 4 ctx 32768: 55.9 at
+    //    16, 59.2 at 32);
+    //  - from 256 groups on the launch stays unsplit: 2 splits give 3 - 8 % from ctx 8192 on and lose below it.
+    const int64_t base = B * Hkv * g.HC * cdiv64(max_q_len, g.TQ);
+    const int64_t one = 256 / base;
+    int64_t ns = std::min<int64_t>(one, pages / 16);
+    ns = std::max<int64_t>(ns, std::min<int64_t>(std::min<int64_t>(one, pages / 4), 8));
+    if (base >= 64 && base < 256) ns = std::max<int64_t>(ns, std::min<int64_t>(512 / base, pages / 32));
+    return (int)std::max<int64_t>(1, std::min<int64_t>(ns, 32));  // (no count above 32 was measured)
+}
+
+// records of the fused combine: [group = (q tile, kv head, chunk block, sequence)][chunk][16 columns][split]
+static int64_t fused_records(int64_t B, int H, int Hkv, int64_t max_q_len, int num_splits) {
+    AttnGeom g = geom(H, Hkv);
+    const int ch = chunks_per_block(g.HC, max_q_len);
+    return B * cdiv64(max_q_len, g.TQ) * Hkv * cdiv64(g.HC, ch) * ch * 16 * num_splits;
 }
 
 extern "C" int64_t tgis_attn_workspace_bytes(int64_t total_q_tokens, int H, int Hkv, int D, int num_splits) {
@@ -671,7 +703,10 @@ extern "C" int64_t tgis_attn_workspace_bytes(int64_t total_q_tokens, int H, int 
     // the larger of the two layouts: per (token, head, split) {O[D], m, l} for the two-launch combine, or the
     // line-padded records of the fused one (16 columns per group and chunk, {m, l} in 16 bytes)
     const int64_t two_pass = total_q_tokens * H * num_splits * ((int64_t)D + 2) * 4;
-    const int64_t fused = fused_records(total_q_tokens, H, Hkv, num_splits) * ((int64_t)D + 4) * 4;
+    // The fused size is that of total_q_tokens sequences of one token.  It covers B sequences of max_q_len tokens
+    // (total_q_tokens = B * max_q_len) as well: their launch has B * ceil(max_q_len / TQ) <= total_q_tokens q tiles per
+    // (kv head, chunk block), and one-chunk blocks over all HC <= ceil(HC / ch) * ch chunks.
+    const int64_t fused = fused_records(total_q_tokens, H, Hkv, 1, num_splits) * ((int64_t)D + 4) * 4;
     return std::max(two_pass, fused);
 }
 
@@ -800,15 +835,18 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
     const bool kv8 = kv_dtype == TGIS_KV_FP8_E4M3;
     TGIS_CHECK_ARG(ld_q % 8 == 0 && ((uintptr_t)q % 16) == 0, "tgis_attn_paged: q must be 16-byte aligned");
     TGIS_CHECK_ARG(max_q_len > 0 && max_pages > 0 && num_splits >= 1, "tgis_attn_paged: bad launch bounds");
-    TGIS_CHECK_ARG(num_splits == 1 || max_q_len == 1, "tgis_attn_paged: key splits are for decode (max_q_len == 1)");
     TGIS_CHECK_ARG(ld_out == 0 || ld_out == (int64_t)H * D ||
                        (ld_out == TGIS_LD_FRAGMENTS && max_q_len == 1 && B <= 64 && ((int64_t)H * D) % 64 == 0),
                    "tgis_attn_paged: out is [tokens, H * D] contiguous (ld_out = 0 or H * D), or — decode, <= 64 sequences — in "
                    "fragment order (ld_out = TGIS_LD_FRAGMENTS)");
     (void)max_ctx;
+    AttnGeom g = geom(H, Hkv);
+    const bool prefill_form = max_q_len * g.Gp > 64;
+    TGIS_CHECK_ARG(num_splits == 1 || !prefill_form,
+                   "tgis_attn_paged: key splits are for the decode form (max_q_len * padded group size <= 64, here %ld * %d): "
+                   "the prefill form takes none", (long)max_q_len, g.Gp);
     if (B == 0) return TGIS_OK;
     hipStream_t st = (hipStream_t)stream;
-    AttnGeom g = geom(H, Hkv);
     AttnArgs a;
     a.q = q;
     a.ld_q = ld_q;
@@ -847,16 +885,16 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
                        (long)workspace_bytes, (long)need);
         a.ws_o = (float*)workspace;
         a.ws_ml = a.ws_o + total_q * H * num_splits * D;
-        // one launch: the last block of each (sequence, kv head) group merges the splits (no combine launch)
-        const int64_t recs = fused_records(B, H, Hkv, num_splits);
-        const int64_t groups = B * Hkv * a.HCB;
+        // one launch: the last block of each (q tile, kv head, chunk block, sequence) group merges the splits (no combine launch)
+        const int64_t recs = fused_records(B, H, Hkv, max_q_len, num_splits);
+        const int64_t groups = B * cdiv64(max_q_len, g.TQ) * Hkv * a.HCB;
         if (groups <= ATTN_COUNTERS && recs * D * 4 < (1ll << 31) && ch == 1) {
             a.counters = attn_counters(st, &lease.dev, &lease.slot);
             if (a.counters) a.ws_ml = a.ws_o + recs * D;
         }
     }
     // long q (prefill): blocks of 128 columns that stage each K/V page once in LDS (attention_prefill.hip)
-    if (num_splits == 1 && max_q_len * g.Gp > 64 && !getenv("TGIS_ATTN_NO_PREFILL_KERNEL")) {
+    if (prefill_form && !getenv("TGIS_ATTN_NO_PREFILL_KERNEL")) {
         TgisTimedScope timed(TGIS_OP_ATTN, st);
         return tgis_launch_attn_prefill(a, B, Hkv, D, max_q_len, dtype, kv8, st);
     }
@@ -879,13 +917,15 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
         nw = (v == 1 || v == 2 || v == 3 || v == 8) ? v : 4;
         if (ch > 1 && (nw > 4 || nw == 3)) nw = 4;
     }
+    // the combine launch of a q_len > 1 call runs over B * max_q_len rows: it reads the real count, cu_seqlens_q[B]
+    const int32_t* q_end = max_q_len > 1 ? cu_seqlens_q + B : nullptr;
     TgisTimedScope timed(TGIS_OP_ATTN, st);
     return by_dtype(dtype, [&](auto t) {
         using T = type_of<decltype(t)>;
         return by_kv<T>(kv8, [&](auto kv) {  // one-byte cache: the same launch shapes over e4m3 pools
             // D = 96: KS = 3, NB = 6 (gpt-neox-20b)
             return by_int<128, 96, 64>(D, "tgis_attn_paged: head_dim", [&](auto d) {
-                return launch_attn<T, type_of<decltype(kv)>, decltype(d)::value>(a, grid, total_q, st, nw, ch);
+                return launch_attn<T, type_of<decltype(kv)>, decltype(d)::value>(a, grid, total_q, q_end, st, nw, ch);
             });
         });
     });

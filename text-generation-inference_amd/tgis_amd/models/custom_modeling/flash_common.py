@@ -63,7 +63,9 @@ def attend(qkv, kv: KVArgs, layer_id: int, H: int, Hkv: int, D: int, scale: floa
     ws = None
     if kv.num_splits > 1:
         ws = workspace(qkv.device)
-        ws.ensure(native.attn_workspace_bytes(T, H, Hkv, D, kv.num_splits))
+        # the launcher sizes its records for B * max_q_len rows: T itself except behind ragged suffixes (prefix reuse)
+        rows = max(T, kv.block_tables.shape[0] * kv.max_q_len)
+        ws.ensure(native.attn_workspace_bytes(rows, H, Hkv, D, kv.num_splits))
     native.attn_paged(qkv, qkv.stride(0), k_pool, v_pool, kv.block_tables, kv.ctx_lens, cu_seqlens_q, attn_output,
                       kv.block_tables.shape[0], H, Hkv, D, kv.max_q_len, kv.max_ctx, scale, kv.num_splits, ws, **scales)
     return attn_output

@@ -239,7 +239,7 @@ class _DecodeGraph:
 class _VerifyGraph(_DecodeGraph):
     """The verify step of speculative decoding for a (batch-size bucket, table width, K) triple: K + 1 rows per request, its
     latest token and its K drafts, through the generic q_len > 1 forward (rotary and cache write per token, the attention's
-    decode form with one key split), then the greedy choice behind every row.  `input_ids` / `positions` stay the
+    decode form, with key splits from 1024 keys on), then the greedy choice behind every row.  `input_ids` / `positions` stay the
     per-request inputs, as in the plain step, so that the launch after either step can leave the next inputs in them."""
 
     def __init__(self, lm, B: int, width: int, K: int):
@@ -252,7 +252,8 @@ class _VerifyGraph(_DecodeGraph):
         self.row_positions = torch.zeros(R, dtype=torch.int32, device=dev)
         self.ctx = torch.full((B,), K + 1, dtype=torch.int32, device=dev)
         self.cu_q = torch.arange(B + 1, dtype=torch.int32, device=dev) * (K + 1)
-        self.num_splits = 1  # the attention's q_len > 1 forms take no key splits
+        # the decode form takes key splits over a long context (tgis_attn_num_splits_q); captured and eager steps share them
+        self.num_splits = native.attn_q_splits(B, lm.num_kv_heads, lm.num_heads, K + 1, self.max_ctx)
         self.spec_out = _SpecOut(B, K, dev)
 
     def _step(self):
@@ -260,7 +261,7 @@ class _VerifyGraph(_DecodeGraph):
         native.spec_stage(self.positions, self.input_ids, self.drafts, self.block_tables, self.row_ids, self.row_positions,
                           self.slots, self.ctx)
         kv = KVArgs(cache=lm.kv_cache, block_tables=self.block_tables, ctx_lens=self.ctx, slots=self.slots,
-                    max_q_len=self.K + 1, max_ctx=self.max_ctx, num_splits=1)
+                    max_q_len=self.K + 1, max_ctx=self.max_ctx, num_splits=self.num_splits)
         logits = self._forward(self.row_ids, self.row_positions, kv)
         ids, lps = native.argmax_logprob(logits, ids_out=self.ids_buf, logprob_out=self.lps_buf, scratch=self.argmax_scratch)
         return logits, ids, lps

@@ -687,7 +687,7 @@ class FlashCausalLM(Model):
         kv = KVArgs(cache=self.kv_cache, block_tables=batch.block_tables,
                     ctx_lens=torch.tensor(lens, dtype=torch.int32, device=dev), slots=up(slots),
                     max_q_len=max_q, max_ctx=max_ctx,
-                    num_splits=native.attn_num_splits(len(lens), self.num_kv_heads, self.num_heads, max_q, max_ctx),
+                    num_splits=native.attn_q_splits(len(lens), self.num_kv_heads, self.num_heads, max_q, max_ctx),
                     past_lens=native.past_lens_tensor(hits, dev) if FRESH_PREFILL_KV else None)
         return self._forward_prefill(batch.input_ids.index_select(0, up(take)), up(positions), cu_q, batch.max_seqlen, None,
                                      kv, (cu_q[1:] - 1).long())

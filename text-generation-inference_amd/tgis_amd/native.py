@@ -99,6 +99,7 @@ SIGNATURES = {
     "tgis_rope_kv_write_prefill_at_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64,
                                                    _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _vp] + _KV8_ARGS + [_vp]),
     "tgis_attn_num_splits": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _c_i64]),
+    "tgis_attn_num_splits_q": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _c_i64]),
     "tgis_attn_workspace_bytes": (_c_i64, [_c_i64, _c_int, _c_int, _c_int, _c_int]),
     "tgis_attn_paged": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int,
                                  _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_int, _vp, _c_i64, _vp]),
@@ -770,6 +771,19 @@ def rope_kv_write_prefill_at(qkv, cos, sin, positions, cu_seqlens, block_tables,
 
 def attn_num_splits(B: int, Hkv: int, H: int, max_q_len: int, max_ctx: int) -> int:
     return load_library().tgis_attn_num_splits(B, Hkv, H, max_q_len, max_ctx)
+
+
+def attn_num_splits_q(B: int, Hkv: int, H: int, max_q_len: int, max_ctx: int) -> int:
+    """Key splits of a launch with up to max_q_len q tokens per sequence (a verify step, a suffix behind reused pages)."""
+    return load_library().tgis_attn_num_splits_q(B, Hkv, H, max_q_len, max_ctx)
+
+
+def attn_q_splits(B: int, Hkv: int, H: int, max_q_len: int, max_ctx: int) -> int:
+    """What the model code asks: attn_num_splits at one q token, else attn_num_splits_q — whose answer below 1024 keys is 1
+    by the rule's own definition (fewer than 32 pages), so the library is only asked from there on."""
+    if max_q_len == 1:
+        return attn_num_splits(B, Hkv, H, 1, max_ctx)
+    return attn_num_splits_q(B, Hkv, H, max_q_len, max_ctx) if max_ctx >= 1024 else 1
 
 
 def attn_workspace_bytes(total_q: int, H: int, Hkv: int, D: int, num_splits: int) -> int:

@@ -1,5 +1,6 @@
 """What a verify step of prompt-lookup speculative decoding (FlashCausalLM(spec_tokens=K)) costs next to the plain decode step,
-on the synthetic cfg3 engine built as bench.py builds it, context 1024.
+on the synthetic cfg3 engine built as bench.py builds it, context 1024 (--ctx: another one; from 1024 keys on the verify
+step's attention takes the key splits of tgis_attn_num_splits_q, which `verify_num_splits` reports).
 
 Per (B, K), in one process: the median ms of the captured plain step and of the captured verify step (HIP events around graph
 replays); their ratio is the break-even number of tokens a verify step must emit.  Then two runs through generate_token, host
@@ -31,7 +32,7 @@ plain (K = 0) step, and of its verify step with every draft forced right and wit
 requests on the same model (the captured argmax in place of the chooser); and the chooser's launch alone (HIP events) on
 B and on B (K + 1) rows.  Seeded streams are reproducible, so the forced drafts are the plain run's own tokens.
 
-    python tools/spec_decode_bench.py [--config llama2-7b-gptq] [--tokens 32] > profiles/spec_decode_bench.json
+    python tools/spec_decode_bench.py [--config llama2-7b-gptq] [--tokens 32] [--ctx 1024] > profiles/spec_decode_bench.json
     python tools/spec_decode_bench.py --speculator 4096,4096,3 > profiles/spec_mlp_bench.json
     python tools/spec_decode_bench.py --sampled > profiles/spec_sampled_bench.json"""
 import argparse
@@ -271,6 +272,7 @@ def sampled_main(args, eng, cfg, dtype, quantize, tok, dev):
 
 
 def main():
+    global CTX, BS, KS
     ap = argparse.ArgumentParser()
     ap.add_argument("--speculator", default=None, metavar="E,I,P",
                     help="draft with a synthetic MLP speculator of these sizes (e.g. 4096,4096,3) instead of the lookup")
@@ -278,7 +280,13 @@ def main():
                     help="sampled requests (temperature + top-p) on a model with spec_sampling: B = 8, K = 3")
     ap.add_argument("--config", default="llama2-7b-gptq", choices=sorted(bench.CONFIGS))
     ap.add_argument("--tokens", type=int, default=32, help="tokens generated per request in the timed runs")
+    ap.add_argument("--ctx", type=int, default=CTX, help="prompt tokens per request")
+    ap.add_argument("--bs", default=None, metavar="B,B,...", help="batch sizes (default 1,4,8,16)")
+    ap.add_argument("--ks", default=None, metavar="K,K,...", help="drafts per request (default 3,7)")
     args = ap.parse_args()
+    CTX = args.ctx
+    BS = [int(b) for b in args.bs.split(",")] if args.bs else BS
+    KS = [int(k) for k in args.ks.split(",")] if args.ks else KS
     kw, quantize, dtype_s, _, _ = bench.CONFIGS[args.config]
     cfg, dtype, dev = LlamaConfig(**kw), getattr(torch, dtype_s), torch.device("cuda:0")
     tensors = llama_tensors(cfg, quantize, seed=1234, device=dev, dtype=dtype)
@@ -364,6 +372,8 @@ def main():
                     res[f"{name}_partings"] = partings
                     res[f"{name}_max_abs_logit_diff_where_equal"] = worst
                 res["verify_step_ms"] = round(replay_ms(lm._graphs[key + (K,)]), 4)
+                res["plain_num_splits"] = lm._graphs[key].num_splits
+                res["verify_num_splits"] = lm._graphs[key + (K,)].num_splits
             if spec is None:
                 res["break_even_tokens_per_verify_step"] = round(res["verify_step_ms"] / res["plain_step_ms"], 3)
             else:
