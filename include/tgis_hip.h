@@ -380,6 +380,27 @@ int tgis_attn_paged_kv8(const void* q, int64_t ld_q, const void* k_pool, const v
                         int64_t B, int H, int Hkv, int D, int64_t max_q_len, int64_t max_ctx, float scale, int dtype,
                         int num_splits, void* workspace, int64_t workspace_bytes, void* stream, int kv_dtype,
                         float k_scale, float v_scale);
+/* tgis_attn_paged with a mask over each sequence's own q rows: the verify step of speculative decoding over several
+ * candidates per request, which the reference flattens into one forward (utils/paged.py:162-330; its attention call is
+ * utils/flash_attn.py:43-78).  q_mask [total_q] uint64, one word per q row: bit j of q_mask[i] is set when q row i of a
+ * sequence attends to that sequence's q row j, whose key sits at cache position ctx_lens[b] - q_len_b + j.  Keys below
+ * ctx_lens[b] - q_len_b are always visible.  The mask is ANDed with the causal bound: a set bit above the row's own index is
+ * ignored; a row with no visible key at all gives zeros.  Any per-row bitmask is served, not only trees.
+ * Only the decode form (max_q_len * next_pow2(min(H / Hkv, 16)) <= 64, so q_len <= 64: one word per row); anything else, or a
+ * NULL q_mask, is TGIS_EINVAL before any launch.  Key splits (callers take num_splits from tgis_attn_num_splits_q), workspace
+ * (tgis_attn_workspace_bytes), both merges and `out` are those of tgis_attn_paged.  The mask changes scores only: every load
+ * the launch issues is one tgis_attn_paged issues for the same ctx_lens and cu_seqlens_q. */
+int tgis_attn_paged_tree(const void* q, int64_t ld_q, const void* k_pool, const void* v_pool, const int32_t* block_tables,
+                         int64_t max_pages, const int32_t* ctx_lens, const int32_t* cu_seqlens_q, void* out, int64_t ld_out,
+                         int64_t B, int H, int Hkv, int D, int64_t max_q_len, int64_t max_ctx, float scale, int dtype,
+                         int num_splits, void* workspace, int64_t workspace_bytes, void* stream, const uint64_t* q_mask);
+/* tgis_attn_paged_tree over pools of element kv_dtype, as tgis_attn_paged_kv8 is to tgis_attn_paged (utils/flash_attn.py:43-78). */
+int tgis_attn_paged_tree_kv8(const void* q, int64_t ld_q, const void* k_pool, const void* v_pool,
+                             const int32_t* block_tables, int64_t max_pages, const int32_t* ctx_lens,
+                             const int32_t* cu_seqlens_q, void* out, int64_t ld_out, int64_t B, int H, int Hkv, int D,
+                             int64_t max_q_len, int64_t max_ctx, float scale, int dtype, int num_splits, void* workspace,
+                             int64_t workspace_bytes, void* stream, int kv_dtype, float k_scale, float v_scale,
+                             const uint64_t* q_mask);
 
 /* ---- KV-cache statistics (replaces nothing in the reference, which has no quantised cache: the calibration pass of the
  *      one-byte cache, utils/kv_cache.py) -------------------------------------------------------------- */
@@ -462,6 +483,56 @@ int tgis_spec_accept_sampled(const int64_t* chosen_ids, const float* chosen_logp
  * (the buffer that travels to the host).  One workgroup per request. */
 int tgis_spec_propose(const int64_t* all_input_ids, int64_t ld_all, const int64_t* position_ids, int64_t K, int64_t N,
                       int64_t* drafts, int32_t* hits, int32_t* hits_copy, int64_t B, void* stream);
+
+/* ---- several candidates per request: the verify step as a token tree ------------------------------
+ * The reference verifies top_k candidates of n_predict tokens per request in one forward and keeps the one with the longest
+ * correct prefix (utils/paged.py:162-330, `best_guess = n_correct.argmax(1)`).  Here: C candidates (1 <= C <= 8) of K drafts
+ * (0 <= K <= 7; C > 1 needs K >= 1), R = 1 + C K <= 64 rows per request.  With pos the position of the latest token, row 0 is
+ * that token (rotary position pos, cache position pos) and row 1 + c K + j is draft j of candidate c: rotary position
+ * pos + 1 + j (its depth), cache position pos + 1 + c K + j (its row).  A row attends to the cache below pos, to row 0 and to
+ * its own candidate's rows up to itself (tgis_attn_paged_tree).  No allocation, no sync; B = 0 returns TGIS_OK. */
+/* The R-row form of tgis_spec_stage (utils/paged.py prepare_inputs_with_speculation).  drafts [B, C, K] int64.  Row
+ * r = b R + i: input_ids[r] = the row's token; positions_out[r] = its rotary position (by depth); slots[r] = the slot of its
+ * cache position (by row), the table index clamped as tgis_spec_stage clamps it; ctx_lens[b] = positions[b] + R.  C = 1 is
+ * tgis_spec_stage bit for bit.  (C is an argument tgis_spec_stage does not have.) */
+int tgis_spec_tree_stage(const int32_t* positions, const int64_t* latest_ids, const int64_t* drafts, int64_t C, int64_t K,
+                         const int32_t* block_tables, int64_t max_pages, int64_t* input_ids, int32_t* positions_out,
+                         int32_t* slots, int32_t* ctx_lens, int64_t B, void* stream);
+/* tgis_spec_accept over C candidates (utils/paged.py process_outputs_with_speculation: the first maximum of n_correct).
+ * argmax_ids int64 / argmax_logprobs f32 [B, R]; drafts [B, C, K].  a_c = the longest j such that for every draft i < j of
+ * candidate c the choice behind its parent row equals it; the parent of draft 0 is row 0, of draft i > 0 row 1 + c K + i - 1.
+ * best [B] int32 = the lowest c with the largest a_c.  With a = a_best, request b emits the a + 1 choices along that path:
+ * argmax_ids[b][0], then those behind drafts 0 .. a - 1 of candidate best.  n_emit, out_ids / out_logprobs [B, K + 1],
+ * latest_ids, position_ids, all_input_ids, cu_seqlens, stage_ids and stage_positions are those of tgis_spec_accept, NULL
+ * where it allows NULL.  One workgroup serves the batch.  C = 1 is tgis_spec_accept bit for bit (best = 0). */
+int tgis_spec_tree_accept(const int64_t* argmax_ids, const float* argmax_logprobs, const int64_t* drafts, int64_t C, int64_t K,
+                          int32_t* n_emit, int32_t* best, int64_t* out_ids, float* out_logprobs, int64_t* latest_ids,
+                          int64_t* position_ids, int64_t* all_input_ids, int64_t ld_all, int32_t* cu_seqlens,
+                          int64_t* stage_ids, int32_t* stage_positions, int64_t B, void* stream);
+/* Behind tgis_spec_tree_accept: the cache as if the best candidate alone had been verified (the reference keeps the best
+ * candidate's cache entries and frees the others', utils/paged.py:303-315).  For every request with best > 0 and n_emit > 1, the keys and values at
+ * cache position pos + 1 + best K + j move to pos + 1 + j, j < n_emit - 1, in every layer and kv head, in ONE launch.
+ *   k_pool / v_pool: layer 0's pools, [num_pages, Hkv, 32 D] elements of elem_bytes (2: f16 / bf16, 1: e4m3 codes) in the
+ *   orders of the KV page layout (K moves as 8-element runs, V element by element); layer l's pools start layer_stride
+ *   ELEMENTS behind layer l - 1's (16-byte aligned).  Bytes are copied, nothing is requantised.
+ *   new_positions [B] int32: the positions tgis_spec_tree_accept left (its stage_positions): pos = new_positions[b] - n_emit[b].
+ *   best / n_emit [B] int32 as tgis_spec_tree_accept wrote them, read on the device (the call needs no host value).
+ * Source and destination positions never overlap: at most K positions move (n_emit - 1 <= K), the destinations lie in
+ * [pos + 1, pos + K] and, with best >= 1, every source lies at pos + 1 + K or beyond (best K >= K positions behind its
+ * destination), so no ordering between the copies is needed.  best is clamped to [0, C - 1], n_emit to [1, K + 1], table indices to
+ * [0, max_pages - 1] and page ids to [0, num_pages - 1]: a wrong value can never address past a request's table or the pool. */
+int tgis_spec_tree_commit(void* k_pool, void* v_pool, int64_t layer_stride, int64_t num_layers, int64_t num_pages,
+                          const int32_t* block_tables, int64_t max_pages, const int32_t* new_positions, const int32_t* best,
+                          const int32_t* n_emit, int64_t C, int64_t K, int64_t B, int Hkv, int D, int elem_bytes,
+                          void* stream);
+/* tgis_spec_propose for C candidates (stands where the reference asks its speculator for top_k candidates, utils/paged.py
+ * prepare_inputs_with_speculation).  Match sites are visited with n from N down to 1 and, within one n, from the latest site
+ * to the earliest; a site becomes the next candidate if the first token of its continuation differs from the first token of
+ * every candidate already taken, so candidates part at depth 1.  drafts [B, C, K] int64, zeros for candidates that were not
+ * found (and where the context ends); hits[b] = the n of the first candidate, 0 if there is none; hits_copy as in
+ * tgis_spec_propose.  One workgroup per request.  C = 1 is tgis_spec_propose bit for bit. */
+int tgis_spec_propose_multi(const int64_t* all_input_ids, int64_t ld_all, const int64_t* position_ids, int64_t C, int64_t K,
+                            int64_t N, int64_t* drafts, int32_t* hits, int32_t* hits_copy, int64_t B, void* stream);
 
 /* ---- MLP speculator, the reference's drafter (models/paged_causal_lm.py:481-562, utils/paged.py:20-38,208) ------------
  * Head i of K <= n_predict:  s = proj_i x + alpha emb_i[t];  x = gelu_erf(rmsln_i(s));  t = argmax(head_i x), starting from

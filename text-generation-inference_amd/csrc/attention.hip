@@ -43,8 +43,15 @@ namespace {
 // PIPE: two pages of K/V loads in flight per wave (twice the fragment registers)
 // KV: the pool's element, T (16-bit cache) or uint8_t (e4m3 codes, kv_layout.h): a one-byte fragment is an 8-byte nontemporal
 // load widened to T in registers; the MFMAs, Q and P stay in T
-template <typename T, typename KV, int D, int NW, int CH, bool PIPE>
-__global__ __launch_bounds__(64 * NW) void attn_paged_kernel(AttnArgs a) {
+// TREE (tgis_attn_paged_tree: one-chunk blocks of 4 waves, no PIPE): the argument block carries q_mask, one 64-bit word per q
+// row.  Keys below ctx - q_len are visible to every row; the key of the sequence's q row j (cache position ctx - q_len + j) is
+// visible to q row i when bit j of q_mask[i] is set AND j <= i.  The fully visible pages then end at ctx - q_len and every page
+// from there on takes the masked body, which tests one more bit per score.  The mask changes scores only: the pages a block
+// walks and every address it loads from are those of the TREE = false kernel for the same ctx_lens and cu_seqlens_q (a page
+// that is full but masked goes through load_page_part with nv = 32, which requests what load_page requests).
+template <typename T, typename KV, int D, int NW, int CH, bool PIPE, bool TREE = false>
+__global__ __launch_bounds__(64 * NW) void attn_paged_kernel(std::conditional_t<TREE, AttnTreeArgs, AttnArgs> a) {
+    static_assert(!TREE || (CH == 1 && !PIPE), "the tree variant exists for one-chunk blocks without the page pipeline");
     using V8 = typename VecT<T>::x8;
     constexpr int KS = D / 32;  // k-steps of the QK^T MFMA
     constexpr int NB = D / 16;  // 16-row blocks of O^T
@@ -99,6 +106,9 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(AttnArgs a) {
         col_valid[ch] = (g < a.Gc) && ((hc0 + ch) * 16 + g < a.G) && (t0 + tq < q_len);
         kmax[ch] = col_valid[ch] ? (ctx - q_len + t0 + tq + 1) : 0;
     }
+    // TREE: this column's mask word; bit j is the key at cache position ctx - q_len + j
+    uint64_t qmask = 0;
+    if constexpr (TREE) qmask = col_valid[0] ? a.q_mask[q0 + t0 + tq] : 0;
     const int kend = ctx - q_len + min(q_len, t0 + a.TQ);  // keys needed by any column of the tile
     const int pages = (kend + 31) >> 5;
     const int pps = (pages + a.NS - 1) / a.NS;
@@ -197,7 +207,15 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(AttnArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float v = s[t][r] * a.scale_log2;
-                    if (!FULL) v = (kp0 + t * 16 + r < kmax[ch]) ? v : NEG_BIG;
+                    if (!FULL) {
+                        bool vis = kp0 + t * 16 + r < kmax[ch];
+                        if constexpr (TREE) {
+                            // (a key at or past kmax may lie 64 or more behind the first q row: the shift count is masked)
+                            const int rel = kp0 + t * 16 + r - (ctx - q_len);
+                            vis = vis && (rel < 0 || ((qmask >> (rel & 63)) & 1));
+                        }
+                        v = vis ? v : NEG_BIG;
+                    }
                     s[t][r] = v;
                     tmax = fmaxf(tmax, v);
                 }
@@ -232,7 +250,8 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(AttnArgs a) {
         ATTN_STAMP(3);  // (kept once: the wave's first page applied)
     };
     // pages below kfull are visible in full to every column of the tile (the tile's first token sees kfull keys)
-    const int kfull = ctx - q_len + t0 + 1;
+    // (TREE: the mask may hide any of the sequence's q rows from the tile, row 0 included)
+    const int kfull = TREE ? ctx - q_len : ctx - q_len + t0 + 1;
     int p = pbeg + w;
     ATTN_STAMP(2);  // q requested, first table entry in
     // The partly visible pages of this wave (decode: the sequence's last page) go FIRST (round 4): the softmax is order-
@@ -589,6 +608,22 @@ static void launch_attn_one(const AttnArgs& a, dim3 grid, hipStream_t st) {
     launch_attn_pipe<T, KV, D, NW, CH, false>(a, grid, st);
 }
 
+// the second launch of a split call that has no arrival counters (multi-chunk blocks, or none were free)
+template <typename T, int D>
+static int launch_combine(const AttnArgs& a, int64_t total_q, const int32_t* q_end, hipStream_t st) {
+    if (a.NS > 1 && !a.counters) {
+        const int64_t rows = total_q * a.H;
+        if (a.NS <= 8)
+            hipLaunchKernelGGL((attn_combine_kernel<T, D, 8>), dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, st, a.ws_o,
+                               a.ws_ml, (T*)a.out, a.NS, a.H, a.out_frag, rows, q_end);
+        else
+            hipLaunchKernelGGL((attn_combine_kernel<T, D, 0>), dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, st, a.ws_o,
+                               a.ws_ml, (T*)a.out, a.NS, a.H, a.out_frag, rows, q_end);
+        TGIS_CHECK_LAUNCH();
+    }
+    return TGIS_OK;
+}
+
 template <typename T, typename KV, int D>
 static int launch_attn(const AttnArgs& a, dim3 grid, int64_t total_q, const int32_t* q_end, hipStream_t st, int nw,
                        int ch) {
@@ -605,17 +640,19 @@ static int launch_attn(const AttnArgs& a, dim3 grid, int64_t total_q, const int3
         else return by_int<1, 2, 4>(nw, "tgis_attn_paged: waves per block", one);
     });
     if (rc != TGIS_OK) return rc;
-    if (a.NS > 1 && !a.counters) {
-        const int64_t rows = total_q * a.H;
-        if (a.NS <= 8)
-            hipLaunchKernelGGL((attn_combine_kernel<T, D, 8>), dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, st, a.ws_o,
-                               a.ws_ml, (T*)a.out, a.NS, a.H, a.out_frag, rows, q_end);
-        else
-            hipLaunchKernelGGL((attn_combine_kernel<T, D, 0>), dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, st, a.ws_o,
-                               a.ws_ml, (T*)a.out, a.NS, a.H, a.out_frag, rows, q_end);
-        TGIS_CHECK_LAUNCH();
-    }
-    return TGIS_OK;
+    return launch_combine<T, D>(a, total_q, q_end, st);
+}
+
+// tgis_attn_paged_tree: the decode form only, as one-chunk blocks of 4 waves — what tgis_attn_paged launches by default at
+// q_len > 1.  The A/B hooks of that launch (TGIS_ATTN_NW, TGIS_ATTN_CH, TGIS_ATTN_PIPE, TGIS_ATTN_XCD) are NOT read here: a
+// measurement that sets one of them compares the causal launch in another configuration with this one as it always is.
+template <typename T, typename KV, int D>
+static int launch_attn_tree(const AttnTreeArgs& a, dim3 grid, int64_t total_q, const int32_t* q_end, hipStream_t st) {
+    constexpr int NW = 4;
+    const size_t lds = (size_t)(NW * D * 16 + NW * 2 * 16) * sizeof(float);  // <= 32.5 KiB: no attribute to raise
+    hipLaunchKernelGGL((attn_paged_kernel<T, KV, D, NW, 1, false, true>), grid, dim3(64 * NW), lds, st, a);
+    TGIS_CHECK_LAUNCH();
+    return launch_combine<T, D>(a, total_q, q_end, st);
 }
 
 }  // namespace
@@ -825,7 +862,7 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
                            const int32_t* cu_seqlens_q, void* out, int64_t ld_out, int64_t B, int H, int Hkv, int D,
                            int64_t max_q_len, int64_t max_ctx, float scale, int dtype, int num_splits,
                            void* workspace, int64_t workspace_bytes, void* stream, int kv_dtype, float k_scale,
-                           float v_scale) {
+                           float v_scale, bool tree = false, const uint64_t* q_mask = nullptr) {
     TGIS_CHECK_ARG(q && k_pool && v_pool && block_tables && ctx_lens && cu_seqlens_q && out,
                    "tgis_attn_paged: null tensor");
     TGIS_CHECK_ARG(H > 0 && Hkv > 0 && H % Hkv == 0, "tgis_attn_paged: H (%d) must be a multiple of Hkv (%d)", H, Hkv);
@@ -845,9 +882,16 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
     TGIS_CHECK_ARG(num_splits == 1 || !prefill_form,
                    "tgis_attn_paged: key splits are for the decode form (max_q_len * padded group size <= 64, here %ld * %d): "
                    "the prefill form takes none", (long)max_q_len, g.Gp);
+    if (tree) {
+        TGIS_CHECK_ARG(q_mask, "tgis_attn_paged_tree: null q_mask");
+        TGIS_CHECK_ARG(!prefill_form,
+                       "tgis_attn_paged_tree: only the decode form is served (max_q_len * padded group size <= 64, here %ld * "
+                       "%d): one 64-bit mask word per q row", (long)max_q_len, g.Gp);
+    }
     if (B == 0) return TGIS_OK;
     hipStream_t st = (hipStream_t)stream;
-    AttnArgs a;
+    AttnTreeArgs a;
+    a.q_mask = q_mask;
     a.q = q;
     a.ld_q = ld_q;
     a.kpool = k_pool;
@@ -867,7 +911,7 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
     while ((1 << a.Gp_shift) < g.Gp) ++a.Gp_shift;
     a.TQ = g.TQ;
     a.HC = g.HC;
-    const int ch = chunks_per_block(g.HC, max_q_len);
+    const int ch = tree ? 1 : chunks_per_block(g.HC, max_q_len);  // (the tree variant: one-chunk blocks at any q_len)
     a.HCB = (g.HC + ch - 1) / ch;
     a.NS = num_splits;
     a.scale_log2 = kv8 ? scale * k_scale * 1.4426950408889634f : scale * 1.4426950408889634f;
@@ -902,6 +946,20 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
     TGIS_CHECK_ARG(q_tiles <= 2147483647LL && (int64_t)Hkv * a.HCB <= 65535 && B * num_splits <= 65535,
                    "tgis_attn_paged: grid too large");
     dim3 grid((unsigned)q_tiles, (unsigned)(Hkv * a.HCB), (unsigned)(B * num_splits));
+    // the combine launch of a q_len > 1 call runs over B * max_q_len rows: it reads the real count, cu_seqlens_q[B]
+    const int32_t* q_end = max_q_len > 1 ? cu_seqlens_q + B : nullptr;
+    if (tree) {
+        a.xcd_remap = 0;
+        TgisTimedScope timed(TGIS_OP_ATTN, st);
+        return by_dtype(dtype, [&](auto t) {
+            using T = type_of<decltype(t)>;
+            return by_kv<T>(kv8, [&](auto kv) {
+                return by_int<128, 96, 64>(D, "tgis_attn_paged_tree: head_dim", [&](auto d) {
+                    return launch_attn_tree<T, type_of<decltype(kv)>, decltype(d)::value>(a, grid, total_q, q_end, st);
+                });
+            });
+        });
+    }
     {
         static const bool xcd_off = getenv("TGIS_ATTN_XCD") && atoi(getenv("TGIS_ATTN_XCD")) == 0;  // A/B hook
         a.xcd_remap = (!xcd_off && max_q_len == 1 && q_tiles == 1 && a.HCB > 1 && (B * num_splits * Hkv) % 8 == 0) ? 1 : 0;
@@ -917,8 +975,6 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
         nw = (v == 1 || v == 2 || v == 3 || v == 8) ? v : 4;
         if (ch > 1 && (nw > 4 || nw == 3)) nw = 4;
     }
-    // the combine launch of a q_len > 1 call runs over B * max_q_len rows: it reads the real count, cu_seqlens_q[B]
-    const int32_t* q_end = max_q_len > 1 ? cu_seqlens_q + B : nullptr;
     TgisTimedScope timed(TGIS_OP_ATTN, st);
     return by_dtype(dtype, [&](auto t) {
         using T = type_of<decltype(t)>;
@@ -952,3 +1008,26 @@ extern "C" int tgis_attn_paged_kv8(const void* q, int64_t ld_q, const void* k_po
                            k_scale, v_scale);
 }
 
+
+// tgis_attn_paged / tgis_attn_paged_kv8 with a per-row mask over the sequence's own q rows (the verify step of speculative
+// decoding over several candidates per request: utils/paged.py:162-330 flattens them into one forward).
+extern "C" int tgis_attn_paged_tree(const void* q, int64_t ld_q, const void* k_pool, const void* v_pool,
+                                    const int32_t* block_tables, int64_t max_pages, const int32_t* ctx_lens,
+                                    const int32_t* cu_seqlens_q, void* out, int64_t ld_out, int64_t B, int H, int Hkv, int D,
+                                    int64_t max_q_len, int64_t max_ctx, float scale, int dtype, int num_splits,
+                                    void* workspace, int64_t workspace_bytes, void* stream, const uint64_t* q_mask) {
+    return attn_paged_impl(q, ld_q, k_pool, v_pool, block_tables, max_pages, ctx_lens, cu_seqlens_q, out, ld_out, B, H, Hkv, D,
+                           max_q_len, max_ctx, scale, dtype, num_splits, workspace, workspace_bytes, stream, TGIS_KV_MODEL,
+                           1.f, 1.f, true, q_mask);
+}
+
+extern "C" int tgis_attn_paged_tree_kv8(const void* q, int64_t ld_q, const void* k_pool, const void* v_pool,
+                                        const int32_t* block_tables, int64_t max_pages, const int32_t* ctx_lens,
+                                        const int32_t* cu_seqlens_q, void* out, int64_t ld_out, int64_t B, int H, int Hkv,
+                                        int D, int64_t max_q_len, int64_t max_ctx, float scale, int dtype, int num_splits,
+                                        void* workspace, int64_t workspace_bytes, void* stream, int kv_dtype, float k_scale,
+                                        float v_scale, const uint64_t* q_mask) {
+    return attn_paged_impl(q, ld_q, k_pool, v_pool, block_tables, max_pages, ctx_lens, cu_seqlens_q, out, ld_out, B, H, Hkv, D,
+                           max_q_len, max_ctx, scale, dtype, num_splits, workspace, workspace_bytes, stream, kv_dtype,
+                           k_scale, v_scale, true, q_mask);
+}

@@ -24,6 +24,12 @@ struct AttnArgs {
     float inv_v_scale;   // one-byte cache: 1 / v_scale, folded into the softmax normaliser (kv_layout.h)
 };
 
+// tgis_attn_paged_tree: the argument block of the TREE variant of the decode kernel.  The mask rides behind the fields every
+// other kernel takes, in a type of its own: the argument blocks of the non-tree kernels stay what they are.
+struct AttnTreeArgs : AttnArgs {
+    const uint64_t* q_mask;  // [total_q]: bit j of word i = q row i of a sequence attends to that sequence's q row j
+};
+
 constexpr float NEG_BIG = -1.0e30f;
 
 // prefill kernel launcher (attention_prefill.hip); `a` carries the geometry filled in by tgis_attn_paged

@@ -26,6 +26,8 @@ class KVArgs:
     fresh_prefill: bool = False        # every sequence starts at cache position 0: page-wise cache writes
     past_lens: Optional[torch.Tensor] = None  # [B] int32: tokens already cached on reused pages (multiples of 32) in
     #                                    front of this prefill's: page-wise cache writes starting behind them
+    q_mask: Optional[torch.Tensor] = None  # [T] int64, one 64-bit word per q row: which of its sequence's q rows the row
+    #                                    attends to (a tree verify step; native.attn_paged's q_mask).  None: causal
 
 
 def layer_pools(kv: KVArgs, layer_id: int):
@@ -66,6 +68,8 @@ def attend(qkv, kv: KVArgs, layer_id: int, H: int, Hkv: int, D: int, scale: floa
         # the launcher sizes its records for B * max_q_len rows: T itself except behind ragged suffixes (prefix reuse)
         rows = max(T, kv.block_tables.shape[0] * kv.max_q_len)
         ws.ensure(native.attn_workspace_bytes(rows, H, Hkv, D, kv.num_splits))
+    if kv.q_mask is not None:
+        scales = dict(scales, q_mask=kv.q_mask)
     native.attn_paged(qkv, qkv.stride(0), k_pool, v_pool, kv.block_tables, kv.ctx_lens, cu_seqlens_q, attn_output,
                       kv.block_tables.shape[0], H, Hkv, D, kv.max_q_len, kv.max_ctx, scale, kv.num_splits, ws, **scales)
     return attn_output

@@ -1,7 +1,8 @@
 """The captured decode step of FlashCausalLM: static buffers + HIP graph per (batch-size bucket, table width), the choice
 between one graph and a chain of segments under tensor parallelism, and the memory pool the captures share.  With
-speculative decoding on (utils/spec_decode.py) the verify step is captured the same way, per (bucket, table width, K); what
-drafts and what follows such a step is models/speculation.py.
+speculative decoding on (utils/spec_decode.py) the verify step is captured the same way, per (bucket, table width, K) — with
+several candidates per request per (bucket, table width, K, C), a token tree of 1 + C K rows per request; what drafts and what
+follows such a step is models/speculation.py.
 
 The state stays on the model, where bench.py, the tests and tools/ read and set it: `lm._graphs`, `lm.graph_captures`,
 `lm.use_graphs`, `lm.max_graphs`, `lm.graph_mode`, `lm.graph_pool`, `lm.tp_world`, `lm.ranks` (utils/rank_group.py)."""
@@ -14,6 +15,7 @@ from tgis_amd import native
 from tgis_amd.models.custom_modeling.flash_common import KVArgs
 from tgis_amd.utils.graph_segments import SegmentedGraph, no_gc_during_capture
 from tgis_amd.utils.kv_cache import PAGE
+from tgis_amd.utils.spec_decode import tree_q_mask, tree_rows
 
 logger = logging.getLogger(__name__)
 
@@ -65,20 +67,28 @@ def _collective_capture_works(lm) -> bool:
 class _SpecOut:
     """What a greedy step of a speculating model sends to the host, in ONE device buffer and one copy to its pinned mirror:
     the emitted ids int64 [B, K + 1] and their logprobs f32 [B, K + 1] (tgis_spec_accept), how many of them count, n_emit
-    int32 [B], and the hits int32 [B] of the lookup that drafted the next step (tgis_spec_propose)."""
+    int32 [B], and the hits int32 [B] of the lookup that drafted the next step (tgis_spec_propose).  `best`: a tree verify
+    step adds the winning candidate int32 [B] (tgis_spec_tree_accept) behind them."""
 
-    def __init__(self, B: int, K: int, dev):
+    def __init__(self, B: int, K: int, dev, best: bool = False):
         R = B * (K + 1)
         self.K1 = K + 1
-        self.buf = torch.zeros(R * 12 + B * 8, dtype=torch.uint8, device=dev)
-        self.host = torch.zeros(R * 12 + B * 8, dtype=torch.uint8).pin_memory()
+        size = R * 12 + B * (12 if best else 8)
+        self.buf = torch.zeros(size, dtype=torch.uint8, device=dev)
+        self.host = torch.zeros(size, dtype=torch.uint8).pin_memory()
         self.ids, self.lps, self.n_emit, self.hits = self._views(self.buf, B, R)
+        self.best = self.buf[R * 12 + B * 8:].view(torch.int32) if best else None
         self.ready = torch.cuda.Event()
 
     @staticmethod
     def _views(buf, B, R):
         return (buf[:R * 8].view(torch.int64), buf[R * 8:R * 12].view(torch.float32),
-                buf[R * 12:R * 12 + B * 4].view(torch.int32), buf[R * 12 + B * 4:].view(torch.int32))
+                buf[R * 12:R * 12 + B * 4].view(torch.int32), buf[R * 12 + B * 4:R * 12 + B * 8].view(torch.int32))
+
+    def read_best(self, n: int):
+        """best [n] of the first n requests as a host list (behind `read`, which waited for the copy)."""
+        B = self.n_emit.numel()
+        return self.host[B * self.K1 * 12 + B * 8:].view(torch.int32)[:n].tolist()
 
     def fetch(self):
         self.host.copy_(self.buf, non_blocking=True)
@@ -97,6 +107,7 @@ class _DecodeGraph:
     """Static buffers + captured HIP graph of one decode step for a (batch-size bucket, table width) pair."""
 
     K = 0  # drafts per request: none in the plain step
+    C = 1  # draft chains per request (more than one: _TreeVerifyGraph)
 
     def __init__(self, lm, B: int, width: int):
         self._init_buffers(lm, B, width, B)
@@ -242,19 +253,21 @@ class _VerifyGraph(_DecodeGraph):
     decode form, with key splits from 1024 keys on), then the greedy choice behind every row.  `input_ids` / `positions` stay the
     per-request inputs, as in the plain step, so that the launch after either step can leave the next inputs in them."""
 
-    def __init__(self, lm, B: int, width: int, K: int):
-        R = B * (K + 1)
+    def __init__(self, lm, B: int, width: int, K: int, C: int = 1):
+        """C > 1 is _TreeVerifyGraph's: C chains per request, 1 + C K rows, drafts [B, C, K]."""
+        R1 = tree_rows(C, K)  # rows per request (K + 1 for the one chain)
+        R = B * R1
         self._init_buffers(lm, B, width, R)
         dev = lm.device
-        self.K = K
-        self.drafts = torch.zeros((B, K), dtype=torch.int64, device=dev)
+        self.K, self.C, self.R1 = K, C, R1
+        self.drafts = torch.zeros((B, K) if C == 1 else (B, C, K), dtype=torch.int64, device=dev)
         self.row_ids = torch.zeros(R, dtype=torch.int64, device=dev)
         self.row_positions = torch.zeros(R, dtype=torch.int32, device=dev)
-        self.ctx = torch.full((B,), K + 1, dtype=torch.int32, device=dev)
-        self.cu_q = torch.arange(B + 1, dtype=torch.int32, device=dev) * (K + 1)
+        self.ctx = torch.full((B,), R1, dtype=torch.int32, device=dev)
+        self.cu_q = torch.arange(B + 1, dtype=torch.int32, device=dev) * R1
         # the decode form takes key splits over a long context (tgis_attn_num_splits_q); captured and eager steps share them
-        self.num_splits = native.attn_q_splits(B, lm.num_kv_heads, lm.num_heads, K + 1, self.max_ctx)
-        self.spec_out = _SpecOut(B, K, dev)
+        self.num_splits = native.attn_q_splits(B, lm.num_kv_heads, lm.num_heads, R1, self.max_ctx)
+        self.spec_out = _SpecOut(B, K, dev, best=C > 1)
 
     def _step(self):
         lm = self.lm
@@ -274,5 +287,28 @@ class _VerifyGraph(_DecodeGraph):
         self.drafts[:n].copy_(drafts, non_blocking=True)
         self._stage(input_ids, position_ids, block_tables)
         logits, ids, lps = self._run()
-        r = n * (self.K + 1)
+        r = n * self.R1
         return logits[:r], ids[:r], lps[:r]
+
+
+class _TreeVerifyGraph(_VerifyGraph):
+    """The verify step over C candidates per request for a (batch-size bucket, table width, K, C) key: R = 1 + C K rows per
+    request as a token tree (utils/spec_decode.py: row 0 the latest token, row 1 + c K + j draft j of candidate c, rotary
+    position by depth, cache position by row), through the same generic q_len > 1 forward; the attention takes the static
+    `q_mask` (tgis_attn_paged_tree) under which a row sees the cache, row 0 and its own candidate up to itself.  `run` is
+    _VerifyGraph's, on drafts [n, C, K]."""
+
+    def __init__(self, lm, B: int, width: int, K: int, C: int):
+        super().__init__(lm, B, width, K, C)
+        # built once on the host: every request of the bucket has the same tree
+        self.q_mask = torch.tensor(tree_q_mask(C, K) * B, dtype=torch.int64, device=lm.device)
+
+    def _step(self):
+        lm = self.lm
+        native.spec_tree_stage(self.positions, self.input_ids, self.drafts, self.block_tables, self.row_ids,
+                               self.row_positions, self.slots, self.ctx)
+        kv = KVArgs(cache=lm.kv_cache, block_tables=self.block_tables, ctx_lens=self.ctx, slots=self.slots,
+                    max_q_len=self.R1, max_ctx=self.max_ctx, num_splits=self.num_splits, q_mask=self.q_mask)
+        logits = self._forward(self.row_ids, self.row_positions, kv)
+        ids, lps = native.argmax_logprob(logits, ids_out=self.ids_buf, logprob_out=self.lps_buf, scratch=self.argmax_scratch)
+        return logits, ids, lps

@@ -27,7 +27,7 @@ import torch
 
 from tgis_amd import native
 from tgis_amd.models.custom_modeling.flash_common import KVArgs
-from tgis_amd.models.decode_graph import _DecodeGraph, _VerifyGraph, renew_unheld_pool
+from tgis_amd.models.decode_graph import _DecodeGraph, _TreeVerifyGraph, _VerifyGraph, renew_unheld_pool
 from tgis_amd.models.model import Model
 from tgis_amd.models.speculation import LookupDrafter, MLPDrafter, spec_step
 from tgis_amd.models.types import Batch, GenerateError
@@ -37,7 +37,8 @@ from tgis_amd.utils.kv_cache import (KV_SCALES_HEADROOM, PAGE, OutOfPages, Paged
                                      agree_kv_prefix_reuse, agree_kv_scales, kv_pool_dtype, kv_scales_stats,
                                      pages_for_budget, parse_kv_cache_dtype, parse_kv_prefix_reuse)
 from tgis_amd.utils.rank_group import RankGroup
-from tgis_amd.utils.spec_decode import (check_spec_world, fallback_cause, may_ever_verify, new_stats, parse_spec_ngram,
+from tgis_amd.utils.spec_decode import (check_spec_candidates, check_spec_world, check_tree_rows, fallback_cause,
+                                        may_ever_verify, new_stats, parse_spec_candidates, parse_spec_ngram,
                                         parse_spec_sampling, parse_spec_tokens)
 from tgis_amd.utils.token_types import InputTokens, TokenInfo
 from tgis_amd.utils.tokens import HeterogeneousNextTokenChooser, get_input_tokens_info, get_token_info
@@ -83,6 +84,8 @@ class FlashCausalLMBatch(Batch):
     # (0 = none; an MLP drafter's are all ones)
     spec_tokens: int = 0
     spec_model: Optional[Any] = None
+    # candidates per request (1: one chain, `spec_drafts` [B, K]; C > 1: a token tree, `spec_drafts` [B, C, K])
+    spec_candidates: int = 1
     spec_drafts: Optional[torch.Tensor] = None
     spec_hits: Optional[torch.Tensor] = None
     # with a drafter that needs it (the MLP speculator): per request the post-norm hidden state that predicted its latest
@@ -174,14 +177,15 @@ class FlashCausalLMBatch(Batch):
             self.spec_model.redraft(self)
 
     def can_verify(self) -> bool:
-        """Whether a batch of this size can verify at all (its bucket times K + 1 rows): if not, nobody drafts for it."""
-        return may_ever_verify(self.spec_tokens, graph_bucket(len(self)))
+        """Whether a batch of this size can verify at all (its bucket times 1 + C K rows): if not, nobody drafts for it."""
+        return may_ever_verify(self.spec_tokens, graph_bucket(len(self)), self.spec_candidates)
 
     def ensure_spec_buffers(self, emb_dim: int = 0, dtype=None):
         """The batch's own `spec_drafts` / `spec_hits` for its present size (and `spec_hidden`, given its width)."""
         B, dev = len(self), self.position_ids.device
         if self.spec_drafts is None or self.spec_drafts.shape[0] != B:
-            self.spec_drafts = torch.zeros((B, self.spec_tokens), dtype=torch.int64, device=dev)
+            shape = (B, self.spec_tokens) if self.spec_candidates == 1 else (B, self.spec_candidates, self.spec_tokens)
+            self.spec_drafts = torch.zeros(shape, dtype=torch.int64, device=dev)
             self.spec_hits = torch.zeros(B, dtype=torch.int32, device=dev)
         if emb_dim and (self.spec_hidden is None or self.spec_hidden.shape[0] != B):
             self.spec_hidden = torch.zeros((B, emb_dim), dtype=dtype, device=dev)
@@ -357,6 +361,7 @@ class FlashCausalLMBatch(Batch):
             total_lengths=total_lengths, all_input_ids_tensor=all_input_ids_tensor,
             next_token_chooser=next_token_chooser, pad_token_id=first.pad_token_id,
             kv_cache=first.kv_cache, pages=None, spec_tokens=first.spec_tokens, spec_model=first.spec_model,
+            spec_candidates=first.spec_candidates,
             spec_hidden=torch.cat([b.spec_hidden for b in batches]) if first.spec_hidden is not None else None)
         merged.pages = pages
         try:
@@ -439,6 +444,8 @@ class FlashCausalLM(Model):
     drafter = speculator = None
     # whether batches that sample or carry processors verify drafts too (set by the constructor)
     spec_sampling = False
+    # draft chains a greedy request brings to a verify step (set by the constructor); 1 = the single chain
+    spec_candidates = 1
 
     def __init__(self, model_name: str, revision: Optional[str], deployment_framework: str, dtype: torch.dtype,
                  quantize: Optional[str], model_config: Union[Any] = None, auto_model_class=None,
@@ -446,7 +453,7 @@ class FlashCausalLM(Model):
                  kv_cache_dtype: Optional[str] = None, kv_scales: Union[None, str, dict] = None,
                  kv_prefix_reuse: Optional[bool] = None, spec_tokens: Optional[int] = None,
                  spec_ngram: Optional[int] = None, speculator: Union[None, str, Any] = None,
-                 spec_sampling: Optional[bool] = None):
+                 spec_sampling: Optional[bool] = None, spec_candidates: Optional[int] = None):
         # KV cache element: "auto" (the model dtype) or "fp8_e4m3" (one byte, utils/kv_cache.py); None reads
         # TGIS_KV_CACHE_DTYPE.  Checked before anything is loaded — except on a rank of a tensor-parallel group, which loads
         # its shard and then tells its peers (agree_kv_cache_dtype below): they sit in a collective only it can release.
@@ -472,6 +479,11 @@ class FlashCausalLM(Model):
         # (an engine built here is checked against the base model below, as soon as its config is read)
         spec_ckpt = mlp_speculator.checked_checkpoint(speculator, self.spec_tokens, getattr(engine, "_config", None))
         self.spec_drafter = "lookup" if spec_ckpt is None else "mlp"
+        # spec_candidates: C > 1 lets a greedy request bring up to C looked-up chains of K drafts to a verify step, verified in
+        # one forward as a token tree of 1 + C K rows (utils/spec_decode.py); None reads TGIS_SPEC_CANDIDATES (unset / 1 = one
+        # chain, 2 .. 4).  It needs spec_tokens > 0, the lookup drafter and no spec_sampling.
+        self.spec_candidates = parse_spec_candidates(spec_candidates)
+        check_spec_candidates(self.spec_candidates, self.spec_tokens, spec_ckpt is not None, self.spec_sampling)
         # kv_scales: the calibrated per-layer scales of a one-byte cache, the contents of a kv_cache_scales.json or its path
         # (utils/kv_cache.py, resolve_kv_scales); None looks at TGIS_KV_SCALES, then next to the weights, else they stay 1.0
         if not torch.cuda.is_available():
@@ -508,13 +520,14 @@ class FlashCausalLM(Model):
         # graph mode, seed
         self.ranks = RankGroup(engine, self.device)
         check_spec_world(self.spec_tokens, self.ranks.world)
+        check_tree_rows(self.spec_candidates, self.spec_tokens, self.num_heads, self.num_kv_heads)
         self._spec_stats = new_stats()
         if spec_ckpt is not None:
             # before the pool is sized: the speculator's bytes come out of the page budget
             mlp_speculator.check_base(spec_ckpt.cfg, self.config.hidden_size, self.config.vocab_size)
             self.drafter = self.speculator = MLPDrafter(spec_ckpt, self.spec_tokens, dtype, self.device)
         elif self.spec_tokens:
-            self.drafter = LookupDrafter(self.spec_tokens, self.spec_ngram)
+            self.drafter = LookupDrafter(self.spec_tokens, self.spec_ngram, self.spec_candidates)
         self.kv_cache_dtype = agree_kv_cache_dtype(self.ranks, kv_cache_dtype)
         self.kv_prefix_reuse = agree_kv_prefix_reuse(self.ranks, kv_prefix_reuse)
         if kv_cache_pages is None:
@@ -718,14 +731,15 @@ class FlashCausalLM(Model):
         if not verify:
             batch.grow_pages()
         key = (graph_bucket(len(batch)), batch.block_tables.shape[1])
+        tree = verify and self.spec_candidates > 1
         if verify:
-            key += (self.spec_tokens,)
+            key += (self.spec_tokens, self.spec_candidates) if tree else (self.spec_tokens,)
         g = self._graphs.get(key)
         if g is None:
             while len(self._graphs) >= self.max_graphs:
                 self._graphs.popitem(last=False)
             renew_unheld_pool(self)
-            g = self._graphs[key] = (_VerifyGraph if verify else _DecodeGraph)(self, *key)
+            g = self._graphs[key] = (_TreeVerifyGraph if tree else _VerifyGraph if verify else _DecodeGraph)(self, *key)
         else:
             self._graphs.move_to_end(key)
         if verify:
@@ -736,9 +750,10 @@ class FlashCausalLM(Model):
 
     def _grow_for_verify(self, batch: FlashCausalLMBatch) -> bool:
         """Whether this decode step verifies the batch's drafts (utils/spec_decode.py, fallback_cause); if so its requests
-        own the pages of K + 1 more tokens afterwards.  A pool that cannot provide them is one more cause to run the plain
-        step, which grows by one token as it always did: speculation never exhausts the pool by itself."""
-        K, st = self.spec_tokens, self._spec_stats
+        own the pages of K + 1 more tokens afterwards (C K + 1 with C candidates per request: one cache position per row).  A
+        pool that cannot provide them is one more cause to run the plain step, which grows by one token as it always did:
+        speculation never exhausts the pool by itself."""
+        K, C, st = self.spec_tokens, self.spec_candidates, self._spec_stats
         st["decode_steps"] += 1
         ntc = batch.next_token_chooser
         plain_greedy = ntc.is_plain_greedy
@@ -747,10 +762,10 @@ class FlashCausalLM(Model):
         greedy = (plain_greedy or self.spec_sampling) and batch.spec_hits is not None
         cause = fallback_cause(
             K, graph_bucket(len(batch)), greedy, any(r.details.top_n_toks or r.details.ranks for r in batch.requests),
-            [t - n for t, n in zip(batch.total_lengths, batch.input_lengths)], batch.spec_hits_host)
+            [t - n for t, n in zip(batch.total_lengths, batch.input_lengths)], batch.spec_hits_host, C)
         if cause is None:
             try:
-                batch.grow_pages(ahead=K)
+                batch.grow_pages(ahead=C * K)
             except OutOfPages:
                 cause = "pages"
         if cause is not None:

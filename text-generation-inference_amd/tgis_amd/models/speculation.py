@@ -27,20 +27,22 @@ from tgis_amd.utils.token_types import TokenInfo
 
 class LookupDrafter:
     """Drafts looked up in the request's own context (tgis_spec_propose): the tokens behind the latest earlier occurrence of
-    its longest suffix of up to `ngram` tokens."""
+    its longest suffix of up to `ngram` tokens.  With `candidates` = C > 1 (tgis_spec_propose_multi) up to C chains per
+    request, `batch.spec_drafts` [B, C, K]: further sites, latest first and longest suffix first, whose continuations start
+    with a token no chain taken before starts with."""
     needs_hidden = False
 
-    def __init__(self, spec_tokens: int, ngram: int):
-        self.K, self.ngram = spec_tokens, ngram
+    def __init__(self, spec_tokens: int, ngram: int, candidates: int = 1):
+        self.K, self.ngram, self.C = spec_tokens, ngram, candidates
 
     def start(self, batch, embeds):
-        batch.spec_tokens, batch.spec_model = self.K, self
+        batch.spec_tokens, batch.spec_model, batch.spec_candidates = self.K, self, self.C
         self.redraft(batch)
 
     def redraft(self, batch, hits_copy: Optional[torch.Tensor] = None):
         batch.ensure_spec_buffers()
-        native.spec_propose(batch.all_input_ids_tensor, batch.position_ids, self.ngram, batch.spec_drafts, batch.spec_hits,
-                            hits_copy)
+        propose = native.spec_propose_multi if self.C > 1 else native.spec_propose
+        propose(batch.all_input_ids_tensor, batch.position_ids, self.ngram, batch.spec_drafts, batch.spec_hits, hits_copy)
         batch.drafts_renewed()
 
     def after_step(self, batch, graph, latest_ids, n_emit, stride, hits_copy, drafting):
@@ -151,14 +153,22 @@ def spec_step(lm, batch, fused, generated_tokens: List[TokenInfo], logits: Optio
     (tgis_warp_sample_verify: the request's parameters, its context plus the drafts in front of the row, the draw
     (seed, offset + j)), a draft is accepted while the chosen token equals it — for a deterministic drafter the
     rejection rule, accept with probability p(draft) — and tgis_spec_accept_sampled also advances each sampled
-    request's stream by what it emitted."""
+    request's stream by what it emitted.
+    A tree verify step (graph.C > 1 candidates per request, greedy only): tgis_spec_tree_accept emits along the best
+    candidate's path and tgis_spec_tree_commit, on the same stream, moves that candidate's keys and values to where a single
+    chain would have written them, so that the cache and every later step are those of a chain step."""
     ids, lps, graph = fused
     B, K, K1, out = len(batch), graph.K, graph.K + 1, graph.spec_out
+    C = graph.C
     ntc = batch.next_token_chooser
     outputs = dict(out_ids=out.ids[:B * K1], out_logprobs=out.lps[:B * K1], all_input_ids=batch.all_input_ids_tensor,
                    cu_seqlens=batch.cu_seqlens, stage_ids=graph.input_ids[:B], stage_positions=graph.positions[:B])
     drafts = batch.spec_drafts if K else None
-    if logits is None:
+    if C > 1:
+        next_token_ids = native.spec_tree_accept(ids, lps, drafts, out.n_emit[:B], out.best[:B], batch.position_ids, **outputs)
+        # (the positions tgis_spec_tree_accept just staged: the step's own are those minus n_emit)
+        native.spec_tree_commit(lm.kv_cache.pool, batch.block_tables, graph.positions[:B], out.best[:B], out.n_emit[:B], C, K)
+    elif logits is None:
         next_token_ids = native.spec_accept(ids, lps, drafts, out.n_emit[:B], batch.position_ids, **outputs)
     else:
         ids, lps, _lse, _scores = ntc.choose_fused_verify(batch.all_input_ids_tensor[:, :batch.max_seqlen], logits,
@@ -185,7 +195,9 @@ def spec_step(lm, batch, fused, generated_tokens: List[TokenInfo], logits: Optio
         batch.input_lengths[i] += n_emit[i]
     if K:
         st = lm._spec_stats
-        st["drafted"] += K * B  # every request's K draft rows are verified, the zero drafts of a lookup that missed too
+        st["drafted"] += C * K * B  # every request's draft rows are verified, the zero drafts of a lookup that missed too
         st["accepted"] += sum(n_emit) - B
         st["emitted"] += sum(n_emit) - B
+        if C > 1:  # what the later candidates bought: steps a request would have ended at its first chain's miss
+            st["won_by_later_candidate"] += sum(1 for c, n in zip(out.read_best(B), n_emit) if c > 0 and n > 1)
     return next_token_ids

@@ -105,6 +105,10 @@ SIGNATURES = {
                                  _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_int, _vp, _c_i64, _vp]),
     "tgis_attn_paged_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int,
                                      _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_int, _vp, _c_i64, _vp] + _KV8_ARGS),
+    "tgis_attn_paged_tree": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int,
+                                      _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_int, _vp, _c_i64, _vp, _vp]),
+    "tgis_attn_paged_tree_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int,
+                                          _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_int, _vp, _c_i64, _vp] + _KV8_ARGS + [_vp]),
     "tgis_kv_absmax": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _c_int, _vp, _vp]),
     "tgis_act_mul": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _c_int, _vp]),
     "tgis_gelu": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_int, _vp]),
@@ -116,6 +120,12 @@ SIGNATURES = {
     "tgis_spec_accept_sampled": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp,
                                           _c_i64, _vp]),
     "tgis_spec_propose": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _c_i64, _vp]),
+    "tgis_spec_tree_stage": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp]),
+    "tgis_spec_tree_accept": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp,
+                                       _c_i64, _vp]),
+    "tgis_spec_tree_commit": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64,
+                                       _c_int, _c_int, _c_int, _vp]),
+    "tgis_spec_propose_multi": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _c_i64, _vp]),
     "tgis_spec_mlp_input": (_c_int, [_vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64, _c_int, _c_f, _c_int, _vp]),
     "tgis_spec_mlp_state": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _vp, _c_f, _c_f, _vp, _c_i64, _c_i64, _c_int, _vp]),
     "tgis_spec_mlp_drafts": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp]),
@@ -792,11 +802,16 @@ def attn_workspace_bytes(total_q: int, H: int, Hkv: int, D: int, num_splits: int
 
 def attn_paged(q, ld_q: int, k_pool, v_pool, block_tables, ctx_lens, cu_seqlens_q, out, B: int, H: int, Hkv: int,
                D: int, max_q_len: int, max_ctx: int, scale: float, num_splits: int, ws: Optional[Workspace],
-               kv_scales=(1.0, 1.0)):
+               kv_scales=(1.0, 1.0), q_mask=None, tree: Optional[bool] = None):
     """q is a (view into a) [T, *] activation whose row stride is ld_q elements; out [T, H*D], or (decode, B <= 64) a
     FragAct of that shape for the o_proj GEMM.  One-byte pools (kv_is8) are read as k_scale * e4m3(k), v_scale * e4m3(v)
-    (tgis_attn_paged_kv8), kv_scales = (k_scale, v_scale)."""
+    (tgis_attn_paged_kv8), kv_scales = (k_scale, v_scale).
+    q_mask (int64 [T], read as 64-bit words): tgis_attn_paged_tree — bit j of word i lets q row i of a sequence attend to that
+    sequence's q row j, under the causal bound; the decode form only.  (tree=True with q_mask None asks the tree entry point
+    with a null mask, which it refuses.)"""
     assert block_tables.dtype == torch.int32 and ctx_lens.dtype == torch.int32 and cu_seqlens_q.dtype == torch.int32
+    if q_mask is not None:
+        assert q_mask.dtype == torch.int64 and q_mask.is_contiguous() and q_mask.numel() >= q.shape[0]
     assert block_tables.is_contiguous()
     if isinstance(out, FragAct):
         assert max_q_len == 1 and out.K == H * D and out.M == B
@@ -808,7 +823,10 @@ def attn_paged(q, ld_q: int, k_pool, v_pool, block_tables, ctx_lens, cu_seqlens_
     args = (_ptr(q), ld_q, _ptr(k_pool), _ptr(v_pool), _ptr(block_tables), block_tables.shape[1], _ptr(ctx_lens),
             _ptr(cu_seqlens_q), optr, ldo, B, H, Hkv, D, max_q_len, max_ctx, float(scale), dtype_code(q.dtype), num_splits,
             wptr, wbytes, _stream())
-    _call_kv("tgis_attn_paged", args, k_pool, v_pool, kv_scales)
+    if not (q_mask is not None if tree is None else tree):
+        _call_kv("tgis_attn_paged", args, k_pool, v_pool, kv_scales)
+    else:
+        _call_kv("tgis_attn_paged_tree", args, k_pool, v_pool, kv_scales, tail=(_ptr(q_mask),))
     return out
 
 
@@ -965,6 +983,81 @@ def spec_propose(all_input_ids, position_ids, ngram: int, drafts, hits, hits_cop
     _check(
         load_library().tgis_spec_propose(_ptr(all_input_ids), all_input_ids.stride(0), _ptr(position_ids), K, ngram,
                                          _ptr(drafts), _ptr(hits), _ptr(hits_copy), B, _stream()), "tgis_spec_propose")
+
+
+def spec_tree_stage(positions, latest_ids, drafts, block_tables, input_ids, positions_out, slots, ctx_lens):
+    """The inputs of a tree verify forward (tgis_spec_tree_stage): drafts [B, C, K]; R = 1 + C K rows per request, the latest
+    token, then candidate by candidate; positions_out by depth, slots by row, ctx_lens = position + R."""
+    B = positions.numel()
+    _, C, K = drafts.shape
+    R = B * (1 + C * K)
+    assert drafts.shape[0] == B and _is(drafts, torch.int64, B * C * K)
+    assert _is(positions, torch.int32, B) and _is(latest_ids, torch.int64, B) and _is(ctx_lens, torch.int32, B)
+    assert block_tables.dtype == torch.int32 and block_tables.shape[0] == B and block_tables.is_contiguous()
+    assert _is(input_ids, torch.int64, R) and _is(positions_out, torch.int32, R) and _is(slots, torch.int32, R)
+    _check(
+        load_library().tgis_spec_tree_stage(_ptr(positions), _ptr(latest_ids), _ptr(drafts), C, K, _ptr(block_tables),
+                                            block_tables.shape[1], _ptr(input_ids), _ptr(positions_out), _ptr(slots),
+                                            _ptr(ctx_lens), B, _stream()), "tgis_spec_tree_stage")
+
+
+def spec_tree_accept(argmax_ids, argmax_logprobs, drafts, n_emit, best, position_ids, out_ids=None, out_logprobs=None,
+                     all_input_ids=None, cu_seqlens=None, stage_ids=None, stage_positions=None):
+    """After a tree verify step (tgis_spec_tree_accept): drafts [B, C, K], argmax_ids / argmax_logprobs [B (1 + C K)];
+    best [B] = the first candidate with the longest accepted prefix, and spec_accept's outputs (out_ids / out_logprobs
+    [B (K + 1)]) along its path.  Returns the new latest ids."""
+    B = position_ids.numel()
+    _, C, K = drafts.shape
+    R, E = B * (1 + C * K), B * (K + 1)
+    assert drafts.shape[0] == B and _is(drafts, torch.int64, B * C * K)
+    assert _is(argmax_ids, torch.int64, R) and _is(position_ids, torch.int64, B)
+    assert _is(n_emit, torch.int32, B) and _is(best, torch.int32, B)
+    assert argmax_logprobs is None or _is(argmax_logprobs, torch.float32, R)
+    assert out_ids is None or _is(out_ids, torch.int64, E)
+    assert out_logprobs is None or (_is(out_logprobs, torch.float32, E) and argmax_logprobs is not None)
+    ld = 0
+    if all_input_ids is not None:
+        assert all_input_ids.dtype == torch.int64 and all_input_ids.stride(1) == 1 and all_input_ids.shape[0] >= B
+        ld = all_input_ids.stride(0)
+    assert cu_seqlens is None or _is(cu_seqlens, torch.int32, B + 1)
+    assert stage_ids is None or _is(stage_ids, torch.int64, B)
+    assert stage_positions is None or _is(stage_positions, torch.int32, B)
+    latest = torch.empty(B, dtype=torch.int64, device=position_ids.device)
+    _check(
+        load_library().tgis_spec_tree_accept(_ptr(argmax_ids), _ptr(argmax_logprobs), _ptr(drafts), C, K, _ptr(n_emit),
+                                             _ptr(best), _ptr(out_ids), _ptr(out_logprobs), _ptr(latest), _ptr(position_ids),
+                                             _ptr(all_input_ids), ld, _ptr(cu_seqlens), _ptr(stage_ids),
+                                             _ptr(stage_positions), B, _stream()), "tgis_spec_tree_accept")
+    return latest
+
+
+def spec_tree_commit(pool, block_tables, new_positions, best, n_emit, C: int, K: int):
+    """Behind spec_tree_accept (tgis_spec_tree_commit): in every layer and kv head of pool [L, 2, pages, Hkv, 32 D] the keys
+    and values of each request's accepted drafts move from the best candidate's rows to the first candidate's, where a chain
+    would have written them.  new_positions [B] int32: what spec_tree_accept left in stage_positions."""
+    B = new_positions.numel()
+    L, two, pages, Hkv, PD = pool.shape
+    assert two == 2 and pool.is_contiguous() and PD % 32 == 0 and pool.element_size() in (1, 2)
+    assert _is(new_positions, torch.int32, B) and _is(best, torch.int32, B) and _is(n_emit, torch.int32, B)
+    assert block_tables.dtype == torch.int32 and block_tables.shape[0] == B and block_tables.is_contiguous()
+    _check(
+        load_library().tgis_spec_tree_commit(_ptr(pool[0, 0]), _ptr(pool[0, 1]), pool.stride(0), L, pages, _ptr(block_tables),
+                                             block_tables.shape[1], _ptr(new_positions), _ptr(best), _ptr(n_emit), C, K, B,
+                                             Hkv, PD // 32, pool.element_size(), _stream()), "tgis_spec_tree_commit")
+
+
+def spec_propose_multi(all_input_ids, position_ids, ngram: int, drafts, hits, hits_copy=None):
+    """Prompt lookup for C candidates (tgis_spec_propose_multi): drafts [B, C, K]; sites from the longest suffix down and
+    from the latest back, a site taken when its continuation starts with a token no taken candidate starts with; zeros for
+    candidates not found.  hits [B] = the suffix length behind the first candidate, 0 = none."""
+    B, C, K = drafts.shape
+    assert all_input_ids.dtype == torch.int64 and all_input_ids.stride(1) == 1 and all_input_ids.shape[0] >= B
+    assert _is(position_ids, torch.int64, B) and _is(drafts, torch.int64, B * C * K) and _is(hits, torch.int32, B)
+    assert hits_copy is None or _is(hits_copy, torch.int32, B)
+    _check(
+        load_library().tgis_spec_propose_multi(_ptr(all_input_ids), all_input_ids.stride(0), _ptr(position_ids), C, K, ngram,
+                                               _ptr(drafts), _ptr(hits), _ptr(hits_copy), B, _stream()),
+        "tgis_spec_propose_multi")
 
 
 def spec_mlp_input(hidden, n_emit, K1: int, out, out_copy=None, scale_input: bool = False, eps: float = 1e-6):

@@ -32,7 +32,15 @@ plain (K = 0) step, and of its verify step with every draft forced right and wit
 requests on the same model (the captured argmax in place of the chooser); and the chooser's launch alone (HIP events) on
 B and on B (K + 1) rows.  Seeded streams are reproducible, so the forced drafts are the plain run's own tokens.
 
+With --candidates C,C,... every (B, K) is measured once per C (spec_candidates=C; 1 = the single chain): the verify step is
+then a token tree of 1 + C K rows per request.  The forced run puts the true continuation into the LAST candidate and junk
+into the others, so every accepted token is won by a later candidate and passes through tgis_spec_tree_commit.  Added per
+line: `commit_ms` (that launch alone, every request moving K positions), and the attention launch alone at the verify
+step's (B, q_len = 1 + C K, ctx) with the tree's mask (`attn_tree_launch_ms`) next to the causal launch of the same shape
+(`attn_chain_launch_ms_same_shape`), both at the verify step's key splits.
+
     python tools/spec_decode_bench.py [--config llama2-7b-gptq] [--tokens 32] [--ctx 1024] > profiles/spec_decode_bench.json
+    python tools/spec_decode_bench.py --candidates 1,2,4 --bs 1,4,8 --ks 3 > profiles/spec_tree_bench.json
     python tools/spec_decode_bench.py --speculator 4096,4096,3 > profiles/spec_mlp_bench.json
     python tools/spec_decode_bench.py --sampled > profiles/spec_sampled_bench.json"""
 import argparse
@@ -55,7 +63,7 @@ from tgis_amd.models.flash_causal_lm import FlashCausalLM, graph_bucket  # noqa:
 from tgis_amd.pb import generate_pb2  # noqa: E402
 from tgis_amd.utils import mlp_speculator  # noqa: E402
 from tgis_amd.utils.kv_cache import PagedKVCache  # noqa: E402
-from tgis_amd.utils.spec_decode import MAX_VERIFY_ROWS  # noqa: E402
+from tgis_amd.utils.spec_decode import MAX_VERIFY_ROWS, tree_q_mask, tree_rows  # noqa: E402
 
 CTX, BS, KS = 1024, [1, 4, 8, 16], [3, 7]
 
@@ -97,12 +105,14 @@ class Tap:
         lm._process_new_tokens = tapped
 
 
-def decode(lm, batch, streams, tokens, force=None, tap=None, keep=None, against=None):
+def decode(lm, batch, streams, tokens, force=None, tap=None, keep=None, against=None, path=None):
     """Decode steps until every request has `tokens` tokens; `force(batch, streams)` sets the drafts before each step.
     keep: a list that receives every step's logits (the plain run; one row per request and token).  against = (plain
     streams, plain logits): every emitted token is held against the plain run until its request's stream parts from it.
     Returns (seconds, steps, tokens emitted, partings) — one record per request that parted: the token index, the plain
-    run's top-2 logit margin there, and max |this run's logits row - the plain run's| for that token."""
+    run's top-2 logit margin there, and max |this run's logits row - the plain run's| for that token.
+    path: the rows of a request, in order, behind which its tokens are emitted (a tree step whose last candidate holds the
+    forced drafts); None: rows 0, 1, ..."""
     torch.cuda.synchronize()
     t0, steps, emitted, trace = time.perf_counter(), 0, 0, []
     while min(len(s) for s in streams.values()) < tokens:
@@ -125,12 +135,12 @@ def decode(lm, batch, streams, tokens, force=None, tap=None, keep=None, against=
         plain, plain_logits = against
         per = rows.shape[0] // len(order)
         for i, rid in enumerate(order):
-            for j in range(per):
+            for j in range(per if path is None else len(path)):
                 t = before[rid] + j
                 if rid in parted or t >= after[rid] or t >= len(plain[rid]) or t - 1 >= len(plain_logits):
                     break  # (rows behind a rejected draft say nothing)
                 ref = plain_logits[t - 1][rid]  # the plain step that chose token t (token 0 is the prefill's)
-                diff = float((rows[i * per + j] - ref).abs().max())
+                diff = float((rows[i * per + (j if path is None else path[j])] - ref).abs().max())
                 if streams[rid][t] != plain[rid][t]:
                     top = ref.topk(2).values
                     partings.append({"request": rid, "token": t, "plain_top2_margin": round(float(top[0] - top[1]), 4),
@@ -153,6 +163,52 @@ def replay_ms(g, n=30):
         b.record()
     torch.cuda.synchronize()
     return statistics.median(a.elapsed_time(b) for a, b in ev)
+
+
+def launch_ms(call, n=30):
+    """Median ms of n launches of `call` (HIP events), three untimed ones in front."""
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+    for _ in range(3):
+        call()
+    for a, b in ev:
+        a.record()
+        call()
+        b.record()
+    torch.cuda.synchronize()
+    return round(statistics.median(a.elapsed_time(b) for a, b in ev), 4)
+
+
+def tree_launches_ms(lm, g, B, C, K, ctx, dev):
+    """(tgis_spec_tree_commit alone with every request moving K positions from the last candidate, the attention launch
+    of the verify step's shape with the tree's mask, the causal launch of the same shape) on layer 0's pools as they are."""
+    from tgis_amd import native
+    from tgis_amd.utils.layers import workspace
+
+    R1 = tree_rows(C, K)
+    H, Hkv, D = lm.num_heads, lm.num_kv_heads, lm.head_size
+    width = PagedKVCache.pages_for(ctx + R1)
+    bt = (torch.arange(B * width, dtype=torch.int32, device=dev) % lm.kv_cache.num_pages).reshape(B, width).contiguous()
+    new_pos = torch.full((B,), ctx + K, dtype=torch.int32, device=dev)
+    best = torch.full((B,), C - 1, dtype=torch.int32, device=dev)
+    n_emit = torch.full((B,), K + 1, dtype=torch.int32, device=dev)
+    commit = launch_ms(lambda: native.spec_tree_commit(lm.kv_cache.pool, bt, new_pos, best, n_emit, C, K))
+    q = torch.randn(B * R1, H * D, device=dev).to(lm.dtype)
+    out = torch.empty_like(q)
+    ctx_lens = torch.full((B,), ctx + R1, dtype=torch.int32, device=dev)
+    cu = torch.arange(B + 1, dtype=torch.int32, device=dev) * R1
+    mask = torch.tensor(tree_q_mask(C, K) * B, dtype=torch.int64, device=dev)
+    ns = native.attn_q_splits(B, Hkv, H, R1, width * 32)
+    ws = None
+    if ns > 1:
+        ws = workspace(dev)
+        ws.ensure(native.attn_workspace_bytes(B * R1, H, Hkv, D, ns))
+    k_pool, v_pool = lm.kv_cache.k_pool(0), lm.kv_cache.v_pool(0)
+
+    def attn(**kw):
+        native.attn_paged(q, q.stride(0), k_pool, v_pool, bt, ctx_lens, cu, out, B, H, Hkv, D, R1, width * 32, D ** -0.5, ns,
+                          ws, **kw)
+
+    return commit, launch_ms(lambda: attn(q_mask=mask)), launch_ms(attn)
 
 
 def synthetic_speculator(E, I, P, V, dtype):
@@ -283,10 +339,14 @@ def main():
     ap.add_argument("--ctx", type=int, default=CTX, help="prompt tokens per request")
     ap.add_argument("--bs", default=None, metavar="B,B,...", help="batch sizes (default 1,4,8,16)")
     ap.add_argument("--ks", default=None, metavar="K,K,...", help="drafts per request (default 3,7)")
+    ap.add_argument("--candidates", default="1", metavar="C,C,...",
+                    help="draft chains per request (spec_candidates; default 1 = the single chain), e.g. 1,2,4")
     args = ap.parse_args()
     CTX = args.ctx
     BS = [int(b) for b in args.bs.split(",")] if args.bs else BS
     KS = [int(k) for k in args.ks.split(",")] if args.ks else KS
+    CS = [int(c) for c in args.candidates.split(",")]
+    assert CS == [1] or not (args.speculator or args.sampled), "--candidates > 1 goes with the lookup and greedy requests"
     kw, quantize, dtype_s, _, _ = bench.CONFIGS[args.config]
     cfg, dtype, dev = LlamaConfig(**kw), getattr(torch, dtype_s), torch.device("cuda:0")
     tensors = llama_tensors(cfg, quantize, seed=1234, device=dev, dtype=dtype)
@@ -296,7 +356,7 @@ def main():
     if args.sampled:
         return sampled_main(args, eng, cfg, dtype, quantize, tok, dev)
     T = args.tokens
-    max_new = T + 16  # every timed step keeps K + 1 tokens in hand
+    max_new = T + max(16, max(CS) * max(KS) + 1)  # every timed step keeps K + 1 (C K + 1) tokens in hand
     pages = max(BS) * PagedKVCache.pages_for(CTX + max_new) + 8
     rng = np.random.default_rng(2025)
     spec, ks = None, KS
@@ -304,19 +364,20 @@ def main():
         E, I, P = (int(x) for x in args.speculator.split(","))
         spec = synthetic_speculator(E, I, P, cfg.vocab_size, dtype)
         ks = [min(P, 7)]
-    for K in ks:
+    for K, C in [(K, C) for K in ks for C in CS]:
         lm = FlashCausalLM("synthetic", None, "synthetic", dtype, quantize, engine=eng, kv_cache_pages=pages, spec_tokens=K,
-                           speculator=spec)
+                           speculator=spec, spec_candidates=C)
         assert lm.use_graphs
         tap = Tap(lm)
         for B in BS:
-            res = {"config": args.config, "ctx": CTX, "B": B, "K": K, "tokens_per_request": T,
+            res = {"config": args.config, "ctx": CTX, "B": B, "K": K, "C": C, "tokens_per_request": T,
                    "note": "synthetic weights: says nothing about real acceptance rates"}
             if spec is not None:
                 res["drafter"] = f"mlp {args.speculator}"
                 res["speculator_bytes"] = lm.speculator.nbytes
-            if graph_bucket(B) * (K + 1) > MAX_VERIFY_ROWS:
-                res["skipped"] = f"graph_bucket(B) * (K + 1) = {graph_bucket(B) * (K + 1)} > {MAX_VERIFY_ROWS}: such a batch never verifies"
+            if graph_bucket(B) * tree_rows(C, K) > MAX_VERIFY_ROWS:
+                res["skipped"] = (f"graph_bucket(B) * (1 + C K) = {graph_bucket(B) * tree_rows(C, K)} > {MAX_VERIFY_ROWS}: "
+                                  "such a batch never verifies")
                 print(json.dumps(res), flush=True)
                 continue
             prompts = [rng.integers(3, cfg.vocab_size, size=CTX).tolist() for _ in range(B)]
@@ -356,28 +417,38 @@ def main():
 
                 def truth(batch, streams):  # the plain run's next K tokens of every request, gathered on the device
                     at = torch.tensor([len(streams[r.id]) for r in batch.requests], device=dev)[:, None] + offs
-                    batch.spec_drafts = plain_dev.gather(1, at.clamp_(max=plain_dev.shape[1] - 1))
+                    right = plain_dev.gather(1, at.clamp_(max=plain_dev.shape[1] - 1))
+                    if C > 1:  # the last candidate holds them, the others junk: every accepted token goes through the commit
+                        right = torch.cat([torch.full((B, C - 1, K), 3, dtype=torch.int64, device=dev), right[:, None]], 1)
+                    batch.spec_drafts = right
                     batch.spec_hits = torch.ones_like(batch.spec_hits)
                     batch.note_spec_hits(ones)
 
                 for name, force in (("accept_all", truth), ("accept_none", garbage)):
-                    (sec, steps, emitted, partings, worst), streams, d, _ = run(force, T, against=(plain, plain_logits))
+                    path = None if C == 1 else [0] + [1 + (C - 1) * K + j for j in range(K)]
+                    (sec, steps, emitted, partings, worst), streams, d, _ = run(force, T, against=(plain, plain_logits),
+                                                                                path=path)
                     res[f"{name}_tokens_per_s"] = round(emitted / sec, 1)
                     res[f"{name}_steps"] = steps
                     res[f"{name}_tokens_per_step_and_request"] = round(emitted / max(1, steps) / B, 3)
-                    res[f"{name}_stats"] = {k: d[k] for k in ("verify_steps", "drafted", "accepted", "emitted")}
+                    res[f"{name}_stats"] = {k: d[k] for k in ("verify_steps", "drafted", "accepted", "emitted",
+                                                              "won_by_later_candidate")}
                     res[f"{name}_ids_equal_plain"] = all(streams[i][:T] == plain[i][:T] for i in streams)
                     # where a stream left the plain run's: how narrowly the plain run decided that token, and how far the
                     # two launch forms' logits are apart there; and the largest such distance over the tokens that agreed
                     res[f"{name}_partings"] = partings
                     res[f"{name}_max_abs_logit_diff_where_equal"] = worst
-                res["verify_step_ms"] = round(replay_ms(lm._graphs[key + (K,)]), 4)
+                vkey = key + ((K,) if C == 1 else (K, C))
+                res["verify_step_ms"] = round(replay_ms(lm._graphs[vkey]), 4)
                 res["plain_num_splits"] = lm._graphs[key].num_splits
-                res["verify_num_splits"] = lm._graphs[key + (K,)].num_splits
+                res["verify_num_splits"] = lm._graphs[vkey].num_splits
+                if C > 1:
+                    res["commit_ms"], res["attn_tree_launch_ms"], res["attn_chain_launch_ms_same_shape"] = tree_launches_ms(
+                        lm, lm._graphs[vkey], B, C, K, CTX, dev)
             if spec is None:
                 res["break_even_tokens_per_verify_step"] = round(res["verify_step_ms"] / res["plain_step_ms"], 3)
             else:
-                res["draft_chain_ms"] = chain = round(replay_ms(lm._graphs[key + (K,)].chain), 4)
+                res["draft_chain_ms"] = chain = round(replay_ms(lm._graphs[vkey].chain), 4)
                 res["draft_chain_after_plain_ms"] = chain0 = round(replay_ms(lm._graphs[key].chain), 4)
                 res["break_even_tokens_per_verify_step"] = round(
                     (res["verify_step_ms"] + chain) / (res["plain_step_ms"] + chain0), 3)
