@@ -49,20 +49,26 @@ namespace {
 // from there on takes the masked body, which tests one more bit per score.  The mask changes scores only: the pages a block
 // walks and every address it loads from are those of the TREE = false kernel for the same ctx_lens and cu_seqlens_q (a page
 // that is full but masked goes through load_page_part with nv = 32, which requests what load_page requests).
+//
+// Kernel argument preload (csrc/gptq_wide_body.h): the leading scalar parameters — 14 dwords, all the user SGPRs a wave has —
+// arrive in SGPRs at wave launch and overrule the same fields of the argument block behind them.  They are what the FIRST
+// scalar requests are formed from: which (sequence, split, kv head) this block is (NS, Hkv, HCB, xcd_remap) and where its
+// lengths and its block table lie (cu_q, ctx_lens, bt, max_pages); kpool fills the last pair.  Everything else is read from
+// the block and arrives with the lengths, one round trip earlier than it did behind a fetch of the block.  Launched through
+// launch_attn_kernel only.
 template <typename T, typename KV, int D, int NW, int CH, bool PIPE, bool TREE = false>
-__global__ __launch_bounds__(64 * NW) void attn_paged_kernel(std::conditional_t<TREE, AttnTreeArgs, AttnArgs> a) {
+__global__ __launch_bounds__(64 * NW) void attn_paged_kernel(const int32_t* bt, const int32_t* cu_q, const int32_t* ctx_lens,
+                                                             const void* kpool, int64_t max_pages, int NS, int Hkv, int HCB,
+                                                             int xcd_remap,
+                                                             std::conditional_t<TREE, AttnTreeArgs, AttnArgs> rest) {
     static_assert(!TREE || (CH == 1 && !PIPE), "the tree variant exists for one-chunk blocks without the page pipeline");
     using V8 = typename VecT<T>::x8;
     constexpr int KS = D / 32;  // k-steps of the QK^T MFMA
     constexpr int NB = D / 16;  // 16-row blocks of O^T
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    {   // every cache line of the argument block the decode path reads is requested at entry (one scalar round trip instead
-        // of one per group of fields: tools/floor/wide.hip `pre`)
-        const int64_t l0 = a.ld_q;
-        const int l1 = a.NS;
-        const void* l2 = a.counters;
-        asm volatile("" ::"s"(l0), "s"(l1), "s"(l2));
-    }
+    std::conditional_t<TREE, AttnTreeArgs, AttnArgs> a = rest;
+    a.bt = bt; a.cu_q = cu_q; a.ctx_lens = ctx_lens; a.kpool = kpool; a.max_pages = max_pages;
+    a.NS = NS; a.Hkv = Hkv; a.HCB = HCB; a.xcd_remap = xcd_remap;
     ATTN_STAMP_DECL
     ATTN_STAMP(0);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -95,6 +101,13 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(std::conditional_t<
     const int32_t* btrow = a.bt + (int64_t)b * a.max_pages;
     const int pg_spec = (a.NS == 1 && w < a.max_pages) ? btrow[w] : 0;
     const int q0 = a.cu_q[b], q_len = a.cu_q[b + 1] - q0;
+    {   // the requests above are formed from preloaded arguments alone.  Every cache line of the argument block the decode path
+        // reads is asked for with them (one scalar round trip instead of one per group of fields: tools/floor/wide.hip `pre`)
+        const int64_t l0 = a.ld_q;
+        const int l1 = a.TQ;
+        const void* l2 = a.counters;
+        asm volatile("" ::"s"(l0), "s"(l1), "s"(l2));
+    }
     const int t0 = qt * a.TQ;
     if (t0 >= q_len) return;
     const int ctx = a.ctx_lens[b];
@@ -581,6 +594,13 @@ static int chunks_per_block(int HC, int64_t max_q_len) {
     return (max_q_len == 1 && HC > 1) ? std::min(HC, 3) : 1;
 }
 
+// the one place that spells attn_paged_kernel's launch: the preloaded leading parameters, then the whole argument block
+template <typename Kernel, typename Args>
+static void launch_attn_kernel(Kernel kern, dim3 grid, int nw, size_t lds, hipStream_t st, const Args& a) {
+    hipLaunchKernelGGL(kern, grid, dim3(64 * nw), lds, st, a.bt, a.cu_q, a.ctx_lens, a.kpool, a.max_pages, a.NS, a.Hkv, a.HCB,
+                       a.xcd_remap, a);
+}
+
 template <typename T, typename KV, int D, int NW, int CH, bool PIPE>
 static void launch_attn_pipe(const AttnArgs& a, dim3 grid, hipStream_t st) {
     const size_t lds = (size_t)CH * (NW * D * 16 + NW * 2 * 16) * sizeof(float);
@@ -590,7 +610,7 @@ static void launch_attn_pipe(const AttnArgs& a, dim3 grid, hipStream_t st) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr = true;
     }
-    hipLaunchKernelGGL((attn_paged_kernel<T, KV, D, NW, CH, PIPE>), grid, dim3(64 * NW), lds, st, a);
+    launch_attn_kernel(attn_paged_kernel<T, KV, D, NW, CH, PIPE>, grid, NW, lds, st, a);
 }
 
 // Two pages in flight where a block is alone on its CU anyway (multi-chunk blocks: nothing else there hides the load
@@ -650,7 +670,7 @@ template <typename T, typename KV, int D>
 static int launch_attn_tree(const AttnTreeArgs& a, dim3 grid, int64_t total_q, const int32_t* q_end, hipStream_t st) {
     constexpr int NW = 4;
     const size_t lds = (size_t)(NW * D * 16 + NW * 2 * 16) * sizeof(float);  // <= 32.5 KiB: no attribute to raise
-    hipLaunchKernelGGL((attn_paged_kernel<T, KV, D, NW, 1, false, true>), grid, dim3(64 * NW), lds, st, a);
+    launch_attn_kernel(attn_paged_kernel<T, KV, D, NW, 1, false, true>, grid, NW, lds, st, a);
     TGIS_CHECK_LAUNCH();
     return launch_combine<T, D>(a, total_q, q_end, st);
 }

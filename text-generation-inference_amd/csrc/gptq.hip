@@ -108,10 +108,14 @@ __global__ __launch_bounds__(64 * TN * WK) void gptq_gemm_kernel(GemmArgs a) {
 }
 
 // Decode batches of up to 32 rows whose activation is in fragment order (gptq_wide_body.h).  8 waves; CT = 4 holds 2 waves
-// per SIMD (one block per CU), CT = 2 / 3 leave room for more.
+// per SIMD (one block per CU), CT = 2 / 3 leave room for more.  The leading parameters are preloaded into SGPRs at wave
+// launch (gptq::wide_args); launched through gptq::wide_launch only.
 template <int CT, int ACT, bool OUTF, int MR>
-__global__ __launch_bounds__(64 * gptq::WIDE_WK) void gptq_wide_kernel(GemmArgs a) {
+__global__ __launch_bounds__(64 * gptq::WIDE_WK) void gptq_wide_kernel(const uint8_t* prep, int64_t offB, const f16* x, int K,
+                                                                       int KS, int G, int NT, int S, int spg_shift, int M,
+                                                                       GemmArgs rest) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const GemmArgs a = gptq::wide_args(prep, offB, x, K, KS, G, NT, S, spg_shift, M, rest);
     gptq::gptq_wide_unit<CT, ACT, OUTF, MR>(a, smem);
 }
 
@@ -647,7 +651,7 @@ static int launch_wide_mr(dim3 grid, hipStream_t st, const GemmArgs& a) {
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_done = true;
     }
-    hipLaunchKernelGGL((gptq_wide_kernel<CT, ACT, OUTF, MR>), grid, dim3(64 * gptq::WIDE_WK), lds, st, a);
+    gptq::wide_launch(gptq_wide_kernel<CT, ACT, OUTF, MR>, grid, lds, st, a);
     return TGIS_OK;
 }
 template <int CT, int ACT, bool OUTF>

@@ -95,6 +95,24 @@ static inline int wide_max_splits(int64_t K, int64_t N) {
                     std::max(plan_wide(K, N, 0, 32, true).S, plan_wide(K, N, 0, 64, true).S));
 }
 
+// Kernel argument preload.  gfx950 hands a wave its LEADING SCALAR kernel parameters in user SGPRs at launch (a by-value
+// struct is never preloaded), so a kernel of this unit takes the fields the first weight, {scale, zero} and activation
+// requests are formed from as leading parameters — 13 dwords — and the whole GemmArgs behind them; its prologue then issues
+// without the scalar round trip to the argument block.  Everything else (bias, positions, slots, cos / sin, pools, out, slabs)
+// is read from the struct and arrives under the first HBM latency.  The leading copies overrule the struct's own fields:
+// wide_args() puts them back into one GemmArgs for the unit, wide_launch() is the only place that spells the launch.
+__device__ __forceinline__ GemmArgs wide_args(const uint8_t* prep, int64_t offB, const f16* x, int K, int KS, int G, int NT,
+                                              int S, int spg_shift, int M, const GemmArgs& rest) {
+    GemmArgs a = rest;
+    a.prep = prep; a.offB = offB; a.x = x; a.K = K; a.KS = KS; a.G = G; a.NT = NT; a.S = S; a.spg_shift = spg_shift; a.M = M;
+    return a;
+}
+template <typename Kernel>
+static inline void wide_launch(Kernel kern, dim3 grid, size_t lds, hipStream_t st, const GemmArgs& a) {
+    hipLaunchKernelGGL(kern, grid, dim3(64 * WIDE_WK), lds, st, a.prep, a.offB, a.x, a.K, a.KS, a.G, a.NT, a.S, a.spg_shift,
+                       a.M, a);
+}
+
 // OUTF: the act = 2 output (the operand of the down projection) leaves in fragment order as well.
 // MR = 32-row blocks of the activation (1: M <= 32; 2: M <= 64 — every dequantised B fragment then feeds two MFMAs, the
 // "two tiles per wave on one activation" of the 64-row passes, with the activation in registers instead of LDS).
@@ -102,12 +120,6 @@ template <int CT, int ACT, bool OUTF, int MR>
 __device__ __forceinline__ void gptq_wide_unit(const GemmArgs& a, unsigned char* smem) {
     constexpr bool ROPE = ACT == 3 || ACT == 4;  // rope image epilogue; 4: k / v into a one-byte (e4m3) cache
     constexpr int WK = WIDE_WK, DEPTH = WIDE_DEPTH, NR = 16 / WK;
-    {   // every cache line of the argument block is requested at entry: one scalar round trip instead of three dependent
-        // ones before the first weight request (tools/floor/wide.hip `pre`: 0.1 - 0.25 us per launch)
-        const int64_t l0 = a.ldo;
-        const int l1 = a.S, l2 = a.rD;
-        asm volatile("" ::"s"(l0), "s"(l1), "s"(l2));
-    }
     const int lane = threadIdx.x & 63;
     const int wk = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int cg = blockIdx.x, split = blockIdx.y;
@@ -167,19 +179,6 @@ __device__ __forceinline__ void gptq_wide_unit(const GemmArgs& a, unsigned char*
         const int r = wk * NR + j;
         return mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
     };
-    // ACT 3: their cache slots and rotary positions
-    int32_t rpos[ROPE ? MR : 1][ROPE ? NR : 1], rslot[ROPE ? MR : 1][ROPE ? NR : 1];
-    if (ROPE) {
-#pragma unroll
-        for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-            for (int j = 0; j < NR; ++j) {
-                const int m = min(row_of(mr, j), mrows - 1);
-                rpos[mr][j] = a.positions[m];
-                rslot[mr][j] = a.slots[m];
-            }
-    }
-
     uint32_t EXr = 0x64006400u, M0r = 0x000F000Fu, M1r = 0x00F000F0u;
     asm volatile("" : "+v"(EXr));
     asm volatile("" : "+s"(M0r), "+s"(M1r));
@@ -193,6 +192,25 @@ __device__ __forceinline__ void gptq_wide_unit(const GemmArgs& a, unsigned char*
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) load_step(d, s0 + d);
     WIDE_STAMP(1);
+    {   // the prologue above is formed from preloaded arguments alone (wide_args).  Every cache line of the rest of the
+        // argument block is asked for here, under the prologue's HBM latency: one scalar round trip instead of three
+        // dependent ones in front of the epilogue (tools/floor/wide.hip `pre`: 0.1 - 0.25 us per launch)
+        const int64_t l0 = a.ldo;
+        const int l1 = a.partial, l2 = a.rD;
+        asm volatile("" ::"s"(l0), "s"(l1), "s"(l2));
+    }
+    // ACT 3: the finishing rows' cache slots and rotary positions (their pointers are in the struct: behind the prologue)
+    int32_t rpos[ROPE ? MR : 1][ROPE ? NR : 1], rslot[ROPE ? MR : 1][ROPE ? NR : 1];
+    if (ROPE) {
+#pragma unroll
+        for (int mr = 0; mr < MR; ++mr)
+#pragma unroll
+            for (int j = 0; j < NR; ++j) {
+                const int m = min(row_of(mr, j), mrows - 1);
+                rpos[mr][j] = a.positions[m];
+                rslot[mr][j] = a.slots[m];
+            }
+    }
 
     auto consume = [&](int d) {
 #pragma unroll

@@ -1,7 +1,10 @@
 // Round 4: the PRODUCT's fragment-order int4 GEMM unit (csrc/gptq_wide_body.h, included as is) on arbitrary shapes, with
 // per-wave s_memtime stamps: where does a launch of the 64-row form (MR = 2) spend its time at the Llama-2-70B shapes?
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DWIDE_TRACE] -I text-generation-inference_amd/csrc -o tools/floor/wide_unit tools/floor/wide_unit.hip
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-kernarg-preload-count=16 [-DWIDE_TRACE] -I text-generation-inference_amd/csrc -o tools/floor/wide_unit tools/floor/wide_unit.hip
 //   tools/floor/wide_unit            (random images: timing and timeline only; parity is tests/test_fragments_gpu.py's job)
+//   tools/floor/wide_unit 7b32       (the 32-row o_proj / down launches of the Llama-2-7B headline only)
+// The stamps cannot see the argument fetch that kernarg preload removes: WIDE_STAMP itself begins with a scalar load (the trace
+// pointer), which overlaps that fetch, and "entry" is taken after it.  Compare the timed build with and without the flag.
 #include <hip/hip_runtime.h>
 // Two builds: plain (timing: the unit exactly as the library compiles it) and -DWIDE_TRACE (per-wave stamps).  The stamps must
 // not be in the timed build: a store inside the loop makes hipcc give up its counted vmcnt waits (loads and stores complete
@@ -26,8 +29,11 @@ static __device__ long long* g_wide_trace = nullptr;   // [blocks][8 waves][8]
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1);} } while (0)
 
 template <int CT, int ACT, bool OUTF, int MR>
-__global__ __launch_bounds__(64 * gptq::WIDE_WK) void unit_kernel(gptq::GemmArgs a) {
+__global__ __launch_bounds__(64 * gptq::WIDE_WK) void unit_kernel(const uint8_t* prep, int64_t offB, const _Float16* x, int K,
+                                                                  int KS, int G, int NT, int S, int spg_shift, int M,
+                                                                  gptq::GemmArgs rest) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const gptq::GemmArgs a = gptq::wide_args(prep, offB, x, K, KS, G, NT, S, spg_shift, M, rest);  // preloaded, as in the library
     gptq::gptq_wide_unit<CT, ACT, OUTF, MR>(a, smem);
 }
 
@@ -76,7 +82,7 @@ static void run(const char* name, int K, int N, int S, int M) {
     const int iters = 2 * nsets;
     for (int rep = 0; rep < 3; ++rep) {
         CK(hipEventRecord(e0, 0));
-        for (int i = 0; i < iters; ++i) { a.prep = sets[i % nsets]; hipLaunchKernelGGL(kern, grid, dim3(512), lds, 0, a); }
+        for (int i = 0; i < iters; ++i) { a.prep = sets[i % nsets]; gptq::wide_launch(kern, grid, lds, 0, a); }
         CK(hipEventRecord(e1, 0)); CK(hipDeviceSynchronize());
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         best = std::min(best, ms * 1000.f / iters);
@@ -88,7 +94,7 @@ static void run(const char* name, int K, int N, int S, int M) {
     const int nw = cgs * S * 8;
     long long* dtr; CK(hipMalloc(&dtr, (size_t)nw * 64)); CK(hipMemset(dtr, 0, (size_t)nw * 64));
     CK(hipMemcpyToSymbol(HIP_SYMBOL(g_wide_trace), &dtr, sizeof(dtr)));
-    for (int i = 0; i < 3; ++i) { a.prep = sets[(i + 1) % nsets]; hipLaunchKernelGGL(kern, grid, dim3(512), lds, 0, a); }
+    for (int i = 0; i < 3; ++i) { a.prep = sets[(i + 1) % nsets]; gptq::wide_launch(kern, grid, lds, 0, a); }
     CK(hipDeviceSynchronize());
     long long* nul = nullptr; CK(hipMemcpyToSymbol(HIP_SYMBOL(g_wide_trace), &nul, sizeof(nul)));
     std::vector<long long> tr((size_t)nw * 8);
@@ -108,7 +114,12 @@ static void run(const char* name, int K, int N, int S, int M) {
     CK(hipFree(dx)); CK(hipFree(dout)); CK(hipFree(dslabs));
 }
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1 && !strcmp(argv[1], "7b32")) {  // the 32-row o_proj / down launches of the headline (plan_wide: CT 2, S 4)
+        run<2, 0, 1>("7B o", 4096, 4096, 4, 32);
+        run<2, 0, 1>("7B down", 11008, 4096, 4, 32);
+        return 0;
+    }
     run<4, 2, 2>("70B gate_up", 8192, 57344, 1, 64);
     run<7, 2, 2>("70B gate_up", 8192, 57344, 1, 64);
     run<8, 2, 2>("70B gate_up", 8192, 57344, 1, 64);
