@@ -19,7 +19,8 @@
 // Every block sum has a fixed association order (per-thread strided, wave butterfly, 16 partials in order), so a row's
 // result depends only on (its scores, its parameters, its RNG state): not on the batch around it, not on timing.
 // Elements exactly tied at a top-p / typical-p boundary are kept or removed together (the reference's sort splits
-// such ties arbitrarily).
+// such ties arbitrarily).  Tied means equal as floats: -0.0 and +0.0 are one value to every filter (order_key gives them
+// one key), as they are to the reference's `scores < kth`; the scores themselves keep their sign.
 //
 // Sampling is the exponential race the host path used (argmax p_i / E_i, E_i ~ Exp(1)) with a counter-based
 // generator: E_i = -log(u_i), u_i from Philox4x32-10 keyed by the request's seed with counter (i, draw offset).
@@ -83,9 +84,13 @@ struct Row {
     }
 };
 
-__device__ __forceinline__ uint32_t order_key(float x) {  // unsigned order == float order
+// unsigned order == float order, equal keys == equal floats: a negative float (sign | m) maps to 2^31 - m (the negation of its
+// bits), so -0.0 shares the key 2^31 of +0.0 and every other negative lies below it in order.  (The bitwise complement
+// 2^31 - 1 - m that stood here put -0.0 one key below +0.0: a top-k whose k-th value was +0.0 removed the -0.0 entries,
+// which `scores < kth` keeps, and a top-p boundary could fall between the two zeros, whose probabilities are equal.)
+__device__ __forceinline__ uint32_t order_key(float x) {
     uint32_t u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return (u & 0x80000000u) ? 0u - u : (u | 0x80000000u);
 }
 
 struct Block {
