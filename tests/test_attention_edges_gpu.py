@@ -31,8 +31,10 @@ import torch
 if __name__ == "__main__":  # the two-launch combine child (test_two_launch_combine_for_single_chunk_groups)
     _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path[:0] = [_ROOT, os.path.join(_ROOT, "text-generation-inference_amd")]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from oracle import ops_ref
+import attn_cases  # noqa: E402
+from oracle import ops_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -50,16 +52,19 @@ def _nat():
 
 
 def _form(H, Hkv, max_q_len, ns, fused=True):
-    """The launch attn_paged_impl picks (csrc/attention.hip)."""
-    G = H // Hkv
-    Gp = 1 << (min(G, 16) - 1).bit_length()
-    if ns == 1 and max_q_len * Gp > 64:
+    """The launch attn_paged_impl picks, asked from the library's plan (tests/attn_cases.py).  `fused`: whether this process
+    lets split launches merge in the launch (the children run with TGIS_ATTN_FUSED_COMBINE=0, and the plan follows it)."""
+    info = attn_cases.query_plan(_nat().load_library(), 1, H, Hkv, 64, max_q_len, ns)
+    assert info is not None, "the library refuses this shape"
+    p = attn_cases.plan_fields(info)
+    if p["form"] == "prefill":
         return "prefill"
     if max_q_len > 1:
         return "decode q>1"
     if ns == 1:
         return "decode"
-    return "fused merge" if fused and G <= 16 else "combine"
+    assert fused or p["merge"] != "fused"
+    return "fused merge" if p["merge"] == "fused" else "combine"
 
 
 class _Case:
@@ -271,6 +276,39 @@ def _split_case(dev, name, dtype, H, Hkv, D, lens, ns, by_rule, fused):
 @pytest.mark.parametrize("name,dtype,H,Hkv,D,lens,ns,by_rule", SPLITS, ids=[s[0] for s in SPLITS])
 def test_split_decode(gpu_device, name, dtype, H, Hkv, D, lens, ns, by_rule):
     _split_case(gpu_device, name, dtype, H, Hkv, D, lens, ns, by_rule, fused=True)
+
+
+# ---- c2. one-token launches on the variants no case above reaches -------------------------------------------------------
+# One case per variant key (tests/attn_cases.py) that tests/test_attn_plan_cpu.py found without a GPU case, at the smallest
+# shape that reaches it, at the split count the rule gives it.  (name, dtype, H, Hkv, D, ctx lens) and the key it must land on.
+DECODE = [
+    # 32 sequences x 32 kv heads = 1024 blocks: 2-wave blocks, 1 - 3 pages dealt over two waves (one wave idle at one page)
+    ("mha-1024-blocks-2waves-d64-f16", F16, 32, 32, 64, [1, 31, 32, 33, 63, 64, 65, 70] + [33 + (5 * i) % 38 for i in range(24)]),
+    # G = 64 as two blocks of 3 + 1 chunks per kv head, 8 (sequence, kv head) groups: the chunk blocks of a group share an XCD
+    ("mqa64-xcd-unsplit-d128-bf16", BF16, 128, 2, 128, [1, 33, 100, 257]),
+    ("mqa64-xcd-combine8-ns2-d96-f16", F16, 128, 2, 96, [1000, 700]),
+    # G = 80: 3 + 2 chunks, the second block's third chunk is past the group
+    ("mqa80-xcd-combine-ns16-d64-bf16", BF16, 80, 1, 64, [8192]),
+]
+DECODE_VARIANTS = {
+    "mha-1024-blocks-2waves-d64-f16": "form=decode,nw=2,ch=1,pipe=0,xcd_remap=0,merge=none",
+    "mqa64-xcd-unsplit-d128-bf16": "form=decode,nw=4,ch=3,pipe=1,xcd_remap=1,merge=none",
+    "mqa64-xcd-combine8-ns2-d96-f16": "form=decode,nw=4,ch=3,pipe=1,xcd_remap=1,merge=combine8",
+    "mqa80-xcd-combine-ns16-d64-bf16": "form=decode,nw=4,ch=3,pipe=1,xcd_remap=1,merge=combine",
+}
+
+
+@pytest.mark.parametrize("name,dtype,H,Hkv,D,lens", DECODE, ids=[c[0] for c in DECODE])
+def test_decode_variant(gpu_device, name, dtype, H, Hkv, D, lens):
+    nat = _nat()
+    ns = nat.attn_num_splits(len(lens), Hkv, H, 1, max(lens))
+    key = attn_cases.key_str(attn_cases.case_key(nat.load_library(), H, Hkv, D, [(1, l) for l in lens], ns))
+    assert key == DECODE_VARIANTS[name], f"the plan changed ({key}): re-choose this case"
+    c = _Case(gpu_device, dtype, H, Hkv, D, [(1, l) for l in lens], seed=H + D + len(lens))
+    got = c.run(ns)
+    c.check(got, c.want(), f"{name}: {ns} split(s) against the oracle", long=ns > 1)
+    if ns > 1:
+        c.check(got, c.run(1), f"{name}: {ns} splits against one", long=True)
 
 
 # ---- e. the two-launch combine for single-chunk groups ----------------------------------------------------------------

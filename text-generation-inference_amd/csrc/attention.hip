@@ -15,15 +15,17 @@
 //   O^T[d][col]  += V^T[d][tok] . P^T[tok][col] A = V^T fragment (1 KiB contiguous loads), B = P^T
 // S^T's accumulator layout IS the B-operand layout of the second MFMA and O^T's column index is the
 // same lane, so the only cross-lane traffic per page is the 2-step row-max exchange.
+//
+// Which launch a shape takes (form, waves and chunks per block, PIPE, XCD remap, grid, merge, key splits, workspace) is decided
+// in attention_plan.h; this file is the kernels, then the launcher of a plan, then the entry points.
 #include <stdio.h>
-#include <stdlib.h>
 #include <algorithm>
 #include <type_traits>
-#include <map>
-#include <mutex>
 #include "common.h"
 #include "dispatch.h"
 #include "attention_args.h"
+#include "attention_counters.h"
+#include "attention_plan.h"
 #include "kv_layout.h"
 
 // tools/floor/attn_unit.hip compiles this unit with per-wave s_memtime stamps (ATTN_STAMP*); the library does not.
@@ -293,7 +295,7 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(const int32_t* bt, 
         const int npairs = p < pend ? nfull >> 1 : 0;
         if (npairs > 0) {
             V8 kfa[2][KS], vfa[NB], kfb[2][KS], vfb[NB];
-            load_page(pg_first, kfa, vfa);
+            load_page(pg_first, kfa, vfa);  // pg_first is a page id only when pbeg + w < pend: npairs > 0 says so
             for (int i = 0; i + 1 < npairs; ++i) {
                 load_page(btrow[p + NW], kfb, vfb);
                 apply_page(p, kfa, vfa, std::true_type{});
@@ -310,7 +312,7 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(const int32_t* bt, 
     // the fully visible pages — a loop of their own, not one loop with both bodies: the register allocator sizes a loop
     // for the union of what its branches hold (180 vs 122 VGPRs here, i.e. 2 instead of 3 waves per SIMD, which costs
     // the HBM-bound many-block shapes 5 %)
-    int pg = PIPE ? ((p < pend) ? btrow[p] : 0) : pg_first;
+    int pg = PIPE ? ((p < pend) ? btrow[p] : 0) : pg_first;  // (pg_first: valid only when pbeg + w < pend, the loop's p < pend)
     for (; p < pend && p * 32 + 32 <= kfull; p += NW) {
         const int pg_next = (p + NW < pend) ? btrow[p + NW] : 0;
         V8 kf[2][KS], vf[NB];
@@ -562,38 +564,6 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restri
     }
 }
 
-static int next_pow2(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
-struct AttnGeom {
-    int G, Gc, Gp, TQ, HC;
-};
-static AttnGeom geom(int H, int Hkv) {
-    AttnGeom g;
-    g.G = H / Hkv;
-    g.Gc = std::min(g.G, 16);
-    g.HC = (g.G + 15) / 16;
-    g.Gp = next_pow2(g.Gc);
-    g.TQ = 16 / g.Gp;
-    return g;
-}
-
-// Decode with fewer than 256 (sequence, kv head) groups: blocks of 8 waves that share one group's keys page by page
-// (and merge through LDS) instead of more key splits merged across blocks.
-static bool wide_decode_blocks(int64_t groups, int ch) { return ch == 1 && groups < 256; }
-
-// 16-head chunks one decode block serves (register budget: 3 sets of O accumulators at D = 128)
-static int chunks_per_block(int HC, int64_t max_q_len) {
-    if (const char* e = getenv("TGIS_ATTN_CH")) {  // tuning hook (tools/attn_nw.py)
-        const int v = atoi(e);
-        if (v >= 1 && v <= 3) return (max_q_len == 1 && HC > 1) ? std::min(HC, v) : 1;
-    }
-    return (max_q_len == 1 && HC > 1) ? std::min(HC, 3) : 1;
-}
-
 // the one place that spells attn_paged_kernel's launch: the preloaded leading parameters, then the whole argument block
 template <typename Kernel, typename Args>
 static void launch_attn_kernel(Kernel kern, dim3 grid, int nw, size_t lds, hipStream_t st, const Args& a) {
@@ -601,282 +571,103 @@ static void launch_attn_kernel(Kernel kern, dim3 grid, int nw, size_t lds, hipSt
                        a.xcd_remap, a);
 }
 
-template <typename T, typename KV, int D, int NW, int CH, bool PIPE>
-static void launch_attn_pipe(const AttnArgs& a, dim3 grid, hipStream_t st) {
-    const size_t lds = (size_t)CH * (NW * D * 16 + NW * 2 * 16) * sizeof(float);
-    static bool attr = false;  // e.g. CH = 3, D = 128, NW = 4: 98 KB of combine scratch
-    if (!attr && lds > 48 * 1024) {
-        (void)hipFuncSetAttribute((const void*)attn_paged_kernel<T, KV, D, NW, CH, PIPE>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
-    launch_attn_kernel(attn_paged_kernel<T, KV, D, NW, CH, PIPE>, grid, NW, lds, st, a);
-}
-
-// Two pages in flight where a block is alone on its CU anyway (multi-chunk blocks: nothing else there hides the load
-// latency; MQA 48:1, B=32, ctx 4096: 30.3 -> 25.8 us).  The 8-wave blocks of few-group shapes measured no different,
-// and the many-block shapes keep the small-register variant.
-template <typename T, typename KV, int D, int NW, int CH>
-static void launch_attn_one(const AttnArgs& a, dim3 grid, hipStream_t st) {
-    static const int pipe_env = getenv("TGIS_ATTN_PIPE") ? atoi(getenv("TGIS_ATTN_PIPE")) : -1;  // A/B hook
-    if constexpr (CH > 1 && NW == 4) {
-        if (pipe_env != 0) return launch_attn_pipe<T, KV, D, NW, CH, true>(a, grid, st);
-    }
-    if constexpr (CH == 1 && (NW == 2 || NW == 4)) {
-        if (pipe_env == 2) return launch_attn_pipe<T, KV, D, NW, CH, true>(a, grid, st);
-    }
-    launch_attn_pipe<T, KV, D, NW, CH, false>(a, grid, st);
-}
-
-// the second launch of a split call that has no arrival counters (multi-chunk blocks, or none were free)
-template <typename T, int D>
-static int launch_combine(const AttnArgs& a, int64_t total_q, const int32_t* q_end, hipStream_t st) {
-    if (a.NS > 1 && !a.counters) {
-        const int64_t rows = total_q * a.H;
-        if (a.NS <= 8)
-            hipLaunchKernelGGL((attn_combine_kernel<T, D, 8>), dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, st, a.ws_o,
-                               a.ws_ml, (T*)a.out, a.NS, a.H, a.out_frag, rows, q_end);
-        else
-            hipLaunchKernelGGL((attn_combine_kernel<T, D, 0>), dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, st, a.ws_o,
-                               a.ws_ml, (T*)a.out, a.NS, a.H, a.out_frag, rows, q_end);
+// the decode kernel as the plan names it, then the combine launch of a split call that has no arrival counters (multi-chunk
+// blocks, or none were free).  That one runs over total_q = B * max_q_len rows: it reads the real count, *q_end.
+template <typename T, typename KV, int D>
+static int launch_decode(const AttnPlan& p, const AttnTreeArgs& a, int64_t total_q, const int32_t* q_end, hipStream_t st) {
+    const dim3 grid((unsigned)p.grid[0], (unsigned)p.grid[1], (unsigned)p.grid[2]);
+    // the instances that exist, as decimal digits (tree, PIPE, chunks per block, waves per block)
+    const int inst = (p.form == ATTN_TREE) * 1000 + p.pipe * 100 + p.ch * 10 + p.nw;
+    const int rc = by_int<11, 12, 13, 14, 18, 112, 114, 21, 22, 24, 124, 31, 32, 34, 134, 1014>(
+        inst, "tgis_attn_paged: (tree, PIPE, chunks, waves)", [&](auto i) {
+        constexpr int I = decltype(i)::value, NW = I % 10, CH = I / 10 % 10;
+        constexpr bool PIPE = I / 100 % 10 != 0, TREE = I / 1000 != 0;
+        auto kern = attn_paged_kernel<T, KV, D, NW, CH, PIPE, TREE>;
+        static bool attr = false;  // (per instance)
+        if (!attr && p.lds_bytes > 48 * 1024) {
+            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+            attr = true;
+        }
+        launch_attn_kernel(kern, grid, NW, (size_t)p.lds_bytes, st, a);
         TGIS_CHECK_LAUNCH();
-    }
+        return TGIS_OK;
+    });
+    if (rc != TGIS_OK || a.NS == 1 || a.counters) return rc;
+    const int64_t rows = total_q * a.H;
+    return by_bool(p.maxs8, [&](auto m8) {
+        hipLaunchKernelGGL((attn_combine_kernel<T, D, decltype(m8)::value ? 8 : 0>), dim3((unsigned)cdiv64(rows, 4)), dim3(256),
+                           0, st, a.ws_o, a.ws_ml, (T*)a.out, a.NS, a.H, a.out_frag, rows, q_end);
+        TGIS_CHECK_LAUNCH();
+        return TGIS_OK;
+    });
+}
+
+// What a shape must satisfy to have a plan, then the plan under `hooks` and its own limit: the checks tgis_attn_paged and
+// tgis_debug_attn_plan share.
+static int checked_plan(int64_t B, int H, int Hkv, int D, int64_t max_q_len, int num_splits, bool tree, const AttnHooks& hooks,
+                        AttnPlan* plan) {
+    TGIS_CHECK_ARG(H > 0 && Hkv > 0 && H % Hkv == 0, "tgis_attn_paged: H (%d) must be a multiple of Hkv (%d)", H, Hkv);
+    TGIS_CHECK_ARG(D == 64 || D == 96 || D == 128, "tgis_attn_paged: head_dim %d not supported (64, 96, 128)", D);
+    TGIS_CHECK_ARG(B >= 0 && max_q_len > 0 && num_splits >= 1, "tgis_attn_paged: bad launch bounds");
+    const AttnGeom g = geom(H, Hkv);
+    const bool prefill_form = max_q_len * g.Gp > 64;
+    TGIS_CHECK_ARG(num_splits == 1 || !prefill_form,
+                   "tgis_attn_paged: key splits are for the decode form (max_q_len * padded group size <= 64, here %ld * %d): "
+                   "the prefill form takes none", (long)max_q_len, g.Gp);
+    TGIS_CHECK_ARG(!tree || !prefill_form,
+                   "tgis_attn_paged_tree: only the decode form is served (max_q_len * padded group size <= 64, here %ld * "
+                   "%d): one 64-bit mask word per q row", (long)max_q_len, g.Gp);
+    *plan = plan_attn(B, H, Hkv, D, max_q_len, num_splits, tree, hooks);
+    TGIS_CHECK_ARG(plan->grid[0] <= 2147483647LL && plan->grid[1] <= 65535 && plan->grid[2] <= 65535,
+                   "tgis_attn_paged: grid too large");
     return TGIS_OK;
 }
 
-template <typename T, typename KV, int D>
-static int launch_attn(const AttnArgs& a, dim3 grid, int64_t total_q, const int32_t* q_end, hipStream_t st, int nw,
-                       int ch) {
-    const int rc = by_int<1, 2, 3>(ch, "tgis_attn_paged: chunks per block", [&](auto chc) {
-        constexpr int CH = decltype(chc)::value;
-        auto one = [&](auto nwc) {
-            launch_attn_one<T, KV, D, decltype(nwc)::value, CH>(a, grid, st);
-            TGIS_CHECK_LAUNCH();
-            return TGIS_OK;
-        };
-        // wide blocks (8 waves): few (sequence, kv head) groups, the waves of one block share the keys; three waves per
-        // SIMD at 1024 blocks is an A/B hook.  Both exist for one-chunk blocks only.
-        if constexpr (CH == 1) return by_int<1, 2, 3, 4, 8>(nw, "tgis_attn_paged: waves per block", one);
-        else return by_int<1, 2, 4>(nw, "tgis_attn_paged: waves per block", one);
-    });
-    if (rc != TGIS_OK) return rc;
-    return launch_combine<T, D>(a, total_q, q_end, st);
-}
-
-// tgis_attn_paged_tree: the decode form only, as one-chunk blocks of 4 waves — what tgis_attn_paged launches by default at
-// q_len > 1.  The A/B hooks of that launch (TGIS_ATTN_NW, TGIS_ATTN_CH, TGIS_ATTN_PIPE, TGIS_ATTN_XCD) are NOT read here: a
-// measurement that sets one of them compares the causal launch in another configuration with this one as it always is.
-template <typename T, typename KV, int D>
-static int launch_attn_tree(const AttnTreeArgs& a, dim3 grid, int64_t total_q, const int32_t* q_end, hipStream_t st) {
-    constexpr int NW = 4;
-    const size_t lds = (size_t)(NW * D * 16 + NW * 2 * 16) * sizeof(float);  // <= 32.5 KiB: no attribute to raise
-    launch_attn_kernel(attn_paged_kernel<T, KV, D, NW, 1, false, true>, grid, NW, lds, st, a);
-    TGIS_CHECK_LAUNCH();
-    return launch_combine<T, D>(a, total_q, q_end, st);
+// the only place that writes an argument block: the geometry and launch form from the plan, the rest from the caller
+static AttnTreeArgs fill_args(const AttnPlan& p, int H, int Hkv, int num_splits, const void* q, int64_t ld_q,
+                              const void* k_pool, const void* v_pool, const int32_t* block_tables, int64_t max_pages,
+                              const int32_t* ctx_lens, const int32_t* cu_seqlens_q, void* out, bool out_frag, float scale_log2,
+                              float inv_v_scale, void* workspace, unsigned* counters, const uint64_t* q_mask) {
+    AttnTreeArgs a;
+    a.q = q, a.ld_q = ld_q, a.kpool = k_pool, a.vpool = v_pool;
+    a.bt = block_tables, a.max_pages = max_pages, a.ctx_lens = ctx_lens, a.cu_q = cu_seqlens_q;
+    a.out = out, a.out_frag = out_frag, a.H = H, a.Hkv = Hkv, a.NS = num_splits;
+    a.G = p.geom.G, a.Gc = p.geom.Gc, a.Gp = p.geom.Gp, a.Gp_shift = p.geom.Gp_shift, a.TQ = p.geom.TQ, a.HC = p.geom.HC;
+    a.HCB = p.HCB, a.xcd_remap = p.xcd_remap;
+    a.scale_log2 = scale_log2, a.inv_v_scale = inv_v_scale;
+    a.ws_o = num_splits > 1 ? (float*)workspace : nullptr;
+    a.ws_ml = num_splits > 1 ? a.ws_o + p.ws_o_floats[counters != nullptr] : nullptr;
+    a.counters = counters, a.q_mask = q_mask;
+    return a;
 }
 
 }  // namespace
 
 extern "C" int tgis_attn_num_splits(int64_t B, int Hkv, int H, int64_t max_q_len, int64_t max_ctx) {
-    if (B <= 0 || Hkv <= 0 || H <= 0 || H % Hkv != 0 || max_q_len != 1) return 1;  // splits: decode only
-    AttnGeom g = geom(H, Hkv);
-    int64_t q_tiles = cdiv64(max_q_len, g.TQ);
-    const int ch = chunks_per_block(g.HC, max_q_len);
-    int64_t base = B * Hkv * cdiv64(g.HC, ch) * q_tiles;
-    int64_t pages = cdiv64(std::max<int64_t>(max_ctx, 1), 32);
-    // single-chunk blocks, many groups: ~512 blocks fill 256 CUs twice; more, thinner blocks lose to the dispatch ramp
-    // and the merge
-    int64_t ns;
-    if (wide_decode_blocks(base, ch)) {
-        // few (sequence, kv head) groups: 8-wave blocks, one round of <= 256 of them, >= 2 pages per wave
-        // (tools/attn_nw.py, us: B=16 GQA 8:1 D=64 ctx 512: 6.8 unsplit vs 8.5 at 4 splits of 4 waves;
-        //  B=1 MHA D=128 ctx 2048: 14.1 at 8 splits vs 17.7 at 16; B=4 GQA 4:1 ctx 4096: 19.0 at 8 vs 24.0 at 16)
-        ns = std::min<int64_t>(cdiv64(256, base), pages / 16);
-        // Round 6 (profiles/r06_attn_fewgroups.log, first column = the rule above): from 32 pages on, up to 8 splits of >= 8
-        // pages pay as long as every block still gets a CU of its own — B 1 MHA ctx 1024 11.6 -> 9.5 us (2 -> 8 splits), B 4
-        // GQA 8:1 12.3 -> 10.4, B 8 GQA 8:1 D 64 9.4 -> 8.3, B 2 MHA 12.9 -> 11.8; 96 groups keep 2 (3 would be 288 blocks:
-        // 16.4 vs 14.3), 16 pages keep 1 (8.7 vs 10.2), long contexts keep the rule above (>= 16 pages per block).
-        if (pages >= 32) ns = std::max<int64_t>(ns, std::min<int64_t>(std::min<int64_t>(256 / base, pages / 8), 8));
-        // From 128 groups on the merge costs more than the second half of the CUs gives while the context is short (a 7B rank at
-        // TP = 8, B 32 x 4 heads, ctx 1024: 16.0 us unsplit, 16.5 at 2 splits; 64 groups, ctx 2048: 24.0 / 19.2 / 17.7 at
-        // 1 / 2 / 4 — profiles/r05_attn_tp8.log).  Round 6 swept it over the context (profiles/r06_attn_base128.log): exactly
-        // 128 groups take 2 splits from ctx 2048 on (26.9 vs 29.1 us, 46.0 vs 51.7 at 4096, 166.6 vs 194.8 at 16384: the page
-        // walk grows, the merge does not); 129 - 255 groups never do (2 splits would be a second round of blocks: 192 groups
-        // 41.2 vs 34.9 at 2048, 272.8 vs 243.5 at 16384).
-        if (base >= 128) ns = (base * 2 <= 256 && pages >= 64) ? 2 : 1;
-    } else if (ch > 1) {
-        // multi-chunk blocks hold three sets of accumulators: one block per CU, one wave per SIMD, so the block's time is
-        // its waves' page count (~1 us per page: issue-bound) plus ~12 us.  Their splits are merged by the combine launch,
-        // not in the launch (a last-arriving block reads NS x 24 KB through ONE CU: 2.7 us at 4 splits, 5.4 at 8).
-        // 48 q heads on 1 kv head, B=32 ctx 4096, us (kernel + combine): 26.7 at 4 splits, 25.1 at 6, 25.3 at 8
-        // (in-launch merge: 28.1 / 28.6 / 30.2)
-        // round 6: with the combine launch down to one round trip (24.1 vs 25.3 us at 6 splits) 8 splits = 256 blocks edge out
-        // 6 (23.9 vs 24.2, profiles/r06_mqa_variants.log)
-        ns = std::min<int64_t>(cdiv64(256, base), pages / 16);
-    } else {
-        ns = cdiv64(512, base);
-        ns = std::min<int64_t>(ns, cdiv64(pages, 4));  // at least one page per wave
-    }
-    ns = std::max<int64_t>(1, std::min<int64_t>(ns, 64));
-    return (int)ns;
+    return attn_num_splits(B, Hkv, H, max_q_len, max_ctx, attn_hooks());
 }
-
-// Key splits of any decode-form launch: tgis_attn_num_splits at q_len 1, 1 for the prefill form, and for a few q tokens per
-// sequence (a verify step of speculative decoding, a short suffix behind reused prefix pages) the rule below.
 extern "C" int tgis_attn_num_splits_q(int64_t B, int Hkv, int H, int64_t max_q_len, int64_t max_ctx) {
-    if (max_q_len == 1) return tgis_attn_num_splits(B, Hkv, H, max_q_len, max_ctx);
-    if (B <= 0 || Hkv <= 0 || H <= 0 || H % Hkv != 0 || max_q_len < 1) return 1;
-    AttnGeom g = geom(H, Hkv);
-    if (max_q_len * g.Gp > 64) return 1;  // the prefill form takes no key splits
-    const int64_t pages = cdiv64(std::max<int64_t>(max_ctx, 1), 32);
-    if (max_ctx < 1024) return 1;  // below 1024 keys (32 pages) every q_len > 1 launch stays the one it was
-    // One-chunk blocks of 4 waves, one per (sequence, kv head, 16-head chunk, q tile) and split.  Fitted to
-    // profiles/attn_qsplit_sweep.log (us per launch, D 128):
-    //  - one round of <= 256 blocks (the floor: 11 splits of 24 groups are 264 blocks, 36.9 us where 8 take 30.7), >= 16 pages
-    //    per block;
-    //  - short contexts: up to 8 splits of >= 4 pages, one per wave (7B B 1 q 4 ctx 1024: 19.9 unsplit, 15.4 at 2, 11.8 at 8;
-    //    GQA 8:1 B 1 q 2 ctx 2048: 13.5 at 8, 15.1 at 16);
-    //  - 64 - 255 groups: a second round of blocks pays from 32 pages per block on (7B B 4 q 4 ctx 8192: 91.6 at 2, 86.3 at 4;
-    //    GQA 8:1 B 4 q 4 ctx 32768: 177.2 at 4, 168.3 at 8); fewer groups lose to the merge (GQA 8:1 B 1 q 4 ctx 32768: 55.9 at
-    //    16, 59.2 at 32);
-    //  - from 256 groups on the launch stays unsplit: 2 splits give 3 - 8 % from ctx 8192 on and lose below it.
-    const int64_t base = B * Hkv * g.HC * cdiv64(max_q_len, g.TQ);
-    const int64_t one = 256 / base;
-    int64_t ns = std::min<int64_t>(one, pages / 16);
-    ns = std::max<int64_t>(ns, std::min<int64_t>(std::min<int64_t>(one, pages / 4), 8));
-    if (base >= 64 && base < 256) ns = std::max<int64_t>(ns, std::min<int64_t>(512 / base, pages / 32));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(ns, 32));  // (no count above 32 was measured)
+    return attn_num_splits_q(B, Hkv, H, max_q_len, max_ctx, attn_hooks());
 }
-
-// records of the fused combine: [group = (q tile, kv head, chunk block, sequence)][chunk][16 columns][split]
-static int64_t fused_records(int64_t B, int H, int Hkv, int64_t max_q_len, int num_splits) {
-    AttnGeom g = geom(H, Hkv);
-    const int ch = chunks_per_block(g.HC, max_q_len);
-    return B * cdiv64(max_q_len, g.TQ) * Hkv * cdiv64(g.HC, ch) * ch * 16 * num_splits;
-}
-
 extern "C" int64_t tgis_attn_workspace_bytes(int64_t total_q_tokens, int H, int Hkv, int D, int num_splits) {
-    if (num_splits <= 1 || Hkv <= 0 || H % Hkv != 0) return 0;
-    // the larger of the two layouts: per (token, head, split) {O[D], m, l} for the two-launch combine, or the
-    // line-padded records of the fused one (16 columns per group and chunk, {m, l} in 16 bytes)
-    const int64_t two_pass = total_q_tokens * H * num_splits * ((int64_t)D + 2) * 4;
-    // The fused size is that of total_q_tokens sequences of one token.  It covers B sequences of max_q_len tokens
-    // (total_q_tokens = B * max_q_len) as well: their launch has B * ceil(max_q_len / TQ) <= total_q_tokens q tiles per
-    // (kv head, chunk block), and one-chunk blocks over all HC <= ceil(HC / ch) * ch chunks.
-    const int64_t fused = fused_records(total_q_tokens, H, Hkv, 1, num_splits) * ((int64_t)D + 4) * 4;
-    return std::max(two_pass, fused);
+    return attn_workspace_bytes(total_q_tokens, H, Hkv, D, num_splits, attn_hooks());
 }
 
-namespace {
-constexpr int64_t ATTN_COUNTERS = 1 << 20;
-constexpr int ATTN_COUNTER_SETS = 4;
-
-// Arrival counters of the fused combine, one per group; zero between launches (the last arriver resets its own).
-// Owned by the library: a pool of ATTN_COUNTER_SETS arrays per device, handed out per STREAM — two split-key launches that
-// overlap on one device are necessarily on different streams, so they never share an array (launches of one stream are
-// ordered).  The pool is allocated by the first call that is not inside a stream capture (the eager warm-up step); handing
-// an array of the pool to a new stream needs no allocation, so a capture stream gets one too.  A fifth concurrent stream,
-// or a capture before any eager call, falls back to the separate combine launch.
-struct CounterPool {
-    unsigned* sets[ATTN_COUNTER_SETS] = {};
-    hipStream_t owner[ATTN_COUNTER_SETS] = {};
-    uint64_t last_use[ATTN_COUNTER_SETS] = {};  // launch stamp: the least recently used slot is handed to a new stream
-    bool in_graph[ATTN_COUNTER_SETS] = {};      // a captured graph holds this slot's pointer: it never changes hands
-    int pending[ATTN_COUNTER_SETS] = {};        // handed out, launch not enqueued yet: an idle owner stream proves nothing
-    uint64_t stamp = 0;
-    int used = 0;
-    bool ready = false;
-    bool warned = false;
-};
-std::mutex g_attn_counters_mu;
-std::map<int, CounterPool> g_attn_counters;
-
-// `slot` receives the index to give back with attn_counters_enqueued() once the launch that uses the array is in its
-// stream (between this call and the launch a second host thread could see the new owner's stream idle and take
-// the same array).
-unsigned* attn_counters(hipStream_t st, int* dev_out, int* slot) {
-    *slot = -1;
-    static const bool off = getenv("TGIS_ATTN_FUSED_COMBINE") && atoi(getenv("TGIS_ATTN_FUSED_COMBINE")) == 0;
-    if (off) return nullptr;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    *dev_out = dev;
-    std::lock_guard<std::mutex> lock(g_attn_counters_mu);
-    CounterPool& pool = g_attn_counters[dev];
-    if (!pool.ready) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        unsigned* p = nullptr;
-        const size_t bytes = (size_t)ATTN_COUNTER_SETS * ATTN_COUNTERS * sizeof(unsigned);
-        if (hipMalloc((void**)&p, bytes) != hipSuccess || hipMemset(p, 0, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        (void)hipDeviceSynchronize();
-        for (int i = 0; i < ATTN_COUNTER_SETS; ++i) pool.sets[i] = p + (size_t)i * ATTN_COUNTERS;
-        pool.ready = true;
-    }
-    ++pool.stamp;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool query_failed = hipStreamIsCapturing(st, &cs) != hipSuccess;
-    if (query_failed) (void)hipGetLastError();  // not this launch's error: do not leave it for TGIS_CHECK_LAUNCH
-    const bool capturing = query_failed || cs != hipStreamCaptureStatusNone;
-    for (int i = 0; i < pool.used; ++i)
-        if (pool.owner[i] == st) {
-            pool.last_use[i] = pool.stamp;
-            pool.in_graph[i] |= capturing;
-            ++pool.pending[i];
-            *slot = i;
-            return pool.sets[i];
-        }
-    if (pool.used < ATTN_COUNTER_SETS) {
-        pool.owner[pool.used] = st;
-        pool.last_use[pool.used] = pool.stamp;
-        pool.in_graph[pool.used] = capturing;
-        ++pool.pending[pool.used];
-        *slot = pool.used;
-        return pool.sets[pool.used++];
-    }
-    // All slots are owned.  A slot whose stream has no launch in flight can change hands (its counters are zero between
-    // launches): take the least recently used one if its stream is idle (hipStreamQuery on a destroyed or capturing stream
-    // fails — then the slot stays put and this launch uses the separate combine kernel, which is always correct).
-    // (a slot whose pointer sits in a captured graph stays where it is: the graph replays on streams this pool never sees)
-    int lru = -1;
-    for (int i = 0; i < ATTN_COUNTER_SETS; ++i)
-        if (!pool.in_graph[i] && pool.pending[i] == 0 && (lru < 0 || pool.last_use[i] < pool.last_use[lru])) lru = i;
-    hipStreamCaptureStatus ocs = hipStreamCaptureStatusNone;
-    // (a query on a stream that is being captured would invalidate its capture: ask that first)
-    const bool owner_capturing = lru < 0 || hipStreamIsCapturing(pool.owner[lru], &ocs) != hipSuccess ||
-                                 ocs != hipStreamCaptureStatusNone;
-    if (!capturing && !owner_capturing && hipStreamQuery(pool.owner[lru]) == hipSuccess) {
-        pool.owner[lru] = st;
-        pool.last_use[lru] = pool.stamp;
-        ++pool.pending[lru];
-        *slot = lru;
-        return pool.sets[lru];
-    }
-    (void)hipGetLastError();
-    if (!pool.warned) {
-        pool.warned = true;
-        fprintf(stderr, "tgis_attn_paged: more than %d streams use split-key decode attention on device %d; the extra ones "
-                        "merge their splits with a second launch\n", ATTN_COUNTER_SETS, dev);
-    }
-    return nullptr;
+// debug aid (not part of the documented ABI): the launch tgis_attn_paged (tree != 0: tgis_attn_paged_tree) would make under
+// the current hooks, without a launch, a device or a stream.  info[16] = {form (0 prefill, 1 decode, 2 tree), waves per block,
+// chunks per block, PIPE, HCB, xcd_remap, grid x, y, z, LDS bytes, fused_ok (NS > 1 and the splits merge in the launch if an
+// arrival-counter array is free; else the combine launch), maxs8 (that launch is attn_combine_kernel<MAXS = 8>), Gp, TQ, HC, NS}.
+extern "C" int tgis_debug_attn_plan(int64_t B, int H, int Hkv, int D, int64_t max_q_len, int num_splits, int tree, int* info) {
+    TGIS_CHECK_ARG(info && B >= 1, "tgis_debug_attn_plan: bad arguments");
+    AttnPlan p;
+    if (const int rc = checked_plan(B, H, Hkv, D, max_q_len, num_splits, tree != 0, attn_hooks(), &p)) return rc;
+    const int v[16] = {p.form, p.nw, p.ch, p.pipe, p.HCB, p.xcd_remap, (int)p.grid[0], (int)p.grid[1], (int)p.grid[2],
+                       (int)p.lds_bytes, p.fused_ok, p.maxs8, p.geom.Gp, p.geom.TQ, p.geom.HC, num_splits};
+    std::copy(v, v + 16, info);
+    return TGIS_OK;
 }
-void attn_counters_enqueued(int dev, int slot) {
-    if (slot < 0) return;
-    std::lock_guard<std::mutex> lock(g_attn_counters_mu);
-    --g_attn_counters[dev].pending[slot];
-}
-struct CounterLease {  // gives the slot back when the launch is in its stream (or the call fails before it)
-    int dev = 0, slot = -1;
-    ~CounterLease() { attn_counters_enqueued(dev, slot); }
-};
-}  // namespace
 
+// validate, plan, lease counters where the plan may merge in the launch, fill the argument block, launch
 static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, const void* v_pool,
                            const int32_t* block_tables, int64_t max_pages, const int32_t* ctx_lens,
                            const int32_t* cu_seqlens_q, void* out, int64_t ld_out, int64_t B, int H, int Hkv, int D,
@@ -885,123 +676,45 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
                            float v_scale, bool tree = false, const uint64_t* q_mask = nullptr) {
     TGIS_CHECK_ARG(q && k_pool && v_pool && block_tables && ctx_lens && cu_seqlens_q && out,
                    "tgis_attn_paged: null tensor");
-    TGIS_CHECK_ARG(H > 0 && Hkv > 0 && H % Hkv == 0, "tgis_attn_paged: H (%d) must be a multiple of Hkv (%d)", H, Hkv);
-    TGIS_CHECK_ARG(D == 64 || D == 96 || D == 128, "tgis_attn_paged: head_dim %d not supported (64, 96, 128)", D);
+    TGIS_CHECK_ARG(!tree || q_mask, "tgis_attn_paged_tree: null q_mask");
     TGIS_CHECK_ARG(dtype == TGIS_F16 || dtype == TGIS_BF16, "tgis_attn_paged: bad dtype");
     TGIS_CHECK_KV_ARGS("tgis_attn_paged_kv8", kv_dtype, k_scale, v_scale);
     const bool kv8 = kv_dtype == TGIS_KV_FP8_E4M3;
     TGIS_CHECK_ARG(ld_q % 8 == 0 && ((uintptr_t)q % 16) == 0, "tgis_attn_paged: q must be 16-byte aligned");
-    TGIS_CHECK_ARG(max_q_len > 0 && max_pages > 0 && num_splits >= 1, "tgis_attn_paged: bad launch bounds");
+    TGIS_CHECK_ARG(max_pages > 0, "tgis_attn_paged: bad launch bounds");
+    (void)max_ctx;
+    const AttnHooks hooks = attn_hooks();  // read once per call
+    AttnPlan plan;
+    if (const int rc = checked_plan(B, H, Hkv, D, max_q_len, num_splits, tree, hooks, &plan)) return rc;
     TGIS_CHECK_ARG(ld_out == 0 || ld_out == (int64_t)H * D ||
                        (ld_out == TGIS_LD_FRAGMENTS && max_q_len == 1 && B <= 64 && ((int64_t)H * D) % 64 == 0),
                    "tgis_attn_paged: out is [tokens, H * D] contiguous (ld_out = 0 or H * D), or — decode, <= 64 sequences — in "
                    "fragment order (ld_out = TGIS_LD_FRAGMENTS)");
-    (void)max_ctx;
-    AttnGeom g = geom(H, Hkv);
-    const bool prefill_form = max_q_len * g.Gp > 64;
-    TGIS_CHECK_ARG(num_splits == 1 || !prefill_form,
-                   "tgis_attn_paged: key splits are for the decode form (max_q_len * padded group size <= 64, here %ld * %d): "
-                   "the prefill form takes none", (long)max_q_len, g.Gp);
-    if (tree) {
-        TGIS_CHECK_ARG(q_mask, "tgis_attn_paged_tree: null q_mask");
-        TGIS_CHECK_ARG(!prefill_form,
-                       "tgis_attn_paged_tree: only the decode form is served (max_q_len * padded group size <= 64, here %ld * "
-                       "%d): one 64-bit mask word per q row", (long)max_q_len, g.Gp);
-    }
     if (B == 0) return TGIS_OK;
     hipStream_t st = (hipStream_t)stream;
-    AttnTreeArgs a;
-    a.q_mask = q_mask;
-    a.q = q;
-    a.ld_q = ld_q;
-    a.kpool = k_pool;
-    a.vpool = v_pool;
-    a.bt = block_tables;
-    a.max_pages = max_pages;
-    a.ctx_lens = ctx_lens;
-    a.cu_q = cu_seqlens_q;
-    a.out = out;
-    a.out_frag = ld_out == TGIS_LD_FRAGMENTS;
-    a.H = H;
-    a.Hkv = Hkv;
-    a.G = g.G;
-    a.Gc = g.Gc;
-    a.Gp = g.Gp;
-    a.Gp_shift = 0;
-    while ((1 << a.Gp_shift) < g.Gp) ++a.Gp_shift;
-    a.TQ = g.TQ;
-    a.HC = g.HC;
-    const int ch = tree ? 1 : chunks_per_block(g.HC, max_q_len);  // (the tree variant: one-chunk blocks at any q_len)
-    a.HCB = (g.HC + ch - 1) / ch;
-    a.NS = num_splits;
-    a.scale_log2 = kv8 ? scale * k_scale * 1.4426950408889634f : scale * 1.4426950408889634f;
-    a.inv_v_scale = kv8 ? 1.f / v_scale : 1.f;
-    a.ws_o = nullptr;
-    a.ws_ml = nullptr;
-    a.counters = nullptr;
-    int64_t total_q = 0;
-    CounterLease lease;
+    // total q tokens is only needed to size the split workspace; callers pass B*max_q_len rows
+    const int64_t total_q = B * max_q_len;
     if (num_splits > 1) {
-        // total q tokens is only needed to size the split workspace; callers pass B*max_q_len rows
-        total_q = B * max_q_len;
-        int64_t need = tgis_attn_workspace_bytes(total_q, H, Hkv, D, num_splits);
+        const int64_t need = attn_workspace_bytes(total_q, H, Hkv, D, num_splits, hooks);
         TGIS_CHECK_ARG(workspace && workspace_bytes >= need, "tgis_attn_paged: workspace too small (%ld < %ld)",
                        (long)workspace_bytes, (long)need);
-        a.ws_o = (float*)workspace;
-        a.ws_ml = a.ws_o + total_q * H * num_splits * D;
-        // one launch: the last block of each (q tile, kv head, chunk block, sequence) group merges the splits (no combine launch)
-        const int64_t recs = fused_records(B, H, Hkv, max_q_len, num_splits);
-        const int64_t groups = B * cdiv64(max_q_len, g.TQ) * Hkv * a.HCB;
-        if (groups <= ATTN_COUNTERS && recs * D * 4 < (1ll << 31) && ch == 1) {
-            a.counters = attn_counters(st, &lease.dev, &lease.slot);
-            if (a.counters) a.ws_ml = a.ws_o + recs * D;
-        }
     }
-    // long q (prefill): blocks of 128 columns that stage each K/V page once in LDS (attention_prefill.hip)
-    if (prefill_form && !getenv("TGIS_ATTN_NO_PREFILL_KERNEL")) {
-        TgisTimedScope timed(TGIS_OP_ATTN, st);
-        return tgis_launch_attn_prefill(a, B, Hkv, D, max_q_len, dtype, kv8, st);
-    }
-    int64_t q_tiles = cdiv64(max_q_len, g.TQ);
-    TGIS_CHECK_ARG(q_tiles <= 2147483647LL && (int64_t)Hkv * a.HCB <= 65535 && B * num_splits <= 65535,
-                   "tgis_attn_paged: grid too large");
-    dim3 grid((unsigned)q_tiles, (unsigned)(Hkv * a.HCB), (unsigned)(B * num_splits));
-    // the combine launch of a q_len > 1 call runs over B * max_q_len rows: it reads the real count, cu_seqlens_q[B]
-    const int32_t* q_end = max_q_len > 1 ? cu_seqlens_q + B : nullptr;
-    if (tree) {
-        a.xcd_remap = 0;
-        TgisTimedScope timed(TGIS_OP_ATTN, st);
-        return by_dtype(dtype, [&](auto t) {
-            using T = type_of<decltype(t)>;
-            return by_kv<T>(kv8, [&](auto kv) {
-                return by_int<128, 96, 64>(D, "tgis_attn_paged_tree: head_dim", [&](auto d) {
-                    return launch_attn_tree<T, type_of<decltype(kv)>, decltype(d)::value>(a, grid, total_q, q_end, st);
-                });
-            });
-        });
-    }
-    {
-        static const bool xcd_off = getenv("TGIS_ATTN_XCD") && atoi(getenv("TGIS_ATTN_XCD")) == 0;  // A/B hook
-        a.xcd_remap = (!xcd_off && max_q_len == 1 && q_tiles == 1 && a.HCB > 1 && (B * num_splits * Hkv) % 8 == 0) ? 1 : 0;
-    }
-    // waves per block: with >= 1024 (sequence, kv head) blocks the chip is full either way and 2-wave blocks halve
-    // the page-count imbalance between a block's waves (33 pages over 4 waves = 9/8/8/8; over 2 = 17/16)
-    const int64_t nblocks = (int64_t)grid.x * grid.y * grid.z;
-    // (past ~2k blocks the dispatch rate, 7 ns per workgroup, costs more than the imbalance)
-    int nw = (max_q_len == 1 && nblocks >= 1024 && nblocks < 2048) ? 2 : 4;
-    if (max_q_len == 1 && wide_decode_blocks(nblocks / num_splits, ch)) nw = 8;
-    if (const char* e = getenv("TGIS_ATTN_NW")) {
-        const int v = atoi(e);
-        nw = (v == 1 || v == 2 || v == 3 || v == 8) ? v : 4;
-        if (ch > 1 && (nw > 4 || nw == 3)) nw = 4;
-    }
+    // arrival counters for the in-launch merge, if the plan allows it and an array is free (else: the combine launch)
+    CounterLease lease;
+    unsigned* counters = plan.fused_ok ? attn_counters(st, &lease.dev, &lease.slot) : nullptr;
+    const AttnTreeArgs a = fill_args(plan, H, Hkv, num_splits, q, ld_q, k_pool, v_pool, block_tables, max_pages, ctx_lens,
+                                     cu_seqlens_q, out, ld_out == TGIS_LD_FRAGMENTS,
+                                     (kv8 ? scale * k_scale : scale) * 1.4426950408889634f, kv8 ? 1.f / v_scale : 1.f, workspace,
+                                     counters, q_mask);
     TgisTimedScope timed(TGIS_OP_ATTN, st);
+    if (plan.form == ATTN_PREFILL) return tgis_launch_attn_prefill(a, B, Hkv, D, max_q_len, dtype, kv8, st);
+    const int32_t* q_end = max_q_len > 1 ? cu_seqlens_q + B : nullptr;
     return by_dtype(dtype, [&](auto t) {
         using T = type_of<decltype(t)>;
         return by_kv<T>(kv8, [&](auto kv) {  // one-byte cache: the same launch shapes over e4m3 pools
             // D = 96: KS = 3, NB = 6 (gpt-neox-20b)
             return by_int<128, 96, 64>(D, "tgis_attn_paged: head_dim", [&](auto d) {
-                return launch_attn<T, type_of<decltype(kv)>, decltype(d)::value>(a, grid, total_q, q_end, st, nw, ch);
+                return launch_decode<T, type_of<decltype(kv)>, decltype(d)::value>(plan, a, total_q, q_end, st);
             });
         });
     });
