@@ -402,6 +402,28 @@ int tgis_attn_paged_tree_kv8(const void* q, int64_t ld_q, const void* k_pool, co
                              int64_t workspace_bytes, void* stream, int kv_dtype, float k_scale, float v_scale,
                              const uint64_t* q_mask);
 
+/* tgis_attn_paged under a sliding window (Mistral's config.sliding_window; the reference has no such model, the semantics
+ * are those of transformers' MistralForCausalLM; call site utils/flash_attn.py:43-78): the q row at cache position p attends
+ * to the `window` positions p - window < j <= p, its own among them.  window >= 1.  A window that no row of the launch
+ * reaches (max_ctx <= window) is the tgis_attn_paged launch, bit for bit.
+ * max_q_len == 1: the decode kernel's window variant.  Pages wholly below a sequence's window are not loaded and their
+ * block_tables entries are not read; key splits divide the visible pages (callers take num_splits from
+ * tgis_attn_num_splits(B, Hkv, H, 1, min(max_ctx, window + 31))), workspace (tgis_attn_workspace_bytes), both merges, `out`
+ * and ld_out = TGIS_LD_FRAGMENTS are those of tgis_attn_paged.
+ * max_q_len > 1: always the prefill kernel's window variant, whatever the group size; num_splits must be 1.
+ * window < 1, num_splits > 1 with max_q_len > 1, or a missing / short workspace with splits is TGIS_EINVAL before any launch. */
+int tgis_attn_paged_window(const void* q, int64_t ld_q, const void* k_pool, const void* v_pool, const int32_t* block_tables,
+                           int64_t max_pages, const int32_t* ctx_lens, const int32_t* cu_seqlens_q, void* out, int64_t ld_out,
+                           int64_t B, int H, int Hkv, int D, int64_t max_q_len, int64_t max_ctx, float scale, int dtype,
+                           int num_splits, void* workspace, int64_t workspace_bytes, void* stream, int64_t window);
+/* tgis_attn_paged_window over pools of element kv_dtype, as tgis_attn_paged_kv8 is to tgis_attn_paged (utils/flash_attn.py:43-78). */
+int tgis_attn_paged_window_kv8(const void* q, int64_t ld_q, const void* k_pool, const void* v_pool,
+                               const int32_t* block_tables, int64_t max_pages, const int32_t* ctx_lens,
+                               const int32_t* cu_seqlens_q, void* out, int64_t ld_out, int64_t B, int H, int Hkv, int D,
+                               int64_t max_q_len, int64_t max_ctx, float scale, int dtype, int num_splits, void* workspace,
+                               int64_t workspace_bytes, void* stream, int kv_dtype, float k_scale, float v_scale,
+                               int64_t window);
+
 /* ---- KV-cache statistics (replaces nothing in the reference, which has no quantised cache: the calibration pass of the
  *      one-byte cache, utils/kv_cache.py) -------------------------------------------------------------- */
 /* Max |x| per kv head over the tokens that B sequences hold in ONE layer's 16-bit pools (dtype TGIS_F16 / TGIS_BF16; D 64,

@@ -51,6 +51,12 @@ namespace {
 // from there on takes the masked body, which tests one more bit per score.  The mask changes scores only: the pages a block
 // walks and every address it loads from are those of the TREE = false kernel for the same ctx_lens and cu_seqlens_q (a page
 // that is full but masked goes through load_page_part with nv = 32, which requests what load_page requests).
+// WINDOW (tgis_attn_paged_window at one q token per sequence: one-chunk blocks of 4 waves, no PIPE): the argument block carries
+// `window`, W keys per q row.  The block's pages begin at the first page its first q row sees (attention_plan.h
+// attn_window_first_key) instead of page 0: pages below it are not loaded and their table entries not read, and the key splits
+// divide that range.  The first of them, when the window starts inside it, takes the masked body with the lower bound — in
+// wave 0 of split 0, in the loop of the partly visible pages — as the page that is being filled takes it with the upper one;
+// when both are one page, that page's pass tests both.
 //
 // Kernel argument preload (csrc/gptq_wide_body.h): the leading scalar parameters — 14 dwords, all the user SGPRs a wave has —
 // arrive in SGPRs at wave launch and overrule the same fields of the argument block behind them.  They are what the FIRST
@@ -58,17 +64,20 @@ namespace {
 // lengths and its block table lie (cu_q, ctx_lens, bt, max_pages); kpool fills the last pair.  Everything else is read from
 // the block and arrives with the lengths, one round trip earlier than it did behind a fetch of the block.  Launched through
 // launch_attn_kernel only.
-template <typename T, typename KV, int D, int NW, int CH, bool PIPE, bool TREE = false>
+template <bool TREE, bool WINDOW>
+using AttnArgsOf = std::conditional_t<TREE, AttnTreeArgs, std::conditional_t<WINDOW, AttnWindowArgs, AttnArgs>>;
+
+template <typename T, typename KV, int D, int NW, int CH, bool PIPE, bool TREE = false, bool WINDOW = false>
 __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(const int32_t* bt, const int32_t* cu_q, const int32_t* ctx_lens,
                                                              const void* kpool, int64_t max_pages, int NS, int Hkv, int HCB,
-                                                             int xcd_remap,
-                                                             std::conditional_t<TREE, AttnTreeArgs, AttnArgs> rest) {
+                                                             int xcd_remap, AttnArgsOf<TREE, WINDOW> rest) {
     static_assert(!TREE || (CH == 1 && !PIPE), "the tree variant exists for one-chunk blocks without the page pipeline");
+    static_assert(!WINDOW || (CH == 1 && !PIPE && !TREE), "the window variant: one-chunk blocks, no page pipeline, no tree");
     using V8 = typename VecT<T>::x8;
     constexpr int KS = D / 32;  // k-steps of the QK^T MFMA
     constexpr int NB = D / 16;  // 16-row blocks of O^T
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    std::conditional_t<TREE, AttnTreeArgs, AttnArgs> a = rest;
+    AttnArgsOf<TREE, WINDOW> a = rest;
     a.bt = bt; a.cu_q = cu_q; a.ctx_lens = ctx_lens; a.kpool = kpool; a.max_pages = max_pages;
     a.NS = NS; a.Hkv = Hkv; a.HCB = HCB; a.xcd_remap = xcd_remap;
     ATTN_STAMP_DECL
@@ -101,7 +110,8 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(const int32_t* bt, 
     // less in front of the first K / V load (inside a decode step those lines are not in this XCD's L2: the GEMMs of the layer
     // have streamed ~100 MB through it since the last attention launch; profiles/r06_attn_cold.log).
     const int32_t* btrow = a.bt + (int64_t)b * a.max_pages;
-    const int pg_spec = (a.NS == 1 && w < a.max_pages) ? btrow[w] : 0;
+    // (WINDOW: a block starts at its first visible page, which the lengths decide)
+    const int pg_spec = (!WINDOW && a.NS == 1 && w < a.max_pages) ? btrow[w] : 0;
     const int q0 = a.cu_q[b], q_len = a.cu_q[b + 1] - q0;
     {   // the requests above are formed from preloaded arguments alone.  Every cache line of the argument block the decode path
         // reads is asked for with them (one scalar round trip instead of one per group of fields: tools/floor/wide.hip `pre`)
@@ -126,13 +136,20 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(const int32_t* bt, 
     if constexpr (TREE) qmask = col_valid[0] ? a.q_mask[q0 + t0 + tq] : 0;
     const int kend = ctx - q_len + min(q_len, t0 + a.TQ);  // keys needed by any column of the tile
     const int pages = (kend + 31) >> 5;
-    const int pps = (pages + a.NS - 1) / a.NS;
-    const int pbeg = split * pps, pend = min(pages, pbeg + pps);
+    // WINDOW: keys below klo are hidden from the tile's first q row, so from every row of the tile; this column's bound is kmin
+    int klo = 0, kmin = 0;
+    if constexpr (WINDOW) {
+        klo = attn_window_first_key(ctx, q_len, t0, a.window);
+        kmin = attn_window_first_key(ctx, q_len, t0 + tq, a.window);
+    }
+    const int pfirst = klo >> 5;  // (0 without a window)
+    const int pps = (pages - pfirst + a.NS - 1) / a.NS;
+    const int pbeg = pfirst + split * pps, pend = min(pages, pbeg + pps);
     ATTN_STAMP(1);  // (the sequence's lengths are in: the stamp macro waits for scalar loads)
     // The first fully visible page's table entry is asked for HERE — as soon as the lengths are in, in front of the q loads and
     // of the partly visible pages: behind them it was a scalar round trip with nothing of this wave in flight (round 5 timeline,
     // profiles/r05_attn_timeline.log: multi-chunk blocks had their first entry 4.8 k ticks after entry, 3.5 k after the lengths).
-    const int pg_first = a.NS == 1 ? pg_spec : ((pbeg + w < pend) ? btrow[pbeg + w] : 0);
+    const int pg_first = (!WINDOW && a.NS == 1) ? pg_spec : ((pbeg + w < pend) ? btrow[pbeg + w] : 0);
 
     // Q^T fragments (B operand): lane supplies Q[col][ks*32 + c*8 .. +8]
     V8 qf[CH][KS];
@@ -229,6 +246,7 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(const int32_t* bt, 
                             const int rel = kp0 + t * 16 + r - (ctx - q_len);
                             vis = vis && (rel < 0 || ((qmask >> (rel & 63)) & 1));
                         }
+                        if constexpr (WINDOW) vis = vis && kp0 + t * 16 + r >= kmin;
                         v = vis ? v : NEG_BIG;
                     }
                     s[t][r] = v;
@@ -273,7 +291,27 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(const int32_t* bt, 
     // independent, and their masked body is a second copy of the page code that each wave runs once — at the end of the
     // launch its instruction fetch and its un-overlapped load were part of every block's tail (ctx 1023 vs 1024: +2.6 us
     // per launch before, +1.7 after); at the start both hide under the first pages' latency.
-    {
+    bool low = false;  // WINDOW: this wave's first page went through the masked loop
+    if constexpr (WINDOW) {
+        // The same loop with one more page in front for the wave that owns it (wave 0 of split 0): the page the window starts
+        // inside, where that is not the sequence's last page anyway.  All of it is written (nv = 32: what load_page requests)
+        // and the masked body hides the keys below this column's kmin.
+        const int nfullp = kfull >> 5;
+        const int pp_top = p + ((max(nfullp - p, 0) + NW - 1) / NW) * NW;
+        low = p == pfirst && (klo & 31) != 0 && p < min(pend, nfullp);
+        int pp = low ? p : pp_top;
+        int pgp = (pp < pend) ? btrow[pp] : 0;
+        while (pp < pend) {
+            const int nxt = pp < pp_top ? pp_top : pp + NW;
+            const int pg_next = (nxt < pend) ? btrow[nxt] : 0;
+            V8 kf[2][KS], vf[NB];
+            load_page_part(pgp, min(32, ctx - pp * 32), kf, vf);
+            apply_page(pp, kf, vf, std::false_type{});
+            pgp = pg_next;
+            pp = nxt;
+        }
+        if (low) p += NW;
+    } else {
         const int nfullp = kfull >> 5;  // pages [0, nfullp) are fully visible
         int pp = p + ((max(nfullp - p, 0) + NW - 1) / NW) * NW;
         int pgp = (pp < pend) ? btrow[pp] : 0;
@@ -312,7 +350,8 @@ __global__ __launch_bounds__(64 * NW) void attn_paged_kernel(const int32_t* bt, 
     // the fully visible pages — a loop of their own, not one loop with both bodies: the register allocator sizes a loop
     // for the union of what its branches hold (180 vs 122 VGPRs here, i.e. 2 instead of 3 waves per SIMD, which costs
     // the HBM-bound many-block shapes 5 %)
-    int pg = PIPE ? ((p < pend) ? btrow[p] : 0) : pg_first;  // (pg_first: valid only when pbeg + w < pend, the loop's p < pend)
+    // (pg_first: valid only when pbeg + w < pend, the loop's p < pend; WINDOW: the loop above may have taken that page)
+    int pg = (PIPE || low) ? ((p < pend) ? btrow[p] : 0) : pg_first;
     for (; p < pend && p * 32 + 32 <= kfull; p += NW) {
         const int pg_next = (p + NW < pend) ? btrow[p + NW] : 0;
         V8 kf[2][KS], vf[NB];
@@ -573,22 +612,31 @@ static void launch_attn_kernel(Kernel kern, dim3 grid, int nw, size_t lds, hipSt
 
 // the decode kernel as the plan names it, then the combine launch of a split call that has no arrival counters (multi-chunk
 // blocks, or none were free).  That one runs over total_q = B * max_q_len rows: it reads the real count, *q_end.
+// (window: the W of a plan of form window, which rides behind the block in an AttnWindowArgs)
 template <typename T, typename KV, int D>
-static int launch_decode(const AttnPlan& p, const AttnTreeArgs& a, int64_t total_q, const int32_t* q_end, hipStream_t st) {
+static int launch_decode(const AttnPlan& p, const AttnTreeArgs& a, int window, int64_t total_q, const int32_t* q_end,
+                         hipStream_t st) {
     const dim3 grid((unsigned)p.grid[0], (unsigned)p.grid[1], (unsigned)p.grid[2]);
-    // the instances that exist, as decimal digits (tree, PIPE, chunks per block, waves per block)
-    const int inst = (p.form == ATTN_TREE) * 1000 + p.pipe * 100 + p.ch * 10 + p.nw;
-    const int rc = by_int<11, 12, 13, 14, 18, 112, 114, 21, 22, 24, 124, 31, 32, 34, 134, 1014>(
-        inst, "tgis_attn_paged: (tree, PIPE, chunks, waves)", [&](auto i) {
+    // the instances that exist, as decimal digits (window, tree, PIPE, chunks per block, waves per block)
+    const int inst = (p.form == ATTN_WINDOW) * 10000 + (p.form == ATTN_TREE) * 1000 + p.pipe * 100 + p.ch * 10 + p.nw;
+    const int rc = by_int<11, 12, 13, 14, 18, 112, 114, 21, 22, 24, 124, 31, 32, 34, 134, 1014, 10014>(
+        inst, "tgis_attn_paged: (window, tree, PIPE, chunks, waves)", [&](auto i) {
         constexpr int I = decltype(i)::value, NW = I % 10, CH = I / 10 % 10;
-        constexpr bool PIPE = I / 100 % 10 != 0, TREE = I / 1000 != 0;
-        auto kern = attn_paged_kernel<T, KV, D, NW, CH, PIPE, TREE>;
+        constexpr bool PIPE = I / 100 % 10 != 0, TREE = I / 1000 % 10 != 0, WINDOW = I / 10000 != 0;
+        auto kern = attn_paged_kernel<T, KV, D, NW, CH, PIPE, TREE, WINDOW>;
         static bool attr = false;  // (per instance)
         if (!attr && p.lds_bytes > 48 * 1024) {
             (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
             attr = true;
         }
-        launch_attn_kernel(kern, grid, NW, (size_t)p.lds_bytes, st, a);
+        if constexpr (WINDOW) {
+            AttnWindowArgs wa;
+            static_cast<AttnArgs&>(wa) = a;
+            wa.window = window;
+            launch_attn_kernel(kern, grid, NW, (size_t)p.lds_bytes, st, wa);
+        } else {
+            launch_attn_kernel(kern, grid, NW, (size_t)p.lds_bytes, st, a);
+        }
         TGIS_CHECK_LAUNCH();
         return TGIS_OK;
     });
@@ -605,19 +653,22 @@ static int launch_decode(const AttnPlan& p, const AttnTreeArgs& a, int64_t total
 // What a shape must satisfy to have a plan, then the plan under `hooks` and its own limit: the checks tgis_attn_paged and
 // tgis_debug_attn_plan share.
 static int checked_plan(int64_t B, int H, int Hkv, int D, int64_t max_q_len, int num_splits, bool tree, const AttnHooks& hooks,
-                        AttnPlan* plan) {
+                        AttnPlan* plan, bool window = false) {
     TGIS_CHECK_ARG(H > 0 && Hkv > 0 && H % Hkv == 0, "tgis_attn_paged: H (%d) must be a multiple of Hkv (%d)", H, Hkv);
     TGIS_CHECK_ARG(D == 64 || D == 96 || D == 128, "tgis_attn_paged: head_dim %d not supported (64, 96, 128)", D);
     TGIS_CHECK_ARG(B >= 0 && max_q_len > 0 && num_splits >= 1, "tgis_attn_paged: bad launch bounds");
     const AttnGeom g = geom(H, Hkv);
-    const bool prefill_form = max_q_len * g.Gp > 64;
+    TGIS_CHECK_ARG(!window || num_splits == 1 || max_q_len == 1,
+                   "tgis_attn_paged_window: key splits are for one q token per sequence (max_q_len %ld): every other windowed "
+                   "call takes the prefill form, which takes none", (long)max_q_len);
+    const bool prefill_form = !window && max_q_len * g.Gp > 64;
     TGIS_CHECK_ARG(num_splits == 1 || !prefill_form,
                    "tgis_attn_paged: key splits are for the decode form (max_q_len * padded group size <= 64, here %ld * %d): "
                    "the prefill form takes none", (long)max_q_len, g.Gp);
     TGIS_CHECK_ARG(!tree || !prefill_form,
                    "tgis_attn_paged_tree: only the decode form is served (max_q_len * padded group size <= 64, here %ld * "
                    "%d): one 64-bit mask word per q row", (long)max_q_len, g.Gp);
-    *plan = plan_attn(B, H, Hkv, D, max_q_len, num_splits, tree, hooks);
+    *plan = plan_attn(B, H, Hkv, D, max_q_len, num_splits, tree, hooks, window);
     TGIS_CHECK_ARG(plan->grid[0] <= 2147483647LL && plan->grid[1] <= 65535 && plan->grid[2] <= 65535,
                    "tgis_attn_paged: grid too large");
     return TGIS_OK;
@@ -667,25 +718,56 @@ extern "C" int tgis_debug_attn_plan(int64_t B, int H, int Hkv, int D, int64_t ma
     return TGIS_OK;
 }
 
+// tgis_debug_attn_plan for tgis_attn_paged_window with a window of `window` keys per q row (not part of the documented ABI
+// either; host only).  info[16] as above: form 3 is the WINDOW variant of the decode kernel (max_q_len 1), form 0 here the WINDOW
+// variant of the prefill kernel (any other max_q_len).  A window no row reaches (max_ctx <= window) is the causal launch, which
+// tgis_debug_attn_plan reports.  For each of n sequences of ctx[i] cached tokens, the last q_len[i] of them q rows, under this
+// window: first[2 i] = the first page its blocks load (table entries below it are not read), first[2 i + 1] = the first key its
+// first q row attends to.
+extern "C" int tgis_debug_attn_plan_window(int64_t B, int H, int Hkv, int D, int64_t max_q_len, int num_splits, int64_t window,
+                                           int64_t n, const int32_t* ctx, const int32_t* q_len, int* info, int* first) {
+    TGIS_CHECK_ARG(info && B >= 1 && n >= 0 && (n == 0 || (ctx && q_len && first)), "tgis_debug_attn_plan_window: bad arguments");
+    TGIS_CHECK_ARG(window >= 1, "tgis_attn_paged_window: window %ld must be at least 1", (long)window);
+    AttnPlan p;
+    if (const int rc = checked_plan(B, H, Hkv, D, max_q_len, num_splits, false, attn_hooks(), &p, true)) return rc;
+    const int v[16] = {p.form, p.nw, p.ch, p.pipe, p.HCB, p.xcd_remap, (int)p.grid[0], (int)p.grid[1], (int)p.grid[2],
+                       (int)p.lds_bytes, p.fused_ok, p.maxs8, p.geom.Gp, p.geom.TQ, p.geom.HC, num_splits};
+    std::copy(v, v + 16, info);
+    const int w = (int)std::min<int64_t>(window, 2147483647);
+    for (int64_t i = 0; i < n; ++i) {
+        TGIS_CHECK_ARG(q_len[i] >= 1 && q_len[i] <= ctx[i], "tgis_debug_attn_plan_window: 1 <= q_len <= ctx");
+        first[2 * i + 1] = attn_window_first_key(ctx[i], q_len[i], 0, w);
+        first[2 * i] = first[2 * i + 1] >> 5;
+    }
+    return TGIS_OK;
+}
+
 // validate, plan, lease counters where the plan may merge in the launch, fill the argument block, launch
 static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, const void* v_pool,
                            const int32_t* block_tables, int64_t max_pages, const int32_t* ctx_lens,
                            const int32_t* cu_seqlens_q, void* out, int64_t ld_out, int64_t B, int H, int Hkv, int D,
                            int64_t max_q_len, int64_t max_ctx, float scale, int dtype, int num_splits,
                            void* workspace, int64_t workspace_bytes, void* stream, int kv_dtype, float k_scale,
-                           float v_scale, bool tree = false, const uint64_t* q_mask = nullptr) {
+                           float v_scale, bool tree = false, const uint64_t* q_mask = nullptr,
+                           const int64_t* window = nullptr) {
     TGIS_CHECK_ARG(q && k_pool && v_pool && block_tables && ctx_lens && cu_seqlens_q && out,
                    "tgis_attn_paged: null tensor");
     TGIS_CHECK_ARG(!tree || q_mask, "tgis_attn_paged_tree: null q_mask");
+    TGIS_CHECK_ARG(!window || *window >= 1, "tgis_attn_paged_window: window %ld must be at least 1", (long)(window ? *window : 0));
     TGIS_CHECK_ARG(dtype == TGIS_F16 || dtype == TGIS_BF16, "tgis_attn_paged: bad dtype");
     TGIS_CHECK_KV_ARGS("tgis_attn_paged_kv8", kv_dtype, k_scale, v_scale);
     const bool kv8 = kv_dtype == TGIS_KV_FP8_E4M3;
     TGIS_CHECK_ARG(ld_q % 8 == 0 && ((uintptr_t)q % 16) == 0, "tgis_attn_paged: q must be 16-byte aligned");
     TGIS_CHECK_ARG(max_pages > 0, "tgis_attn_paged: bad launch bounds");
-    (void)max_ctx;
     const AttnHooks hooks = attn_hooks();  // read once per call
     AttnPlan plan;
-    if (const int rc = checked_plan(B, H, Hkv, D, max_q_len, num_splits, tree, hooks, &plan)) return rc;
+    if (const int rc = checked_plan(B, H, Hkv, D, max_q_len, num_splits, tree, hooks, &plan, window != nullptr)) return rc;
+    // a window that no row of the launch reaches is the causal launch (the refusals above hold for it all the same)
+    if (window && max_ctx <= *window) {
+        window = nullptr;
+        if (const int rc = checked_plan(B, H, Hkv, D, max_q_len, num_splits, tree, hooks, &plan)) return rc;
+    }
+    const int W = window ? (int)std::min<int64_t>(*window, 2147483647) : 0;  // (positions are 32-bit)
     TGIS_CHECK_ARG(ld_out == 0 || ld_out == (int64_t)H * D ||
                        (ld_out == TGIS_LD_FRAGMENTS && max_q_len == 1 && B <= 64 && ((int64_t)H * D) % 64 == 0),
                    "tgis_attn_paged: out is [tokens, H * D] contiguous (ld_out = 0 or H * D), or — decode, <= 64 sequences — in "
@@ -707,14 +789,14 @@ static int attn_paged_impl(const void* q, int64_t ld_q, const void* k_pool, cons
                                      (kv8 ? scale * k_scale : scale) * 1.4426950408889634f, kv8 ? 1.f / v_scale : 1.f, workspace,
                                      counters, q_mask);
     TgisTimedScope timed(TGIS_OP_ATTN, st);
-    if (plan.form == ATTN_PREFILL) return tgis_launch_attn_prefill(a, B, Hkv, D, max_q_len, dtype, kv8, st);
+    if (plan.form == ATTN_PREFILL) return tgis_launch_attn_prefill(a, B, Hkv, D, max_q_len, dtype, kv8, st, W);
     const int32_t* q_end = max_q_len > 1 ? cu_seqlens_q + B : nullptr;
     return by_dtype(dtype, [&](auto t) {
         using T = type_of<decltype(t)>;
         return by_kv<T>(kv8, [&](auto kv) {  // one-byte cache: the same launch shapes over e4m3 pools
             // D = 96: KS = 3, NB = 6 (gpt-neox-20b)
             return by_int<128, 96, 64>(D, "tgis_attn_paged: head_dim", [&](auto d) {
-                return launch_decode<T, type_of<decltype(kv)>, decltype(d)::value>(plan, a, total_q, q_end, st);
+                return launch_decode<T, type_of<decltype(kv)>, decltype(d)::value>(plan, a, W, total_q, q_end, st);
             });
         });
     });
@@ -763,4 +845,26 @@ extern "C" int tgis_attn_paged_tree_kv8(const void* q, int64_t ld_q, const void*
     return attn_paged_impl(q, ld_q, k_pool, v_pool, block_tables, max_pages, ctx_lens, cu_seqlens_q, out, ld_out, B, H, Hkv, D,
                            max_q_len, max_ctx, scale, dtype, num_splits, workspace, workspace_bytes, stream, kv_dtype,
                            k_scale, v_scale, true, q_mask);
+}
+
+// tgis_attn_paged / tgis_attn_paged_kv8 under a sliding window of `window` keys per q row (Mistral: config.sliding_window).
+extern "C" int tgis_attn_paged_window(const void* q, int64_t ld_q, const void* k_pool, const void* v_pool,
+                                      const int32_t* block_tables, int64_t max_pages, const int32_t* ctx_lens,
+                                      const int32_t* cu_seqlens_q, void* out, int64_t ld_out, int64_t B, int H, int Hkv, int D,
+                                      int64_t max_q_len, int64_t max_ctx, float scale, int dtype, int num_splits,
+                                      void* workspace, int64_t workspace_bytes, void* stream, int64_t window) {
+    return attn_paged_impl(q, ld_q, k_pool, v_pool, block_tables, max_pages, ctx_lens, cu_seqlens_q, out, ld_out, B, H, Hkv, D,
+                           max_q_len, max_ctx, scale, dtype, num_splits, workspace, workspace_bytes, stream, TGIS_KV_MODEL,
+                           1.f, 1.f, false, nullptr, &window);
+}
+
+extern "C" int tgis_attn_paged_window_kv8(const void* q, int64_t ld_q, const void* k_pool, const void* v_pool,
+                                          const int32_t* block_tables, int64_t max_pages, const int32_t* ctx_lens,
+                                          const int32_t* cu_seqlens_q, void* out, int64_t ld_out, int64_t B, int H, int Hkv,
+                                          int D, int64_t max_q_len, int64_t max_ctx, float scale, int dtype, int num_splits,
+                                          void* workspace, int64_t workspace_bytes, void* stream, int kv_dtype, float k_scale,
+                                          float v_scale, int64_t window) {
+    return attn_paged_impl(q, ld_q, k_pool, v_pool, block_tables, max_pages, ctx_lens, cu_seqlens_q, out, ld_out, B, H, Hkv, D,
+                           max_q_len, max_ctx, scale, dtype, num_splits, workspace, workspace_bytes, stream, kv_dtype,
+                           k_scale, v_scale, false, nullptr, &window);
 }

@@ -30,9 +30,15 @@ struct AttnTreeArgs : AttnArgs {
     const uint64_t* q_mask;  // [total_q]: bit j of word i = q row i of a sequence attends to that sequence's q row j
 };
 
+// tgis_attn_paged_window: the argument block of the WINDOW variants of the decode and the prefill kernel, a type of its own for
+// the same reason.
+struct AttnWindowArgs : AttnArgs {
+    int window;  // W >= 1: the q row at cache position p attends to the positions p - W < j <= p
+};
+
 constexpr float NEG_BIG = -1.0e30f;
 
 // prefill kernel launcher (attention_prefill.hip); `a` carries the geometry filled in by tgis_attn_paged
-// (kv8: the pools hold e4m3 codes, kv_layout.h)
+// (kv8: the pools hold e4m3 codes, kv_layout.h; window: 0 = causal, else the WINDOW variant with that many keys per row)
 int tgis_launch_attn_prefill(const AttnArgs& a, int64_t B, int Hkv, int D, int64_t max_q_len, int dtype, bool kv8,
-                             hipStream_t st);
+                             hipStream_t st, int window = 0);

@@ -161,12 +161,20 @@ static inline int64_t attn_workspace_bytes(int64_t total_q_tokens, int H, int Hk
     return std::max(two_pass, fused);
 }
 
-enum AttnForm { ATTN_PREFILL = 0, ATTN_DECODE = 1, ATTN_TREE = 2 };
+enum AttnForm { ATTN_PREFILL = 0, ATTN_DECODE = 1, ATTN_TREE = 2, ATTN_WINDOW = 3 };
+
+// Sliding-window attention (tgis_attn_paged_window): the q row at cache position p attends to the W positions p - W < j <= p.
+// Row t of a sequence's q_len rows sits at p = ctx - q_len + t, so this is the first position it sees; the first page a block
+// loads is that of its first row, >> 5.  (constexpr: the kernels call it too.)
+constexpr int attn_window_first_key(int ctx, int q_len, int t, int window) {
+    return ctx - q_len + t + 1 > window ? ctx - q_len + t + 1 - window : 0;
+}
 
 constexpr int64_t ATTN_FUSED_MAX_GROUPS = 1 << 20;  // the in-launch merge counts arrivals per group (attention_counters.h)
 
 struct AttnPlan {
-    AttnForm form;    // prefill: attention_prefill.hip; decode / tree: attn_paged_kernel<.., nw, ch, pipe, tree>
+    AttnForm form;    // prefill: attention_prefill.hip; decode / tree / window: attn_paged_kernel<.., nw, ch, pipe, tree, window>
+    bool window;      // the WINDOW variant of the form's kernel (form window at one q token per sequence, else form prefill)
     AttnGeom geom;
     int ch, HCB, nw;  // 16-head chunks per block; blocks per kv head along the chunks; waves per block
     bool pipe, xcd_remap;  // two pages in flight per wave; the chunk blocks of a (sequence, split, kv head) group on one XCD
@@ -178,12 +186,16 @@ struct AttnPlan {
 };
 
 // The one chooser.  The arguments are valid (H % Hkv == 0, sizes >= 1) and the prefill form comes unsplit and without a tree.
+// window: a windowed call (never a tree) takes the restricted plan of the tree variant at one q token per sequence and the
+// prefill form at any other q length, whatever max_q_len * Gp is and whatever TGIS_ATTN_NO_PREFILL_KERNEL says.
 static inline AttnPlan plan_attn(int64_t B, int H, int Hkv, int D, int64_t max_q_len, int num_splits, bool tree,
-                                 const AttnHooks& hooks) {
+                                 const AttnHooks& hooks, bool window = false) {
     AttnPlan p = {};
     const AttnGeom g = p.geom = geom(H, Hkv);
     const bool prefill_form = max_q_len * g.Gp > 64;
     p.form = tree ? ATTN_TREE : (prefill_form && !hooks.no_prefill_kernel) ? ATTN_PREFILL : ATTN_DECODE;
+    if (window) p.form = max_q_len > 1 ? ATTN_PREFILL : ATTN_WINDOW, p.window = true;
+    tree = tree || window;  // from here on: the restricted plan, which follows no hook but FUSED_COMBINE
     p.maxs8 = num_splits <= 8;
     if (p.form == ATTN_PREFILL) {
         // long q (prefill): blocks of 128 columns that stage each K/V page once in LDS (attention_prefill.hip)
@@ -193,8 +205,8 @@ static inline AttnPlan plan_attn(int64_t B, int H, int Hkv, int D, int64_t max_q
         p.groups = p.grid[0] * p.grid[1] * p.grid[2];
         return p;
     }
-    // the tree variant: one-chunk blocks of 4 waves at any q_len — what the causal launch takes by default at q_len > 1.  It
-    // follows none of the NW, CH, PIPE and XCD hooks: a measurement that sets one of them compares the causal launch in
+    // the tree variant (and the window variant): one-chunk blocks of 4 waves at any q_len — what the causal launch takes by
+    // default at q_len > 1.  It follows none of the NW, CH, PIPE and XCD hooks: a measurement that sets one of them compares the causal launch in
     // another configuration with this one as it always is.
     p.ch = tree ? 1 : chunks_per_block(g.HC, max_q_len, hooks);
     p.HCB = (g.HC + p.ch - 1) / p.ch;

@@ -16,14 +16,18 @@
 #include "common.h"
 #include "dispatch.h"
 #include "attention_args.h"
+#include "attention_plan.h"
 #include "kv_layout.h"
 
 namespace {
 
 // KV: the pool's element, T or uint8_t (e4m3 codes, kv_layout.h): a one-byte page is widened to T in the staging registers, so
 // the LDS images and everything behind them are those of the 16-bit cache
-template <typename T, typename KV, int D>
-__global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs a) {
+// WINDOW (tgis_attn_paged_window at more than one q token per sequence): a q row sees the a.window keys up to its own.  The
+// block's page loop starts at the first page its first q row sees, the masked form of the softmax tests the lower bound as
+// well, and a page takes the mask-free form when it lies inside both bounds of every column of the wave.
+template <typename T, typename KV, int D, bool WINDOW = false>
+__global__ __launch_bounds__(256, 2) void attn_prefill_kernel(std::conditional_t<WINDOW, AttnWindowArgs, AttnArgs> a) {
     using V8 = typename VecT<T>::x8;
     constexpr int KS = D / 32;  // k-steps of the QK^T MFMA
     constexpr int NB = D / 16;  // 16-row blocks of O^T
@@ -44,7 +48,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs a) {
     const int ctx = a.ctx_lens[b];
     const int g = col & (a.Gp - 1);
     const int head = hk * a.G + hc * 16 + g;
-    int tq[CG], kmax[CG];
+    int tq[CG], kmax[CG], kmin[CG];  // (kmin: WINDOW only)
     bool col_valid[CG];
     int wave_kmax = 0, wave_kmin = 0x7fffffff;
 #pragma unroll
@@ -52,6 +56,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs a) {
         tq[cg] = ((w * CG + cg) * 16 + col) >> a.Gp_shift;
         col_valid[cg] = (g < a.Gc) && (hc * 16 + g < a.G) && (t0 + tq[cg] < q_len);
         kmax[cg] = col_valid[cg] ? (ctx - q_len + t0 + tq[cg] + 1) : 0;  // this column attends to positions < kmax
+        if constexpr (WINDOW) kmin[cg] = attn_window_first_key(ctx, q_len, t0 + tq[cg], a.window);  // ... and >= kmin
         wave_kmax = max(wave_kmax, kmax[cg]);
         if (col_valid[cg]) wave_kmin = min(wave_kmin, kmax[cg]);  // invalid columns (q = 0, never stored) need no mask
     }
@@ -63,6 +68,14 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs a) {
     }
     const int kend = ctx - q_len + min(q_len, t0 + TQB);  // keys needed by any column of the block
     const int pages = (kend + 31) >> 5;
+    // WINDOW: the first page any row of the block sees (its first row's); the wave's columns all see the keys in
+    // [wave_lo_full, wave_kmin) and none below wave_lo_any.  Without a window all three are 0.
+    int p0 = 0, wave_lo_full = 0, wave_lo_any = 0;
+    if constexpr (WINDOW) {
+        p0 = attn_window_first_key(ctx, q_len, t0, a.window) >> 5;
+        wave_lo_full = max(wave_kmax - a.window, 0);
+        wave_lo_any = wave_kmin == 0x7fffffff ? 0 : max(wave_kmin - a.window, 0);
+    }
 
     // Q^T fragments (B operand): lane supplies Q[col][ks*32 + c*8 .. +8]
     V8 qf[CG][KS];
@@ -122,14 +135,14 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs a) {
         }
     };
 
-    page_load(0);
-    page_store(0);
+    page_load(p0);
+    page_store(p0 & 1);
     __syncthreads();
 
-    for (int p = 0; p < pages; ++p) {
+    for (int p = p0; p < pages; ++p) {
         const bool more = p + 1 < pages;
         if (more) page_load(p + 1);
-        if (p * 32 < wave_kmax) {
+        if (p * 32 < wave_kmax && (!WINDOW || p * 32 + 32 > wave_lo_any)) {
             const T* kl = lds + (p & 1) * 2 * PAGE_ELEMS + lane * 8;
             const T* vl = kl + PAGE_ELEMS;
             const int kp0 = p * 32 + c * 4;
@@ -160,7 +173,11 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs a) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             float v = s[cg][t][r] * a.scale_log2;
-                            if (MASKED) v = (kp0 + t * 16 + r < kmax[cg]) ? v : NEG_BIG;
+                            if (MASKED) {
+                                bool vis = kp0 + t * 16 + r < kmax[cg];
+                                if constexpr (WINDOW) vis = vis && kp0 + t * 16 + r >= kmin[cg];
+                                v = vis ? v : NEG_BIG;
+                            }
                             s[cg][t][r] = v;
                             tmax = fmaxf(tmax, v);
                         }
@@ -184,7 +201,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs a) {
                     lsum[cg] = lsum[cg] * alpha[cg] + psum;
                 }
             };
-            if ((p + 1) * 32 <= wave_kmin)
+            if ((p + 1) * 32 <= wave_kmin && (!WINDOW || p * 32 >= wave_lo_full))
                 softmax_page(std::false_type{});
             else
                 softmax_page(std::true_type{});
@@ -237,7 +254,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs a) {
 }  // namespace
 
 int tgis_launch_attn_prefill(const AttnArgs& a, int64_t B, int Hkv, int D, int64_t max_q_len, int dtype, bool kv8,
-                             hipStream_t st) {
+                             hipStream_t st, int window) {
     const int TQB = a.TQ * 8;
     const int64_t q_tiles = cdiv64(max_q_len, TQB);
     TGIS_CHECK_ARG(q_tiles <= 2147483647LL && (int64_t)Hkv * a.HC <= 65535 && B <= 65535, "tgis_attn_paged: grid too large");
@@ -248,8 +265,16 @@ int tgis_launch_attn_prefill(const AttnArgs& a, int64_t B, int Hkv, int D, int64
         return by_kv<T>(kv8, [&](auto kv) {
             // every head size by name: a size the caller lets through without a kernel here is an error, not the 64 path
             return by_int<128, 96, 64>(D, "tgis_attn_paged: prefill head_dim", [&](auto d) {
-                hipLaunchKernelGGL((attn_prefill_kernel<T, type_of<decltype(kv)>, decltype(d)::value>), grid, dim3(256), lds,
-                                   st, a);
+                if (window > 0) {
+                    AttnWindowArgs wa;
+                    static_cast<AttnArgs&>(wa) = a;
+                    wa.window = window;
+                    hipLaunchKernelGGL((attn_prefill_kernel<T, type_of<decltype(kv)>, decltype(d)::value, true>), grid,
+                                       dim3(256), lds, st, wa);
+                } else {
+                    hipLaunchKernelGGL((attn_prefill_kernel<T, type_of<decltype(kv)>, decltype(d)::value>), grid, dim3(256),
+                                       lds, st, a);
+                }
                 TGIS_CHECK_LAUNCH();
                 return TGIS_OK;
             });

@@ -1,6 +1,7 @@
 """The native engine: model type -> MI355X model class, process group, safetensors `Weights`, GPTQ params
 (mirrors inference_engine/tgis_native.py:23-139 of the reference; model families of the configs in
-BASELINE.json: llama, and gpt_bigcode when flash_santacoder_modeling is present; gpt_neox)."""
+BASELINE.json: llama, and gpt_bigcode when flash_santacoder_modeling is present; gpt_neox; mistral, whose tensors carry
+Llama's names and whose sliding window FlashCausalLM reads from the config)."""
 import os
 from typing import Any, Optional
 
@@ -12,7 +13,7 @@ from tgis_amd.utils.dist import initialize_torch_distributed
 from tgis_amd.utils.hub import local_weight_files
 from tgis_amd.utils.weights import Weights
 
-FLASH_TYPES = ["llama", "gpt_bigcode", "gpt_neox"]
+FLASH_TYPES = ["llama", "gpt_bigcode", "gpt_neox", "mistral"]
 
 
 def _barrier(group):
@@ -25,7 +26,7 @@ def _barrier(group):
 def model_class_for(config):
     model_type = config.model_type
     aliases = None
-    if model_type == "llama":
+    if model_type in ("llama", "mistral"):
         if getattr(config, "tie_word_embeddings", False):
             aliases = {"lm_head.weight": ["model.embed_tokens.weight"]}
         from tgis_amd.models.custom_modeling.flash_llama_modeling import FlashLlamaForCausalLM

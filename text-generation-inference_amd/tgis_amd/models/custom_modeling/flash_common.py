@@ -28,6 +28,9 @@ class KVArgs:
     #                                    front of this prefill's: page-wise cache writes starting behind them
     q_mask: Optional[torch.Tensor] = None  # [T] int64, one 64-bit word per q row: which of its sequence's q rows the row
     #                                    attends to (a tree verify step; native.attn_paged's q_mask).  None: causal
+    window: Optional[int] = None       # sliding-window attention (Mistral's config.sliding_window): a q row attends to this
+    #                                    many cache positions up to its own (native.attn_paged's window).  None: causal.
+    #                                    `num_splits` is then the count for min(max_ctx, window + 31) keys (decode) or 1
 
 
 def layer_pools(kv: KVArgs, layer_id: int):
@@ -70,6 +73,8 @@ def attend(qkv, kv: KVArgs, layer_id: int, H: int, Hkv: int, D: int, scale: floa
         ws.ensure(native.attn_workspace_bytes(rows, H, Hkv, D, kv.num_splits))
     if kv.q_mask is not None:
         scales = dict(scales, q_mask=kv.q_mask)
+    if kv.window is not None and kv.max_ctx > kv.window:  # (a window no row reaches: the causal call, as for every other model)
+        scales = dict(scales, window=kv.window)
     native.attn_paged(qkv, qkv.stride(0), k_pool, v_pool, kv.block_tables, kv.ctx_lens, cu_seqlens_q, attn_output,
                       kv.block_tables.shape[0], H, Hkv, D, kv.max_q_len, kv.max_ctx, scale, kv.num_splits, ws, **scales)
     return attn_output

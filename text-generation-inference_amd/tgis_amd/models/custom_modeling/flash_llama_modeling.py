@@ -106,7 +106,8 @@ class FlashLlamaAttention:
     def __init__(self, prefix: str, config, weights):
         self.num_heads = config.num_attention_heads
         self.hidden_size = config.hidden_size
-        self.head_size = self.hidden_size // self.num_heads
+        # (Mistral-Nemo: hidden 5120, 32 heads of `head_dim` 128; q_proj / o_proj are then [H head_dim, E] / [E, H head_dim])
+        self.head_size = getattr(config, "head_dim", None) or self.hidden_size // self.num_heads
         theta, scaling = rope_settings(config)
         self.rotary_emb = PositionRotaryEmbedding.static(dim=self.head_size, base=theta,
                                                          device=weights.device, scaling_factor=scaling)
@@ -118,11 +119,11 @@ class FlashLlamaAttention:
         assert config.num_key_value_heads % tp == 0, "num_key_value_heads must be divisible by the shard count"
         self.num_heads = self.num_heads // tp
         self.num_key_value_heads = config.num_key_value_heads // tp
+        attention_bias = getattr(config, "attention_bias", False)  # (a Mistral config carries neither bias field)
         self.query_key_value = TensorParallelColumnLinear.load_multi(
             config, prefixes=[f"{prefix}.q_proj", f"{prefix}.k_proj", f"{prefix}.v_proj"], dim=0, weights=weights,
-            bias=config.attention_bias)
-        self.o_proj = TensorParallelRowLinear.load(config, prefix=f"{prefix}.o_proj", weights=weights,
-                                                   bias=config.attention_bias)
+            bias=attention_bias)
+        self.o_proj = TensorParallelRowLinear.load(config, prefix=f"{prefix}.o_proj", weights=weights, bias=attention_bias)
         # where the linear has that launch, decode steps of up to 64 rows rotate q / k and write the cache in the GEMM epilogue
         self.query_key_value.declare_rope_heads(self.num_heads, self.num_key_value_heads, self.head_size)
 
@@ -159,11 +160,10 @@ class LlamaMLP:
     def __init__(self, prefix, config, weights):
         if config.hidden_act != "silu":
             raise NotImplementedError(f"hidden_act {config.hidden_act}: only silu is wired into the fused kernel")
+        mlp_bias = getattr(config, "mlp_bias", False)
         self.gate_up_proj = TensorParallelColumnLinear.load_multi(
-            config, prefixes=[f"{prefix}.gate_proj", f"{prefix}.up_proj"], weights=weights, dim=0,
-            bias=config.mlp_bias)
-        self.down_proj = TensorParallelRowLinear.load(config, prefix=f"{prefix}.down_proj", weights=weights,
-                                                      bias=config.mlp_bias)
+            config, prefixes=[f"{prefix}.gate_proj", f"{prefix}.up_proj"], weights=weights, dim=0, bias=mlp_bias)
+        self.down_proj = TensorParallelRowLinear.load(config, prefix=f"{prefix}.down_proj", weights=weights, bias=mlp_bias)
         self.intermediate_size = config.intermediate_size // weights.process_group.size()
         # GPTQ: SiLU(gate)*up runs in the gate_up GEMM epilogue (columns interleaved at prepare time);
         # dense: it runs while down_proj stages its operand.  Reference: eager ops at :332-335.

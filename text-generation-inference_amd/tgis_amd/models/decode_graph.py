@@ -114,7 +114,12 @@ class _DecodeGraph:
         dev = lm.device
         self.ctx = torch.ones(B, dtype=torch.int32, device=dev)
         self.cu_q = torch.arange(B + 1, dtype=torch.int32, device=dev)
-        self.num_splits = native.attn_num_splits(B, lm.num_kv_heads, lm.num_heads, 1, self.max_ctx)
+        # sliding-window attention: a graph whose table cannot hold more than W keys is the causal graph; a wider one makes
+        # the windowed launch, its key splits sized for the keys a step can see (W of them over at most W + 31 slots of pages)
+        W = getattr(lm, "sliding_window", None)
+        self.window = W if W is not None and self.max_ctx > W else None
+        keys = self.max_ctx if self.window is None else min(self.max_ctx, self.window + PAGE - 1)
+        self.num_splits = native.attn_num_splits(B, lm.num_kv_heads, lm.num_heads, 1, keys)
         # a speculating model's plain steps report through tgis_spec_accept (K = 0) too: the next lookup's hits ride along
         self.spec_out = _SpecOut(B, 0, dev) if lm.spec_tokens else None
 
@@ -169,7 +174,7 @@ class _DecodeGraph:
         lm = self.lm
         native.decode_slots(self.positions, self.block_tables, self.slots, self.ctx)
         kv = KVArgs(cache=lm.kv_cache, block_tables=self.block_tables, ctx_lens=self.ctx, slots=self.slots,
-                    max_q_len=1, max_ctx=self.max_ctx, num_splits=self.num_splits)
+                    max_q_len=1, max_ctx=self.max_ctx, num_splits=self.num_splits, window=self.window)
         logits = self._forward(self.input_ids, self.positions, kv)
         ids, lps = native.argmax_logprob(logits, ids_out=self.ids_buf, logprob_out=self.lps_buf, scratch=self.argmax_scratch)
         return logits, ids, lps

@@ -37,6 +37,7 @@ from tgis_amd.utils.kv_cache import (KV_SCALES_HEADROOM, PAGE, OutOfPages, Paged
                                      agree_kv_prefix_reuse, agree_kv_scales, kv_pool_dtype, kv_scales_stats,
                                      pages_for_budget, parse_kv_cache_dtype, parse_kv_prefix_reuse)
 from tgis_amd.utils.rank_group import RankGroup
+from tgis_amd.utils.sliding_window import check_window_options, parse_sliding_window
 from tgis_amd.utils.spec_decode import (check_spec_candidates, check_spec_world, check_tree_rows, fallback_cause,
                                         may_ever_verify, new_stats, parse_spec_candidates, parse_spec_ngram,
                                         parse_spec_sampling, parse_spec_tokens)
@@ -446,6 +447,8 @@ class FlashCausalLM(Model):
     spec_sampling = False
     # draft chains a greedy request brings to a verify step (set by the constructor); 1 = the single chain
     spec_candidates = 1
+    # sliding-window attention: W keys per q row (config.sliding_window, Mistral), None = causal (set by the constructor)
+    sliding_window = None
 
     def __init__(self, model_name: str, revision: Optional[str], deployment_framework: str, dtype: torch.dtype,
                  quantize: Optional[str], model_config: Union[Any] = None, auto_model_class=None,
@@ -530,6 +533,10 @@ class FlashCausalLM(Model):
             self.drafter = LookupDrafter(self.spec_tokens, self.spec_ngram, self.spec_candidates)
         self.kv_cache_dtype = agree_kv_cache_dtype(self.ranks, kv_cache_dtype)
         self.kv_prefix_reuse = agree_kv_prefix_reuse(self.ranks, kv_prefix_reuse)
+        # config.sliding_window (None / 0 = off): the fresh prefill and the decode graphs attend under it
+        # (utils/sliding_window.py); the options whose launches do not are refused before any page is allocated
+        self.sliding_window = parse_sliding_window(self.config)
+        check_window_options(self.sliding_window, self.config, self.spec_tokens, self.kv_prefix_reuse)
         if kv_cache_pages is None:
             kv_cache_pages = self._default_kv_pages()
         # Tensor parallel: every rank must hold the SAME number of pages.  Each rank sizes its pool from its own free
@@ -582,6 +589,7 @@ class FlashCausalLM(Model):
         runs it on the same batches; the heads of all ranks are reduced, every rank returns the same dict."""
         if self.kv_cache.is_fp8:
             raise ValueError("calibrate_kv_scales measures the 16-bit cache: build the model with kv_cache_dtype='auto'")
+        check_window_options(self.sliding_window, self.config, calibrate_kv_scales=True)
         L, Hkv, D = self.num_layers, self.num_kv_heads, self.head_size
         stats = torch.zeros((L, 2, Hkv), dtype=torch.float32, device=self.device)
         tokens = 0
@@ -721,7 +729,8 @@ class FlashCausalLM(Model):
         kv = KVArgs(cache=self.kv_cache, block_tables=batch.block_tables,
                     ctx_lens=torch.tensor(lens, dtype=torch.int32, device=dev),
                     slots=torch.from_numpy(slots).to(dev, non_blocking=True),
-                    max_q_len=max(lens), max_ctx=max(lens), num_splits=1, fresh_prefill=FRESH_PREFILL_KV)
+                    max_q_len=max(lens), max_ctx=max(lens), num_splits=1, fresh_prefill=FRESH_PREFILL_KV,
+                    window=self.sliding_window)
         lm_head_indices = None if self._need_all_logits else (batch.cu_seqlens[1:] - 1).long()
         return self._forward_prefill(batch.input_ids, batch.position_ids.to(torch.int32), batch.cu_seqlens,
                                      batch.max_seqlen, batch.inputs_embeds, kv, lm_head_indices)

@@ -109,6 +109,11 @@ SIGNATURES = {
                                       _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_int, _vp, _c_i64, _vp, _vp]),
     "tgis_attn_paged_tree_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int,
                                           _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_int, _vp, _c_i64, _vp] + _KV8_ARGS + [_vp]),
+    "tgis_attn_paged_window": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int,
+                                        _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_int, _vp, _c_i64, _vp, _c_i64]),
+    "tgis_attn_paged_window_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int,
+                                            _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_int, _vp, _c_i64, _vp] + _KV8_ARGS
+                                   + [_c_i64]),
     "tgis_kv_absmax": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _c_int, _vp, _vp]),
     "tgis_act_mul": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _c_int, _vp]),
     "tgis_gelu": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_int, _vp]),
@@ -802,13 +807,15 @@ def attn_workspace_bytes(total_q: int, H: int, Hkv: int, D: int, num_splits: int
 
 def attn_paged(q, ld_q: int, k_pool, v_pool, block_tables, ctx_lens, cu_seqlens_q, out, B: int, H: int, Hkv: int,
                D: int, max_q_len: int, max_ctx: int, scale: float, num_splits: int, ws: Optional[Workspace],
-               kv_scales=(1.0, 1.0), q_mask=None, tree: Optional[bool] = None):
+               kv_scales=(1.0, 1.0), q_mask=None, tree: Optional[bool] = None, window: Optional[int] = None):
     """q is a (view into a) [T, *] activation whose row stride is ld_q elements; out [T, H*D], or (decode, B <= 64) a
     FragAct of that shape for the o_proj GEMM.  One-byte pools (kv_is8) are read as k_scale * e4m3(k), v_scale * e4m3(v)
     (tgis_attn_paged_kv8), kv_scales = (k_scale, v_scale).
     q_mask (int64 [T], read as 64-bit words): tgis_attn_paged_tree — bit j of word i lets q row i of a sequence attend to that
     sequence's q row j, under the causal bound; the decode form only.  (tree=True with q_mask None asks the tree entry point
-    with a null mask, which it refuses.)"""
+    with a null mask, which it refuses.)
+    window (an int, not with q_mask / tree): tgis_attn_paged_window — a q row attends to the `window` cache positions up to
+    its own; at max_q_len 1 the caller sizes num_splits for min(max_ctx, window + 31) keys, at any other it passes 1."""
     assert block_tables.dtype == torch.int32 and ctx_lens.dtype == torch.int32 and cu_seqlens_q.dtype == torch.int32
     if q_mask is not None:
         assert q_mask.dtype == torch.int64 and q_mask.is_contiguous() and q_mask.numel() >= q.shape[0]
@@ -823,7 +830,10 @@ def attn_paged(q, ld_q: int, k_pool, v_pool, block_tables, ctx_lens, cu_seqlens_
     args = (_ptr(q), ld_q, _ptr(k_pool), _ptr(v_pool), _ptr(block_tables), block_tables.shape[1], _ptr(ctx_lens),
             _ptr(cu_seqlens_q), optr, ldo, B, H, Hkv, D, max_q_len, max_ctx, float(scale), dtype_code(q.dtype), num_splits,
             wptr, wbytes, _stream())
-    if not (q_mask is not None if tree is None else tree):
+    if window is not None:
+        assert q_mask is None and not tree, "a windowed launch takes no q_mask"
+        _call_kv("tgis_attn_paged_window", args, k_pool, v_pool, kv_scales, tail=(int(window),))
+    elif not (q_mask is not None if tree is None else tree):
         _call_kv("tgis_attn_paged", args, k_pool, v_pool, kv_scales)
     else:
         _call_kv("tgis_attn_paged_tree", args, k_pool, v_pool, kv_scales, tail=(_ptr(q_mask),))
