@@ -15,7 +15,8 @@ import torch
 class TinyMistralConfig:
     model_type = "mistral"
 
-    def __init__(self, sliding_window: Optional[int] = 40, head_dim: Optional[int] = None):
+    def __init__(self, sliding_window: Optional[int] = 40, head_dim: Optional[int] = None,
+                 max_position_embeddings: int = 512):
         self.vocab_size = 256
         self.hidden_size = 256
         self.intermediate_size = 512
@@ -24,7 +25,7 @@ class TinyMistralConfig:
         self.num_key_value_heads = 2
         self.rms_norm_eps = 1e-5
         self.rope_theta = 10000.0
-        self.max_position_embeddings = 512
+        self.max_position_embeddings = max_position_embeddings
         self.hidden_act = "silu"
         self.sliding_window = sliding_window
         if head_dim is not None:

@@ -1,6 +1,7 @@
 """CPU: the launch plan of sliding-window attention (csrc/attention_plan.h plan_attn with a window, reported by
 tgis_debug_attn_plan_window): the form, the grid and, per (ctx, q_len, W), the first visible page and key against the
-restatement tests/attn_window_ref.py over the grid of tests/test_attn_window_gpu.py; its refusals; and that
+restatement tests/attn_window_ref.py over the grid of tests/test_attn_window_gpu.py and, for the decode form, the windows of
+tests/test_attn_window_wide_gpu.py; its refusals; and that
 tgis_debug_attn_plan still answers what the commit before the window did (tests/golden/attn_plan_parent.npz: its info[16] at
 every point tests/test_attn_plan_cpu.py asks, recorded from that commit's library)."""
 import os
@@ -20,6 +21,7 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "att
 
 # the grid of the GPU file, restated (importing it would import torch and the GPU fixtures)
 WINDOWS = (1, 32, 40, 64, 95)
+WIDE_WINDOWS = (129, 300, 1000, 1024, 4096)  # tests/test_attn_window_wide_gpu.py's (its own grid: test_attn_window_wide_cpu.py)
 GEOMS = ((4, 4), (8, 2), (8, 1), (20, 1))
 
 
@@ -43,7 +45,7 @@ def test_decode_form_plan_and_visible_range(lib):
     for H, Hkv in GEOMS:
         Gp, TQ, HC = _geom(H, Hkv)
         for D in (64, 96, 128):
-            for W in WINDOWS:
+            for W in WINDOWS + WIDE_WINDOWS:
                 seqs = [(1, c) for c in window_ctxs(W)]
                 for ns in (1, 2, 5):
                     got = query_window_plan(lib, 3, H, Hkv, D, 1, ns, W, seqs)

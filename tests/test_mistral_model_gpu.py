@@ -2,7 +2,11 @@
 fp32 CPU MistralForCausalLM (tests/golden/mistral_window.npz, made by tests/golden/make_mistral_fixtures.py on the seeded tiny
 checkpoint of tests/mistral_tiny.py): prompts of 7, 45 and 100 tokens in one batch, 50 greedy tokens each, so the prefill runs
 the windowed prefill form, every decode step the windowed decode form, and the short request crosses the window and a page
-edge while it decodes."""
+edge while it decodes.
+
+test_mistral_at_a_window_of_1000_keys runs the same checkpoint at a window of 31 pages (prompts of 7, 990 and 1100 tokens):
+there the waves of the windowed decode form walk several pages each, its key splits are live in the captured graphs and the
+prefill takes most pages mask-free; the reference is the windowed fp32 oracle of test_mistral_over_the_e4m3_cache."""
 import json
 import os
 import sys
@@ -29,12 +33,13 @@ def _fixture():
     return json.loads(bytes(z["meta"]).decode()), z["ids"], z["logits"]
 
 
-def _build(meta, sliding_window=40, model_type="mistral", use_graphs=True, **kw):
+def _build(meta, sliding_window=40, model_type="mistral", use_graphs=True, max_position_embeddings=512, kv_cache_pages=64,
+           **kw):
     from tgis_amd.inference_engine.synthetic import InferenceEngine
     from tgis_amd.models.custom_modeling.flash_llama_modeling import LlamaConfig
     from tgis_amd.models.flash_causal_lm import FlashCausalLM
 
-    cfg = TinyMistralConfig(sliding_window=sliding_window)
+    cfg = TinyMistralConfig(sliding_window=sliding_window, max_position_embeddings=max_position_embeddings)
     if model_type == "mistral":  # what a Mistral config.json carries: no bias fields
         config = types.SimpleNamespace(model_type="mistral", **cfg.to_dict())
     else:
@@ -43,7 +48,7 @@ def _build(meta, sliding_window=40, model_type="mistral", use_graphs=True, **kw)
         config = LlamaConfig(**fields)
     tok = FixtureTokenizer(cfg.vocab_size)
     eng = InferenceEngine(tiny_mistral_tensors(cfg, meta["seed"]), config, torch.float16, None, tokenizer=tok)
-    lm = FlashCausalLM("fixture", None, "synthetic", torch.float16, None, engine=eng, kv_cache_pages=64, **kw)
+    lm = FlashCausalLM("fixture", None, "synthetic", torch.float16, None, engine=eng, kv_cache_pages=kv_cache_pages, **kw)
     lm.use_graphs = use_graphs
     return lm, tok
 
@@ -147,3 +152,70 @@ def test_mistral_over_the_e4m3_cache(gpu_device, monkeypatch):
         worst = max(worst, err)
         assert err <= KV_FP8_LOGIT_TOL, f"step {i}: max |logit - quantised-KV oracle| = {err:.3f} > {KV_FP8_LOGIT_TOL}"
     print(f"e4m3 cache: max |logit - quantised-KV oracle| over {len(got)} steps = {worst:.4f}")
+
+
+WIDE_WINDOW = 1000            # 31 pages and a bit: a step sees up to 33 pages, 8 or 9 per wave when the launch is not split
+WIDE_PROMPT_LENS = (7, 990, 1100)  # below the window; crossing it while it decodes; beyond it, so that the prefill is windowed
+WIDE_STEPS = 40
+WIDE_BUILD = dict(max_position_embeddings=2048, kv_cache_pages=128)  # 2 + 33 + 36 pages are in use at the last step
+
+
+def test_mistral_at_a_window_of_1000_keys(gpu_device, monkeypatch):
+    """sliding_window 1000: every captured decode graph is a windowed one with the key splits the rule gives its W + 31 keys
+    (more than one), graph and eager runs agree bit for bit, every logit is within the f16 bar of the windowed fp32 oracle fed
+    the model's own ids, every id is the oracle's argmax wherever the oracle's top-2 margin exceeds twice the bar, and the
+    same weights without a window leave the oracle at the 1100-token prompt's prefill.  The oracle is LlamaRef with its attention
+    replaced by tests/attn_window_ref.py at this W: test_mistral_over_the_e4m3_cache holds it to 1e-2 of the transformers
+    fixture at W 40, and the width is a parameter of the same restatement."""
+    import attn_window_ref
+    from oracle import ops_ref
+    from oracle.llama_ref import LlamaRef
+    from tgis_amd import native
+
+    seed = _fixture()[0]["seed"]
+    rng = np.random.default_rng(WIDE_WINDOW)
+    meta = {"seed": seed, "prompts": [rng.integers(3, 256, size=n).tolist() for n in WIDE_PROMPT_LENS], "max_new": WIDE_STEPS}
+    cfg = TinyMistralConfig(sliding_window=WIDE_WINDOW, max_position_embeddings=WIDE_BUILD["max_position_embeddings"])
+
+    runs = {}
+    for use_graphs in (True, False):
+        lm, tok = _build(meta, sliding_window=WIDE_WINDOW, use_graphs=use_graphs, **WIDE_BUILD)
+        assert lm.sliding_window == WIDE_WINDOW
+        runs[use_graphs] = _run(lm, tok, meta, WIDE_STEPS)
+        if use_graphs:
+            assert lm._graphs
+            for g in lm._graphs.values():
+                assert g.graph is not None and g.window == WIDE_WINDOW and g.max_ctx > WIDE_WINDOW
+                rule = native.attn_num_splits(g.rows, lm.num_kv_heads, lm.num_heads, 1, min(g.max_ctx, WIDE_WINDOW + 31))
+                assert g.num_splits == rule > 1, (g.rows, g.max_ctx, g.num_splits, rule)
+    for i, ((ig, lg), (ie, le)) in enumerate(zip(runs[True], runs[False])):
+        assert ig == ie and np.array_equal(lg, le), f"step {i}: graph and eager differ"
+
+    def windowed(q, k, v, cu_q, cu_k, scale):
+        assert list(cu_q) == [0, q.shape[0]] and list(cu_k) == [0, k.shape[0]]  # one sequence per call
+        return attn_window_ref.window_attention(q, k, v, WIDE_WINDOW, scale).float()
+
+    monkeypatch.setattr(ops_ref, "attention_varlen", windowed)
+    ref = LlamaRef(cfg, tiny_mistral_tensors(cfg, seed))
+    got = runs[True]
+    want = ref.generate_greedy(meta["prompts"], WIDE_STEPS, forced=[ids for ids, _ in got])
+    worst, decided = 0.0, 0
+    for i, ((got_ids, got_logits), w) in enumerate(zip(got, want)):
+        wl = w["logits"].numpy()
+        err = float(np.abs(got_logits - wl).max())
+        worst = max(worst, err)
+        top2 = np.sort(wl, axis=1)[:, -2:]
+        for r in range(len(got_ids)):
+            if top2[r, 1] - top2[r, 0] > 2 * LOGIT_TOL:
+                decided += 1
+                assert got_ids[r] == int(wl[r].argmax()), f"step {i} request {r}: id {got_ids[r]} != oracle {int(wl[r].argmax())}"
+        assert err <= LOGIT_TOL, f"step {i}: max |logit - windowed oracle| = {err:.3f} > {LOGIT_TOL}"
+    print(f"W {WIDE_WINDOW}: max |logit - windowed oracle| over {WIDE_STEPS} steps = {worst:.4f}; {decided} of "
+          f"{3 * WIDE_STEPS} ids decided by a margin above {2 * LOGIT_TOL}")
+    assert decided >= 2 * WIDE_STEPS  # (the head is scaled so that margins sit far above the bar: most ids are checked)
+
+    # the feature check at this width: without the window the 1100-token prompt's prefill is another model's
+    lm, tok = _build(meta, sliding_window=None, **WIDE_BUILD)
+    _ids, causal_logits = _run(lm, tok, meta, 1)[0]
+    err = np.abs(causal_logits - want[0]["logits"].numpy()).max(axis=1)
+    assert err[0] <= LOGIT_TOL and err[1] <= LOGIT_TOL and err[2] > LOGIT_TOL, err
