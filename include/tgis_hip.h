@@ -122,7 +122,12 @@ int tgis_gptq_fragments_ok(int64_t M, int64_t K, int64_t N, int64_t groups, int 
  * x row stride ldx, out row stride ldo (elements).  perm (int32 [K] or NULL) gathers x columns
  * for act-order matrices.  act: 0 = none; 1 = x is [M,2K] and the kernel consumes silu(x[:, :K]) * x[:, K:]
  * while staging it; 2 = the image was prepared with TGIS_GPTQ_GATE_UP and out is [M, N/2] =
- * silu(gate) * up applied in the epilogue (both fuse LlamaMLP's activation, flash_llama_modeling.py:332-335). */
+ * silu(gate) * up applied in the epilogue (both fuse LlamaMLP's activation, flash_llama_modeling.py:332-335).
+ * act 4 / 5 (M <= 256, row-major x and out, not a TGIS_GPTQ_GATE_UP image): out = f16(gelu(f16(x @ W + bias))), exact erf
+ * form / tanh approximation — the `self.act(...)` behind an int4 `c_fc` (flash_santacoder_modeling.py:284-306).  The plan is
+ * the one of act 0 and the activation is applied where that plan finishes the sum (the epilogue of an unsplit plan, the
+ * split-K reduce otherwise): bit-identical to tgis_gptq_gemm_f16(act 0) followed by tgis_gelu.
+ * tgis_gptq_gemm_fused_rows(act 4 | 5) is 256: above, the caller runs act 0 (or its library path) and tgis_gelu. */
 int tgis_gptq_gemm_f16(const void* x, int64_t ldx, const void* prepared, const void* bias,
                        const int32_t* perm, void* out, int64_t ldo, int64_t M, int64_t K, int64_t N,
                        int64_t groups, int act, void* workspace, int64_t workspace_bytes, void* stream);

@@ -378,6 +378,32 @@ __global__ __launch_bounds__(256) void splitk_reduce_silu_kernel(const float* __
     }
 }
 
+// The plain sum again, followed by out = f16(gelu(f16(sum + bias))): the act 4 / 5 finish of a projection whose plan splits
+// over k.  The sum is rounded to f16 exactly as splitk_reduce_f16_kernel rounds it and the activation reads that value, so
+// the result has the bits of that kernel followed by tgis_gelu.
+__global__ __launch_bounds__(256) void splitk_reduce_gelu_kernel(const float* __restrict__ slabs,
+                                                                 const f16* __restrict__ bias, f16* __restrict__ out,
+                                                                 int64_t ldo, int M, int N, int NP, int S, int tanh_approx) {
+    const int np4 = NP >> 2;
+    int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int mslab = blockIdx.y;
+    if (idx >= (int64_t)32 * np4) return;
+    const int m = idx / np4, c4 = (idx - (int64_t)m * np4) * 4;
+    if (mslab * 32 + m >= M) return;
+    f32x4 v = {0, 0, 0, 0};
+    const float* base = slabs + ((int64_t)mslab * S * 32 + m) * NP + c4;
+    for (int s2 = 0; s2 < S; ++s2) v += *reinterpret_cast<const f32x4*>(base + (int64_t)s2 * 32 * NP);
+    f16* o = out + (int64_t)(mslab * 32 + m) * ldo + c4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (c4 + e < N) {
+            float f = v[e];
+            if (bias) f += (float)bias[c4 + e];
+            o[e] = (f16)gelu_f32((float)(f16)f, tanh_approx != 0);
+        }
+    }
+}
+
 }  // namespace
 
 // every split-K sum of this file (declared in gptq_gemm_body.h)
@@ -482,7 +508,8 @@ static bool gptq_group64(int64_t K, int64_t groups) {
     return K % 64 == 0 && (groups == 1 || (gs % 64 == 0 && (spg & (spg - 1)) == 0));
 }
 static bool tall_ok(int64_t M, int64_t K, int64_t groups, const int32_t* perm, int act) {
-    return M >= tall_min_m() && perm == nullptr && act != 1 && gptq_group64(K, groups);
+    // (act 4 / 5, GELU: finished by the streaming passes and their reduce only, up to 256 rows)
+    return M >= tall_min_m() && perm == nullptr && act != 1 && act != 4 && act != 5 && gptq_group64(K, groups);
 }
 struct TallPlan {
     int BMR, S, KR, TW;
@@ -659,6 +686,11 @@ static int launch_wide_one(dim3 grid, hipStream_t st, const GemmArgs& a) {
     return a.M > 32 ? launch_wide_mr<CT, ACT, OUTF, 2>(grid, st, a) : launch_wide_mr<CT, ACT, OUTF, 1>(grid, st, a);
 }
 
+// Kernel template values of the GELU finish.  The public act 4 / 5 of tgis_gptq_gemm_f16 (the numbers tgis_dense_gemm uses)
+// map onto these: inside this file ACT 3 / 4 are the rope epilogues.  Only an unsplit plan runs them; a split one runs
+// ACT 0 and finishes in splitk_reduce_gelu_kernel.
+constexpr int ACT_GELU_ERF = 5, ACT_GELU_TANH = 6;
+
 static int launch_gptq(const void* x, int64_t ldx, const void* prepared, const void* bias, const int32_t* perm,
                        void* out, int64_t ldo, int64_t M, int64_t K, int64_t N, int64_t groups, int act, float* slabs,
                        int partial, const GemmPlan& pl, hipStream_t st, const RopeEpi* rope = nullptr) {
@@ -693,9 +725,9 @@ static int launch_gptq(const void* x, int64_t ldx, const void* prepared, const v
     const int rc = by_pair<pair_c<4, 4>, pair_c<4, 2>, pair_c<3, 4>, pair_c<3, 2>, pair_c<2, 4>, pair_c<2, 2>>(
         pl.TN, pl.WK, "tgis_gptq_gemm: plan (TN, WK)", [&](auto tw) {
         constexpr int TN = decltype(tw)::first, WK = decltype(tw)::second;
-        return by_int<0, 1, 2, 3, 4>(act, "tgis_gptq_gemm: act", [&](auto ac) {
+        return by_int<0, 1, 2, 3, 4, ACT_GELU_ERF, ACT_GELU_TANH>(act, "tgis_gptq_gemm: act", [&](auto ac) {
             constexpr int ACT = decltype(ac)::value;
-            if constexpr (ACT >= 3) {  // rope epilogues (4: into a one-byte e4m3 cache): 64 * 2^n groups, no act-order (caller)
+            if constexpr (ACT == 3 || ACT == 4) {  // rope epilogues (4: into a one-byte e4m3 cache): 64 * 2^n groups, no act-order (caller)
                 return launch_variant<TN, WK, ACT, true, false>(mr, grid, lds, st, a);
             } else {
                 return by_bool(group64, [&](auto g) {
@@ -767,6 +799,7 @@ static GptqLaunch choose_gptq(int entry, int64_t M, int64_t K, int64_t N, int64_
         c.tp = plan_tall(M, K, N, act);
         return c;
     }
+    if (act == 4 || act == 5) act = 0;  // GELU of the finished sum: the plain plan, the same summation order over k
     c.family = FAM_STREAM;
     c.pl = plan_gemm(K, N, entry == ENTRY_PARTIAL ? 0 : act, M);
     // SiLU * up whose unsplit plan has few blocks (TP shards): every block would take in its whole M x K activation
@@ -788,7 +821,15 @@ extern "C" int tgis_gptq_gemm_f16(const void* x, int64_t ldx, const void* prepar
                                   const int32_t* perm, void* out, int64_t ldo, int64_t M, int64_t K,
                                   int64_t N, int64_t groups, int act, void* workspace,
                                   int64_t workspace_bytes, void* stream) {
-    int rc = check_gemm_args(x, ldx, prepared, M, K, N, groups, act);
+    const int gelu = act == 4 ? 1 : act == 5 ? 2 : 0;  // GELU of the finished sum: epilogue (unsplit) or split-K reduce
+    if (gelu) {
+        TGIS_CHECK_ARG(ldx != TGIS_LD_FRAGMENTS && ldo != TGIS_LD_FRAGMENTS,
+                       "tgis_gptq_gemm_f16: act 4 / 5 (GELU) take a row-major activation and give a row-major output, not "
+                       "fragment order");
+        TGIS_CHECK_ARG(M <= 256, "tgis_gptq_gemm_f16: act 4 / 5 (GELU) serve up to 256 rows (M=%ld): above, act 0 and tgis_gelu",
+                       (long)M);
+    }
+    int rc = check_gemm_args(x, ldx, prepared, M, K, N, groups, gelu ? 0 : act);
     if (rc != TGIS_OK) return rc;
     TGIS_CHECK_ARG(out, "tgis_gptq_gemm_f16: null out");
     if (M == 0) return TGIS_OK;
@@ -822,6 +863,20 @@ extern "C" int tgis_gptq_gemm_f16(const void* x, int64_t ldx, const void* prepar
         dim3 rgrid((unsigned)cdiv64((int64_t)32 * (NP / 32) * 4, 256), (unsigned)cdiv64(M, 32));
         hipLaunchKernelGGL(splitk_reduce_silu_kernel, rgrid, dim3(256), 0, st, slabs, (const f16*)bias, (f16*)out, ldo, (int)M,
                            (int)N, NP, c.pl.S);
+        TGIS_CHECK_LAUNCH();
+        return TGIS_OK;
+    }
+    if (gelu) {
+        if (c.pl.S == 1)
+            return launch_gptq(x, ldx, prepared, bias, perm, out, ldo, M, K, N, groups,
+                               gelu == 2 ? ACT_GELU_TANH : ACT_GELU_ERF, slabs, 0, c.pl, st);
+        // split over k: the act 0 kernel leaves its slabs, and the activation follows their sum
+        rc = launch_gptq(x, ldx, prepared, nullptr, perm, out, ldo, M, K, N, groups, 0, slabs, 1, c.pl, st);
+        if (rc != TGIS_OK) return rc;
+        const int NP = (int)cdiv64(N, 32) * 32;
+        dim3 rgrid((unsigned)cdiv64((int64_t)32 * (NP / 4), 256), (unsigned)cdiv64(M, 32));
+        hipLaunchKernelGGL(splitk_reduce_gelu_kernel, rgrid, dim3(256), 0, st, slabs, (const f16*)bias, (f16*)out, ldo, (int)M,
+                           (int)N, NP, c.pl.S, gelu == 2);
         TGIS_CHECK_LAUNCH();
         return TGIS_OK;
     }
@@ -919,6 +974,8 @@ extern "C" int tgis_gptq_fragments_ok(int64_t M, int64_t K, int64_t N, int64_t g
 extern "C" int tgis_gptq_gemm_f16_partial(const void* x, int64_t ldx, const void* prepared, const int32_t* perm,
                                           int64_t M, int64_t K, int64_t N, int64_t groups, int act, float* slabs,
                                           int64_t slabs_bytes, int* num_slabs, int64_t* slab_ld, void* stream) {
+    TGIS_CHECK_ARG(act != 4 && act != 5,
+                   "tgis_gptq_gemm_f16_partial: act 4 / 5 (GELU) need the finished sum (use tgis_gptq_gemm_f16)");
     int rc = check_gemm_args(x, ldx, prepared, M, K, N, groups, act);
     if (rc != TGIS_OK) return rc;
     TGIS_CHECK_ARG(M >= 1 && cdiv64(M, 32) <= 65535, "tgis_gptq_gemm_f16_partial: bad M");
@@ -953,6 +1010,12 @@ extern "C" int tgis_debug_gemm_plan(int entry, int64_t M, int64_t K, int64_t N, 
     for (int i = 0; i < 16; ++i) info[i] = 0;
     if (entry >= 3) return dense::debug_plan(entry - 3, M, K, N, act, dtype, info);
     TGIS_CHECK_ARG(entry >= 0 && groups > 0 && K % groups == 0, "tgis_debug_gemm_plan: bad arguments");
+    if (act == 4 || act == 5) {  // GELU: tgis_gptq_gemm_f16 only, row-major, up to 256 rows; reported as the plain plan + info[14]
+        TGIS_CHECK_ARG(entry == ENTRY_GEMM && !frag_in && !frag_out && M <= 256,
+                       "tgis_debug_gemm_plan: act 4 / 5 (GELU) is a form of tgis_gptq_gemm_f16 with row-major operands and up to "
+                       "256 rows");
+        info[14] = act == 4 ? 1 : 2;
+    }
     const GptqLaunch c = choose_gptq(entry, M, K, N, groups, entry == ENTRY_ROPE ? 3 : act, act_order != 0, frag_in != 0);
     info[0] = c.family;
     const bool finished = entry == ENTRY_GEMM;
@@ -972,7 +1035,7 @@ extern "C" int tgis_debug_gemm_plan(int entry, int64_t M, int64_t K, int64_t N, 
         return TGIS_OK;
     }
     info[5] = gemm_row_class(c.pl);
-    info[8] = c.family == FAM_GPTQ_ROPE ? 3 : c.family == FAM_SPLIT_SILU ? 0 : act;
+    info[8] = c.family == FAM_GPTQ_ROPE ? 3 : (c.family == FAM_SPLIT_SILU || info[14]) ? 0 : act;
     info[9] = c.family == FAM_GPTQ_ROPE || gptq_group64(K, groups);
     info[10] = act_order != 0 && c.family != FAM_GPTQ_ROPE;
     info[12] = c.family == FAM_SPLIT_SILU ? 2 : (finished && c.pl.S > 1 && !getenv("TGIS_GPTQ_NOREDUCE"));

@@ -129,6 +129,7 @@ template <int TN, int WK, int ACT, bool GROUP64, bool PERM, int MR>
 __device__ __forceinline__ void gptq_gemm_unit(const GemmArgs& a, const int ntg, const int split, const int mslab,
                                                unsigned char* smem) {
     constexpr bool ROPE = ACT == 3 || ACT == 4;  // rope image epilogue; 4: k / v into a one-byte (e4m3) cache
+    constexpr bool GELU = ACT == 5 || ACT == 6;  // GELU of the rounded sum + bias (5: erf form, 6: tanh approximation); S == 1
     static_assert(MR == 1 || WK == 2, "64-row passes need the LDS of two k-parts");
     static_assert(WK > 1, "the finish below exchanges k-parts");
     static_assert(!ROPE || !PERM, "the rope epilogue is a decode form (<= 64 rows, no act-order)");
@@ -514,7 +515,15 @@ __device__ __forceinline__ void gptq_gemm_unit(const GemmArgs& a, const int ntg,
 #pragma unroll
                     for (int j = 0; j < NR; ++j) {
                         const int m = mr * 32 + row_of(j);
-                        if (m < mrows) a.out[(int64_t)(m0 + m) * a.ldo + n] = (f16)(fin[mr][j] + bv);
+                        if constexpr (GELU) {
+                            // the sum (+ bias) is rounded to f16 first and the activation reads that value back, as
+                            // tgis_gelu would from the act 0 output: same bits as the two launches
+                            const f16 t = (f16)(fin[mr][j] + bv);
+                            const f16 g = (f16)gelu_f32((float)t, ACT == 6);
+                            if (m < mrows) a.out[(int64_t)(m0 + m) * a.ldo + n] = g;
+                        } else {
+                            if (m < mrows) a.out[(int64_t)(m0 + m) * a.ldo + n] = (f16)(fin[mr][j] + bv);
+                        }
                     }
             }
         } else {

@@ -111,15 +111,42 @@ class BigCodeConfig:
         self.num_key_value_heads = 1
 
 
-def bigcode_tensors(config, seed: int, device="cpu", dtype=torch.bfloat16) -> Dict[str, torch.Tensor]:
-    """Seeded full GPT-BigCode checkpoint in HF naming (tied head): N(0, 1/sqrt(fan_in)) weights, small biases."""
+def _random_gptq(t: Dict[str, torch.Tensor], name: str, n: int, k: int, g, device, groupsize: int, bits: int) -> None:
+    """The GPTQ tensors of llama_tensors for one [k, n] matrix, sized to the weight range +-k^-0.5 * U(0.5, 1.5) of the
+    dense BigCode / NeoX recipes: random codes, zero points centred on the mean code (stored nibbles 0..13 / bytes
+    118..134, for the reason given in llama_tensors), g_idx = k // group."""
+    G, per = k // groupsize, 32 // bits
+    shifts = bits * torch.arange(per, device=device, dtype=torch.int64)
+
+    def packed(v, axis):  # `per` codes of `bits` bits along `axis` -> one int32
+        w = (v << shifts.view([-1 if a == axis else 1 for a in range(v.dim())])).sum(axis)
+        return torch.where(w >= 2**31, w - 2**32, w).to(torch.int32)
+
+    t[f"{name}.qweight"] = packed(torch.randint(0, 1 << bits, (k // per, per, n), generator=g, device=device,
+                                                dtype=torch.int64), 1)
+    lo, hi = (0, 14) if bits == 4 else (118, 135)
+    t[f"{name}.qzeros"] = packed(torch.randint(lo, hi, (G, n // per, per), generator=g, device=device, dtype=torch.int64), 2)
+    t[f"{name}.scales"] = ((torch.rand(G, n, generator=g, device=device) + 0.5) * (2.0 / ((1 << bits) - 1)) * k ** -0.5
+                           ).to(torch.float16)
+    t[f"{name}.g_idx"] = torch.arange(k, device=device, dtype=torch.int32) // groupsize
+
+
+def bigcode_tensors(config, seed: int, device="cpu", dtype=torch.bfloat16, quantize: Optional[str] = None,
+                    groupsize: int = 128, bits: int = 4) -> Dict[str, torch.Tensor]:
+    """Seeded full GPT-BigCode checkpoint in HF naming (tied head): N(0, 1/sqrt(fan_in)) weights, small biases.
+    quantize="gptq": the four linears of every layer as qweight / qzeros / scales / g_idx (+ bias) at `bits` = 4 or 8 and
+    `groupsize`; embeddings and LayerNorms stay dense."""
+    assert quantize in (None, "gptq") and bits in (4, 8), (quantize, bits)
     g = torch.Generator(device=device).manual_seed(seed)
     E, I, V = config.hidden_size, config.n_inner, config.vocab_size
     D = E // config.num_attention_heads
     t: Dict[str, torch.Tensor] = {}
 
     def lin(name, n, k):
-        t[f"{name}.weight"] = (torch.randn(n, k, generator=g, device=device) * k ** -0.5).to(dtype)
+        if quantize == "gptq":
+            _random_gptq(t, name, n, k, g, device, groupsize, bits)
+        else:
+            t[f"{name}.weight"] = (torch.randn(n, k, generator=g, device=device) * k ** -0.5).to(dtype)
         t[f"{name}.bias"] = (torch.randn(n, generator=g, device=device) * 0.02).to(dtype)
 
     def ln(name):

@@ -30,19 +30,29 @@ def _shard_q_keep_kv(t: torch.Tensor, dim: int, head_size: int, rank: int, world
     return torch.cat([q, kv], dim=dim)
 
 
+def shard_mqa_gptq(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor, head_size: int, bits: int, rank: int,
+                   world: int):
+    """This rank's (qweight, qzeros, scales) of a fused GPTQ `c_attn` [K, H*D + 2*D]: all three are cut along their column
+    axis, which qzeros holds packed — 32 / bits columns per int32 (8 at 4 bits, 4 at 8 bits)."""
+    pack = 32 // bits
+    assert head_size % pack == 0 and qzeros.shape[1] * pack == qweight.shape[1] == scales.shape[1]
+    return (_shard_q_keep_kv(qweight, 1, head_size, rank, world),
+            _shard_q_keep_kv(qzeros, 1, head_size // pack, rank, world),
+            _shard_q_keep_kv(scales, 1, head_size, rank, world))
+
+
 def load_multi_mqa(config, prefix: str, weights, bias: bool, head_size, num_heads, hidden_size):
     world, rank = weights.process_group.size(), weights.process_group.rank()
     if config.quantize == "gptq":
         if not weights.has(f"{prefix}.c_attn.qweight") or getattr(config, "transpose", False):
             raise NotImplementedError("Gptq loading with santacoder is not implemented")
-        qweight = _shard_q_keep_kv(weights._full(f"{prefix}.c_attn.qweight"), 1, head_size, rank, world)
-        scales = _shard_q_keep_kv(weights._full(f"{prefix}.c_attn.scales"), 1, head_size, rank, world)
-        assert 2 * head_size % 8 == 0
-        qzeros = _shard_q_keep_kv(weights._full(f"{prefix}.c_attn.qzeros"), 1, head_size // 8, rank, world)
-        g_idx = weights.get_tensor(f"{prefix}.c_attn.g_idx")
         bits, groupsize = weights._get_gptq_params()
+        qweight, qzeros, scales = shard_mqa_gptq(weights._full(f"{prefix}.c_attn.qweight"),
+                                                 weights._full(f"{prefix}.c_attn.qzeros"),
+                                                 weights._full(f"{prefix}.c_attn.scales"), head_size, bits, rank, world)
+        g_idx = weights.get_tensor(f"{prefix}.c_attn.g_idx")
         weight = (qweight.to(weights.device), qzeros.to(weights.device), scales.to(weights.device), g_idx, bits,
-                  groupsize, True)
+                  groupsize, bits == 4)
         b = None
         if bias:
             b = weights._finish(_shard_q_keep_kv(weights._full(f"{prefix}.c_attn.bias"), 0, head_size, rank, world))

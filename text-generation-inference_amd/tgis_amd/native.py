@@ -395,8 +395,15 @@ class GptqWeight(_GptqImage):
 def gptq_gemm(x, w: GptqWeight, ws: Workspace, bias=None, act: int = 0, out=None, out_frag: bool = False):
     """act 0: out[M,N] = x @ dequant(W) (+bias); act 1: x is [M,2K], silu(x[:, :K]) * x[:, K:] is the operand;
     act 2 (weight prepared with gate_up=True): out[M,N/2] = silu(gate) * up.
+    act 4 / 5 (M <= w.fused_rows(4) = 256, row-major x): out = gelu(x @ dequant(W) + bias), exact erf form / tanh
+    approximation, applied where the GEMM finishes its output — the bits of act 0 followed by `gelu`.
     x may be a FragAct (decode, M <= 64); with act 2 the result may then leave as a FragAct too (out_frag)."""
     assert act != 2 or w.flags & 1, "act=2 needs a weight prepared with gate_up=True"
+    if act in (4, 5):
+        assert not isinstance(x, FragAct), "act 4 / 5 (GELU) take a row-major activation"
+        if w.flags & 1:  # the library call does not carry the image's column order: refused here, in its name
+            raise TgisHipError("tgis_gptq_gemm_f16: act 4 / 5 (GELU) on a gate|up image (its columns are interleaved for "
+                               "act 2)")
     if isinstance(x, FragAct):
         assert x.K == w.K and act in (0, 2) and w.perm is None
         M, xp, ldx = x.M, _ptr(x.buf), LD_FRAGMENTS

@@ -27,7 +27,7 @@ DEFER_REDUCE = os.getenv("TGIS_DEFER_REDUCE", "true").lower() not in ("0", "fals
 # decode batches of up to 32 rows: rotary embedding + cache write in the epilogue of the int4 qkv GEMM (one launch
 # instead of GEMM + tgis_rope_kv_write, no split-K slabs).  Costs a second image of the qkv weights.
 FUSED_ROPE_GEMM = os.getenv("TGIS_FUSED_ROPE_GEMM", "true").lower() not in ("0", "false")
-# GELU applied by the dense decode GEMM that produces its operand (TGIS_FUSED_GELU_GEMM=false: a launch of its own)
+# GELU applied by the dense or int4 decode GEMM that produces its operand (TGIS_FUSED_GELU_GEMM=false: a launch of its own)
 FUSED_GELU_GEMM = os.getenv("TGIS_FUSED_GELU_GEMM", "true").lower() not in ("0", "false")
 
 _WORKSPACES = {}
@@ -241,6 +241,16 @@ class Ex4bitLinearV2(GptqLinear):
     def forward_rope(self, x, cos, sin, positions, slots, k_pool, v_pool, **kv_scales):
         return native.gptq_gemm_rope(x, self.rope_handle, self.bias, cos, sin, positions, slots, k_pool, v_pool,
                                      *self.rope_heads, **kv_scales)
+
+    def forward_gelu(self, x: torch.Tensor, tanh: bool) -> torch.Tensor:
+        """As FastLinear.forward_gelu, for an int4 `c_fc`: one launch (act 4: erf form / act 5: tanh approximation) up to
+        the rows the streaming passes serve; same bits as the two steps."""
+        assert not self.gate_up
+        if self.q_handle is None:
+            self.post_init()
+        if x.shape[0] <= self.q_handle.fused_rows(4) and FUSED_GELU_GEMM:
+            return native.gptq_gemm(x, self.q_handle, workspace(x.device), bias=self.bias, act=5 if tanh else 4)
+        return native.gelu(self.forward(x), tanh)
 
     def wants_fragments(self, rows: int, act: int = 0) -> bool:
         if self.q_handle is None:
