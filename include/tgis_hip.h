@@ -244,6 +244,35 @@ int tgis_dense_gemm_partial(const void* x, int64_t ldx, const void* prepared, in
                             int dtype, int act, float* slabs, int64_t slabs_bytes, int* num_slabs,
                             int64_t* slab_ld, void* stream);
 
+/* ---- routed expert MLP (Mixtral: transformers' MixtralTopKRouter + MixtralExperts; the reference has no such model) ----
+ * A slot is (token t, choice k) = t * top_k + k.  Nothing below reads the routing on the host, so the four launches of a
+ * block (router GEMM by tgis_dense_gemm with out_f32, route, up, down) can be captured.  Deterministic: integer work for
+ * the lists, k-parts and the top_k addends summed in fixed order, no float atomics. */
+/* logits: fp32 [T, E] (row stride ld), the router GEMM's output.  Per token: softmax over all E, the top_k largest (ties
+ * to the lower expert index), those renormalised to sum 1.  Writes expert_ids int32 [T, top_k], expert_w f32 [T, top_k],
+ * counts int32 [E], offsets int32 [E + 1] (exclusive prefix sum of counts) and slot_rows int32 [T * top_k]: the slots
+ * grouped by expert, ascending inside each expert.  2 <= E <= 64, 1 <= top_k <= min(E, 8), T >= 0 (T * top_k < 2^31);
+ * anything else is TGIS_EINVAL before the device is touched. */
+int tgis_moe_route(const float* logits, int64_t ld, int64_t T, int E, int top_k, int32_t* expert_ids, float* expert_w,
+                   int32_t* counts, int32_t* offsets, int32_t* slot_rows, void* stream);
+/* h[slot, :] = silu(x[t] @ Wgate[e]^T) * (x[t] @ Wup[e]^T) for every slot, e = the slot's expert, each factor rounded to
+ * the model dtype as act 2 of tgis_dense_gemm does.  images: E gate|up images (tgis_dense_prepare with flags bit 0, N =
+ * 2 I rows, I a multiple of 16) expert_stride bytes apart; x [T, K] (row stride ldx, K % 8 == 0); h [T * top_k, N / 2]
+ * (row stride ldh).  The grid is (N / 32, E) whatever the routing; a block whose expert nobody chose reads no weights. */
+int tgis_moe_gemm_up(const void* x, int64_t ldx, const void* images, int64_t expert_stride, const int32_t* offsets,
+                     const int32_t* slot_rows, void* h, int64_t ldh, int64_t T, int64_t K, int64_t N, int E, int top_k,
+                     int dtype, void* stream);
+/* y[slot, :] = (h[slot] @ Wdown[e]^T) * expert_w[slot], the product in fp32.  images: E plain images of W2 [N, K].
+ * form 0 (decode): scratch receives the slabs [ceil(T/32)][top_k][32][ceil(N/32)*32] of a deferred sum — slab k, row t holds
+ * token t's k-th expert, every (t, k) written exactly once — for tgis_rmsnorm_residual_partial with num_slabs = top_k;
+ * out is not used.  form 1: scratch holds y as fp32 [T * top_k, N] and a second launch writes
+ * out[t] = T(sum_k y[t * top_k + k]) in the order k = 0 .. top_k - 1 (N % 4 == 0; row stride ldo).
+ * tgis_moe_gemm_down_bytes: the size of scratch. */
+int64_t tgis_moe_gemm_down_bytes(int64_t T, int64_t N, int top_k, int form);
+int tgis_moe_gemm_down(const void* h, int64_t ldh, const void* images, int64_t expert_stride, const int32_t* offsets,
+                       const int32_t* slot_rows, const float* expert_w, int64_t T, int64_t K, int64_t N, int E, int top_k,
+                       int dtype, int form, float* scratch, int64_t scratch_bytes, void* out, int64_t ldo, void* stream);
+
 /* ---- fused residual-add + RMSNorm / LayerNorm (replaces dropout_layer_norm.dropout_add_ln_fwd,
  *      custom_modeling/flash_llama_modeling.py:132-152, utils/layers.py:376-396) ---------------- */
 /* res_out = x (+ residual); y = res_out * rsqrt(mean(res_out^2) + eps) * weight.

@@ -91,6 +91,55 @@ def llama_tensors(config, quantize: Optional[str], seed: int, groupsize: int = 1
     return t
 
 
+class MixtralConfig:
+    """The fields of HF's MixtralConfig that FlashMixtralForCausalLM reads; the defaults are Mixtral-8x7B's."""
+    model_type = "mixtral"
+
+    def __init__(self, vocab_size=32000, hidden_size=4096, intermediate_size=14336, num_hidden_layers=32,
+                 num_attention_heads=32, num_key_value_heads=8, num_local_experts=8, num_experts_per_tok=2,
+                 max_position_embeddings=32768, rms_norm_eps=1e-5, rope_theta=1e6, sliding_window=None):
+        self.vocab_size, self.hidden_size, self.intermediate_size = vocab_size, hidden_size, intermediate_size
+        self.num_hidden_layers, self.num_attention_heads = num_hidden_layers, num_attention_heads
+        self.num_key_value_heads = num_key_value_heads
+        self.num_local_experts, self.num_experts_per_tok = num_local_experts, num_experts_per_tok
+        self.max_position_embeddings, self.rms_norm_eps, self.rope_theta = max_position_embeddings, rms_norm_eps, rope_theta
+        self.sliding_window = sliding_window
+        self.hidden_act = "silu"
+        self.tie_word_embeddings = False
+        self.pad_token_id, self.bos_token_id, self.eos_token_id = None, 1, 2
+
+
+def mixtral_tensors(config, seed: int, device="cpu", dtype=torch.bfloat16, head_scale: float = 1.0) -> Dict[str, torch.Tensor]:
+    """Seeded full Mixtral checkpoint under the published names (block_sparse_moe.gate, experts.N.w1 / w3 / w2 = gate, up,
+    down): N(0, 1/sqrt(fan_in)) linears, so that the router's logits spread over the experts, unit RMSNorms."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    E, I, V = config.hidden_size, config.intermediate_size, config.vocab_size
+    D = getattr(config, "head_dim", None) or E // config.num_attention_heads
+    H, Hkv = config.num_attention_heads, config.num_key_value_heads
+    t: Dict[str, torch.Tensor] = {}
+
+    def lin(name, n, k, scale=1.0):
+        t[f"{name}.weight"] = (torch.randn(n, k, generator=g, device=device) * (k ** -0.5 * scale)).to(dtype)
+
+    t["model.embed_tokens.weight"] = torch.randn(V, E, generator=g, device=device).to(dtype)
+    for i in range(config.num_hidden_layers):
+        p = f"model.layers.{i}"
+        lin(f"{p}.self_attn.q_proj", H * D, E)
+        lin(f"{p}.self_attn.k_proj", Hkv * D, E)
+        lin(f"{p}.self_attn.v_proj", Hkv * D, E)
+        lin(f"{p}.self_attn.o_proj", E, H * D)
+        lin(f"{p}.block_sparse_moe.gate", config.num_local_experts, E)
+        for e in range(config.num_local_experts):
+            lin(f"{p}.block_sparse_moe.experts.{e}.w1", I, E)
+            lin(f"{p}.block_sparse_moe.experts.{e}.w3", I, E)
+            lin(f"{p}.block_sparse_moe.experts.{e}.w2", E, I)
+        t[f"{p}.input_layernorm.weight"] = torch.ones(E, device=device, dtype=dtype)
+        t[f"{p}.post_attention_layernorm.weight"] = torch.ones(E, device=device, dtype=dtype)
+    t["model.norm.weight"] = torch.ones(E, device=device, dtype=dtype)
+    lin("lm_head", V, E, head_scale)
+    return t
+
+
 class BigCodeConfig:
     """The fields of HF's GPTBigCodeConfig that FlashSantacoderForCausalLM reads (multi-query attention)."""
     model_type = "gpt_bigcode"

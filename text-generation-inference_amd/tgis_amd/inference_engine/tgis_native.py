@@ -1,7 +1,8 @@
 """The native engine: model type -> MI355X model class, process group, safetensors `Weights`, GPTQ params
 (mirrors inference_engine/tgis_native.py:23-139 of the reference; model families of the configs in
 BASELINE.json: llama, and gpt_bigcode when flash_santacoder_modeling is present; gpt_neox; mistral, whose tensors carry
-Llama's names and whose sliding window FlashCausalLM reads from the config)."""
+Llama's names and whose sliding window FlashCausalLM reads from the config; mixtral, which is mistral around a routed expert
+MLP)."""
 import os
 from typing import Any, Optional
 
@@ -13,7 +14,7 @@ from tgis_amd.utils.dist import initialize_torch_distributed
 from tgis_amd.utils.hub import local_weight_files
 from tgis_amd.utils.weights import Weights
 
-FLASH_TYPES = ["llama", "gpt_bigcode", "gpt_neox", "mistral"]
+FLASH_TYPES = ["llama", "gpt_bigcode", "gpt_neox", "mistral", "mixtral"]
 
 
 def _barrier(group):
@@ -32,6 +33,12 @@ def model_class_for(config):
         from tgis_amd.models.custom_modeling.flash_llama_modeling import FlashLlamaForCausalLM
 
         return FlashLlamaForCausalLM, aliases
+    if model_type == "mixtral":
+        if getattr(config, "tie_word_embeddings", False):
+            aliases = {"lm_head.weight": ["model.embed_tokens.weight"]}
+        from tgis_amd.models.custom_modeling.flash_mixtral_modeling import FlashMixtralForCausalLM
+
+        return FlashMixtralForCausalLM, aliases
     if model_type == "gpt_bigcode":
         from tgis_amd.models.custom_modeling.flash_santacoder_modeling import FlashSantacoderForCausalLM
 

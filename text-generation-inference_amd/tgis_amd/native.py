@@ -72,7 +72,13 @@ SIGNATURES = {
     "tgis_dense_gemm_partial_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
     "tgis_dense_gemm_partial": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _vp, _c_i64,
                                          ctypes.POINTER(_c_int), ctypes.POINTER(_c_i64), _vp]),
-    "tgis_rmsnorm_residual": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_f, _c_int, _vp]),
+    "tgis_moe_route": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tgis_moe_gemm_up": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int,
+                                  _c_int, _vp]),
+    "tgis_moe_gemm_down_bytes": (_c_i64, [_c_i64, _c_i64, _c_int, _c_int]),
+    "tgis_moe_gemm_down": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int,
+                                    _c_int, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "tgis_rmsnorm_residual":(_c_int, [_vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_f, _c_int, _vp]),
     "tgis_rmsnorm_residual_partial": (_c_int, [_vp, _c_int, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_f,
                                                _c_int, _vp]),
     "tgis_layernorm_residual": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_f, _c_int, _vp]),
@@ -634,6 +640,93 @@ def dense_gemm_rope(x: torch.Tensor, w: DenseWeight, bias, cos, sin, positions, 
             _ptr(out), out.stride(0), _ptr(k_pool), _ptr(v_pool), M, w.K, w.N, H, Hkv, D, dtype_code(w.dtype), _stream())
     _call_kv("tgis_dense_gemm_rope", args, k_pool, v_pool, kv_scales)
     return out
+
+
+# ---- routed expert MLP (Mixtral) ----------------------------------------------------------------------
+class MoeWeights:
+    """One projection of E experts: E images of tgis_dense_prepare in one buffer, `stride` bytes apart.  gate_up=True: each
+    expert's weight is its [gate | up] (w1 | w3) and the image interleaves the pairs for the SiLU * up epilogue.
+    `expert_weight(e)` returns expert e's [N, K] tensor on the GPU; it is dropped as soon as its image is made."""
+
+    def __init__(self, expert_weight, E: int, gate_up: bool = False):
+        lib = load_library()
+        self.E, self.flags = E, (1 if gate_up else 0)
+        self.image = None
+        for e in range(E):
+            w = expert_weight(e).contiguous()
+            if self.image is None:
+                assert w.dim() == 2
+                self.N, self.K = w.shape
+                self.dtype = w.dtype
+                self.stride = lib.tgis_dense_prepared_bytes(self.N, self.K)
+                self.image = torch.empty((E, self.stride), dtype=torch.uint8, device=w.device)
+            assert tuple(w.shape) == (self.N, self.K) and w.dtype == self.dtype
+            _check(lib.tgis_dense_prepare(_ptr(w), self.N, self.K, dtype_code(w.dtype), self.flags, _ptr(self.image[e]),
+                                          _stream()), "tgis_dense_prepare")
+            torch.cuda.current_stream().synchronize()  # (w goes out of scope here)
+
+    def expert(self, e: int) -> DenseWeight:
+        """Expert e's image as a DenseWeight (a view, nothing is copied): what dense_gemm takes on the loop path."""
+        w = DenseWeight.__new__(DenseWeight)
+        w.N, w.K, w.dtype, w.flags, w.answers, w.image = self.N, self.K, self.dtype, self.flags, {}, self.image[e]
+        return w
+
+
+class Routing:
+    """What moe_route leaves on the device for T tokens: expert_ids int32 [T, top_k], expert_w f32 [T, top_k], counts int32
+    [E], offsets int32 [E + 1], slot_rows int32 [T top_k] (slots t * top_k + k grouped by expert, ascending inside each)."""
+
+    def __init__(self, T: int, E: int, top_k: int, device):
+        self.T, self.E, self.top_k = T, E, top_k
+        self.expert_ids = torch.empty((T, top_k), dtype=torch.int32, device=device)
+        self.expert_w = torch.empty((T, top_k), dtype=torch.float32, device=device)
+        # counts and offsets share one allocation: the loop path reads both back in one copy
+        self.lists = torch.empty(2 * E + 1, dtype=torch.int32, device=device)
+        self.counts, self.offsets = self.lists[:E], self.lists[E:]
+        self.slot_rows = torch.empty(T * top_k, dtype=torch.int32, device=device)
+
+
+def moe_route(logits: torch.Tensor, top_k: int) -> Routing:
+    """Top-k routing of fp32 router logits [T, E] (softmax, top_k, renormalise: MixtralTopKRouter), all on the device."""
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and (logits.shape[0] == 0 or logits.stride(1) == 1)
+    T, E = logits.shape
+    r = Routing(T, E, top_k, logits.device)
+    _check(load_library().tgis_moe_route(_ptr(logits), logits.stride(0), T, E, top_k, _ptr(r.expert_ids), _ptr(r.expert_w),
+                                         _ptr(r.counts), _ptr(r.offsets), _ptr(r.slot_rows), _stream()), "tgis_moe_route")
+    return r
+
+
+def moe_gemm_up(x: torch.Tensor, w: MoeWeights, r: Routing, out=None) -> torch.Tensor:
+    """h [T top_k, I]: SiLU(gate) * up of every slot's token under the slot's expert (act 2's rounding)."""
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == w.dtype and x.shape == (r.T, w.K) and w.flags & 1 and w.E == r.E
+    if out is None:
+        out = torch.empty((r.T * r.top_k, w.N // 2), dtype=w.dtype, device=x.device)
+    _check(load_library().tgis_moe_gemm_up(_ptr(x), x.stride(0), _ptr(w.image), w.stride, _ptr(r.offsets), _ptr(r.slot_rows),
+                                           _ptr(out), out.stride(0), r.T, w.K, w.N, w.E, r.top_k, dtype_code(w.dtype),
+                                           _stream()), "tgis_moe_gemm_up")
+    return out
+
+
+def moe_gemm_down(h: torch.Tensor, w: MoeWeights, r: Routing, partial: bool = False):
+    """Every slot's row of h through its expert's down projection, scaled by its routing weight in fp32.  partial (T <=
+    PARTIAL_MAX_M): a Partial with S = top_k whose slab k, row t holds token t's k-th expert — the next add + RMSNorm
+    finishes the sum.  Otherwise the finished [T, hidden] tensor in the model dtype, summed over k in fixed order."""
+    assert h.dim() == 2 and h.stride(1) == 1 and h.dtype == w.dtype and h.shape == (r.T * r.top_k, w.K)
+    assert not (w.flags & 1) and w.E == r.E
+    lib = load_library()
+    form = 0 if partial else 1
+    assert not partial or r.T <= PARTIAL_MAX_M
+    nbytes = lib.tgis_moe_gemm_down_bytes(r.T, w.N, r.top_k, form)
+    scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=h.device)
+    out = None if partial else torch.empty((r.T, w.N), dtype=w.dtype, device=h.device)
+    _check(lib.tgis_moe_gemm_down(_ptr(h), h.stride(0), _ptr(w.image), w.stride, _ptr(r.offsets), _ptr(r.slot_rows),
+                                  _ptr(r.expert_w), r.T, w.K, w.N, w.E, r.top_k, dtype_code(w.dtype), form, _ptr(scratch),
+                                  nbytes, _ptr(out), w.N, _stream()), "tgis_moe_gemm_down")
+    if not partial:
+        return out
+    p = Partial(scratch, r.top_k, (w.N + 31) // 32 * 32, r.T, w.N, None)
+    p.dtype = w.dtype
+    return p
 
 
 def clear_error() -> None:
