@@ -19,13 +19,18 @@ def _lib():
     return lib
 
 
-@pytest.mark.parametrize("case", mc.plan_cases(), ids=lambda c: "which{}-T{}-K{}-N{}".format(*c))
+def _case_id(c):
+    """The cases at E 8, top_k 2 keep the ids they had before the tuples carried E and top_k."""
+    return "which{}-T{}-K{}-N{}".format(*c) + ("" if c[4:] == (mc.E, mc.TOP_K) else "-E{}-k{}".format(*c[4:]))
+
+
+@pytest.mark.parametrize("case", mc.plan_cases(), ids=_case_id)
 def test_plan_is_the_restated_one(case):
-    which, T, K, N = case
+    which, T, K, N, E, top_k = case
     lib = _lib()
     info = (ctypes.c_int * 16)()
-    assert lib.tgis_debug_moe_plan(which, T, K, N, mc.E, mc.TOP_K, info) == 0, lib.tgis_last_error()
-    assert list(info)[:12] == mc.plan(which, T, K, N, mc.E, mc.TOP_K)
+    assert lib.tgis_debug_moe_plan(which, T, K, N, E, top_k, info) == 0, lib.tgis_last_error()
+    assert list(info)[:12] == mc.plan(which, T, K, N, E, top_k)
     assert list(info)[12:] == [0, 0, 0, 0]
 
 
