@@ -272,6 +272,20 @@ int64_t tgis_moe_gemm_down_bytes(int64_t T, int64_t N, int top_k, int form);
 int tgis_moe_gemm_down(const void* h, int64_t ldh, const void* images, int64_t expert_stride, const int32_t* offsets,
                        const int32_t* slot_rows, const float* expert_w, int64_t T, int64_t K, int64_t N, int E, int top_k,
                        int dtype, int form, float* scratch, int64_t scratch_bytes, void* out, int64_t ldo, void* stream);
+/* The two expert GEMMs over int4 GPTQ weights: the contracts of tgis_moe_gemm_up / tgis_moe_gemm_down (same grid, same
+ * early return for an unchosen expert — neither its nibbles nor its scale table are read — same epilogues, same slabs and
+ * tgis_moe_gemm_down_bytes, same run-to-run bytes) with images = E images of tgis_gptq_prepare for (K, N, groups),
+ * expert_stride >= tgis_gptq_prepared_bytes(K, N, groups) bytes apart (a multiple of 16); gate|up images are prepared with
+ * flags bit 0.  The weight a product sees is f16((q - z - 1) * scale), one rounding, as tgis_gptq_gemm_f16's.
+ * Served: dtype TGIS_F16, K % 64 == 0, N % 32 == 0, one group or groups of 64 * 2^n rows that divide K, no act-order
+ * permutation; anything else (groups of 32 rows, bf16, a stride below one image) is TGIS_EINVAL before any launch. */
+int tgis_moe_gptq_gemm_up(const void* x, int64_t ldx, const void* images, int64_t expert_stride, const int32_t* offsets,
+                          const int32_t* slot_rows, void* h, int64_t ldh, int64_t T, int64_t K, int64_t N, int64_t groups,
+                          int E, int top_k, int dtype, void* stream);
+int tgis_moe_gptq_gemm_down(const void* h, int64_t ldh, const void* images, int64_t expert_stride, const int32_t* offsets,
+                            const int32_t* slot_rows, const float* expert_w, int64_t T, int64_t K, int64_t N, int64_t groups,
+                            int E, int top_k, int dtype, int form, float* scratch, int64_t scratch_bytes, void* out,
+                            int64_t ldo, void* stream);
 
 /* ---- fused residual-add + RMSNorm / LayerNorm (replaces dropout_layer_norm.dropout_add_ln_fwd,
  *      custom_modeling/flash_llama_modeling.py:132-152, utils/layers.py:376-396) ---------------- */

@@ -16,15 +16,31 @@
 // Expert weights are E images of tgis_dense_prepare (dense_gemm_body.h's layout: [NT][KS][4][64 lanes][8 elements], zero
 // padded past K and N) at a fixed byte stride: gate|up images with flags bit 0 (a (gate, up) pair sits 16 lanes apart in
 // one wave), down images plain.  mfma32, finish_out and the SiLU * up rounding are the dense unit's, by inclusion.
+//
+//   tgis_moe_gptq_gemm_up / _down  the same two launches over E int4 images of tgis_gptq_prepare (gptq_gemm_body.h's
+//                       layout: nibbles [NT][KS'][64 lanes][4 words], then {scale, 1024 + z + 1} pairs [NT][G][32]).  The
+//                       kernel is the one above with another weight source: a wave loads 1 KiB per k64-step, dequantises it
+//                       with the int4 unit's dequant8 (one rounding to f16) and feeds the same MFMAs; the slab walk, the LDS
+//                       exchange and the epilogues are shared.  f16, K a multiple of 64, groups of 64 * 2^n rows or one group.
 #include <algorithm>
 #include "common.h"
 #include "dispatch.h"
 #include "dense_gemm_body.h"
+#include "gptq_gemm_body.h"
 
 namespace {
 
 constexpr int MOE_WK = 4;        // k-parts (waves) per block
 constexpr int MOE_RING = 4;      // k64-steps of weights a wave keeps in flight (4 x 4 KiB)
+// The int4 images' ring.  A step is 1 KiB there, a quarter of the dense ring's bytes in flight at the same depth, but 4 / 8 /
+// 16 swept with tools/bench_mixtral.py --quantize gptq --ring measured 4 fastest at B 1, 8 and 32: the registers of a deeper
+// ring cost a wave per SIMD each time (3 / 2 / 1 waves), which hides more latency than the ring does.
+// The macro is that sweep's switch.
+#ifndef TGIS_MOE_GPTQ_RING
+#define TGIS_MOE_GPTQ_RING 4
+#endif
+constexpr int MOE_GPTQ_RING = TGIS_MOE_GPTQ_RING;
+static_assert(MOE_GPTQ_RING == 4 || MOE_GPTQ_RING == 8 || MOE_GPTQ_RING == 16, "the int4 ring is 4, 8 or 16 k64-steps");
 constexpr int MOE_THREADS = 64 * MOE_WK;
 constexpr int MOE_LDS = MOE_WK * 64 * 16 * 4;  // the k-part exchange: [WK][64 lanes][16] fp32
 constexpr int ROUTE_THREADS = 1024;
@@ -127,13 +143,92 @@ struct MoeArgs {
     int64_t ldo;              // elements between output rows (form 0: the slab row stride)
     int K, N, NT, KS, top_k;
     int form;                 // DOWN: 0 slabs [T / 32][top_k][32][ldo], 1 one fp32 row per slot
+    // int4 images only
+    int KSI;                  // k64-steps a tile holds in the image (KS' of gptq::prep_layout: the real ones plus padding)
+    int G, spg_shift;         // groups; log2(k64-steps per group), 30 under a single group
+    int64_t offB;             // bytes from an image's start to its {scale, zero} table
+};
+
+// ---- weight sources: where a wave's B fragments of one k64-step come from ---------------------------------------------------
+// A source is built once per wave for (expert, column tile, first k64-step); load(step, slot) asks for the step's bytes and
+// frags(slot, b) turns them into the four 32x32x16 B fragments.
+
+// 16-bit image of tgis_dense_prepare: 4 KiB per step, stored as fragments.
+template <typename T>
+struct DenseSource {
+    using V8 = typename VecT<T>::x8;
+    static constexpr int RING = MOE_RING;
+    static constexpr int NACC = 2;  // accumulators the MFMAs of a step alternate between
+    static constexpr int WAVES = 1;  // waves per SIMD the register allocation must leave room for
+    struct Step {
+        V8 v[4];
+    };
+    const char* tile;
+    uint32_t woff;
+    __device__ __forceinline__ DenseSource(const MoeArgs& a, int e, int nt, int ks0, int lane)
+        : tile(reinterpret_cast<const char*>(a.images) + (int64_t)e * a.stride + ((int64_t)nt * a.KS + ks0) * 4096),
+          woff(lane * 16) {}
+    __device__ __forceinline__ void load(int step, Step& dst) const {
+        const char* p = tile + (int64_t)step * 4096;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dst.v[i] = __builtin_nontemporal_load(reinterpret_cast<const V8*>(p + i * 1024 + woff));
+    }
+    __device__ __forceinline__ void frags(const Step& s, V8 (&b)[4]) const {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) b[i] = s.v[i];
+    }
+};
+
+// int4 image of tgis_gptq_prepare (f16): 1 KiB of nibbles per step, one 16-byte load per lane, and the lane's column's
+// {scale, 1024 + z + 1} pair of the step's group, asked for with the nibbles and kept with them in the ring.
+struct Int4Source {
+    using V8 = f16x8;
+    static constexpr int RING = MOE_GPTQ_RING;
+    // One accumulator, as the int4 unit of gptq_gemm_body.h: the dequantisation between two MFMAs covers their dependency,
+    // and without the second one the kernel fits 128 registers — 4 waves per SIMD, which measured 8 - 18 % faster than 3
+    // (DESIGN.md section 6).  A deeper ring does not fit and keeps the allocator's own choice.
+    static constexpr int NACC = 1;
+    static constexpr int WAVES = MOE_GPTQ_RING == 4 ? 4 : 1;
+    struct Step {
+        u32x4 q;
+        uint32_t sz;
+    };
+    const char* tile;
+    const char* sztile;
+    uint32_t woff, szoff, EX, M0, M1;
+    int ks0, spg_shift, G;
+    __device__ __forceinline__ Int4Source(const MoeArgs& a, int e, int nt, int ks0_, int lane)
+        : woff(lane * 16), szoff((lane & 31) * 4), EX(0x64006400u), M0(0x000F000Fu), M1(0x00F000F0u), ks0(ks0_),
+          spg_shift(a.spg_shift), G(a.G) {
+        const char* image = reinterpret_cast<const char*>(a.images) + (int64_t)e * a.stride;
+        tile = image + ((int64_t)nt * a.KSI + ks0) * 1024;
+        sztile = image + a.offB + (int64_t)nt * a.G * 128;
+        asm volatile("" : "+v"(EX));  // dequant8 takes the exponent pair in a VGPR and the masks in SGPRs
+        asm volatile("" : "+s"(M0), "+s"(M1));
+    }
+    __device__ __forceinline__ void load(int step, Step& dst) const {
+        const int g = min((ks0 + step) >> spg_shift, G - 1);
+        dst.sz = *reinterpret_cast<const uint32_t*>(sztile + (int64_t)g * 128 + szoff);
+        dst.q = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(tile + (int64_t)step * 1024 + woff));
+    }
+    __device__ __forceinline__ void frags(const Step& s, V8 (&b)[4]) const {
+        const f16x2 szh = __builtin_bit_cast(f16x2, s.sz);
+        const f16 zc1 = szh[1];
+        const f16 zd1 = (f16)960.f - zc1;  // -(64 + z + 1), exact
+        const f16x2 zc = {zc1, zc1}, zd = {zd1, zd1}, sc = {szh[0], szh[0]};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) b[i] = gptq::dequant8(s.q[i], zc, zd, sc, EX, M0, M1);
+    }
 };
 
 // UP == true: gate|up image, SiLU * up epilogue, rows of x gathered through slot / top_k.
 // UP == false: plain image, rows of h are the slots themselves, each finished row scaled by its expert_w in fp32.
-template <typename T, bool UP>
-__global__ __launch_bounds__(MOE_THREADS) void moe_gemm_kernel(MoeArgs a) {
+// W: the weight source (DenseSource<T> or Int4Source).
+template <typename T, bool UP, typename W>
+__global__ __launch_bounds__(MOE_THREADS, W::WAVES) void moe_gemm_kernel(MoeArgs a) {
     using V8 = typename VecT<T>::x8;
+    using WStep = typename W::Step;
+    constexpr int RING = W::RING;
     __shared__ __attribute__((aligned(16))) float red[MOE_WK * 64 * 16];
     const int nt = blockIdx.x, e = blockIdx.y;
     const int row0 = a.offsets[e], cnt = a.offsets[e + 1] - row0;
@@ -143,15 +238,8 @@ __global__ __launch_bounds__(MOE_THREADS) void moe_gemm_kernel(MoeArgs a) {
     const int per = (a.KS + MOE_WK - 1) / MOE_WK;
     const int ks0 = min(wk * per, a.KS), ks1 = min(ks0 + per, a.KS);
     const int nsteps = ks1 - ks0;  // (may be 0 under a short K: the wave then contributes zeros)
-    const char* wtile = reinterpret_cast<const char*>(a.images) + (int64_t)e * a.stride + ((int64_t)nt * a.KS + ks0) * 4096;
-    const uint32_t woff = lane * 16;
+    const W src_w(a, e, nt, ks0, lane);
     const int c = lane & 31, half_k = (lane >> 5) * 32;
-
-    auto w_load = [&](int step, V8* dst) {
-        const char* p = wtile + (int64_t)step * 4096;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dst[i] = __builtin_nontemporal_load(reinterpret_cast<const V8*>(p + i * 1024 + woff));
-    };
 
     for (int slab = 0; slab * 32 < cnt; ++slab) {
         const int rows = min(32, cnt - slab * 32);
@@ -173,29 +261,32 @@ __global__ __launch_bounds__(MOE_THREADS) void moe_gemm_kernel(MoeArgs a) {
             }
         };
         f32x16 acc0 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc1 = acc0;
-        V8 wq[MOE_RING][4], xq[2][4];
+        WStep wq[RING];
+        V8 xq[2][4];
         if (nsteps > 0) {
             x_load(0, xq[0]);
 #pragma unroll
-            for (int s = 0; s < MOE_RING; ++s)
-                if (s < nsteps) w_load(s, wq[s]);
+            for (int s = 0; s < RING; ++s)
+                if (s < nsteps) src_w.load(s, wq[s]);
         }
-        for (int s0 = 0; s0 < nsteps; s0 += MOE_RING) {
+        for (int s0 = 0; s0 < nsteps; s0 += RING) {
 #pragma unroll
-            for (int r = 0; r < MOE_RING; ++r) {
+            for (int r = 0; r < RING; ++r) {
                 const int s = s0 + r;
                 if (s < nsteps) {
                     if (s + 1 < nsteps) x_load(s + 1, xq[(r + 1) & 1]);
+                    V8 b[4];
+                    src_w.frags(wq[r], b);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        if (i & 1) acc1 = mfma32(xq[r & 1][i], wq[r][i], acc1);
-                        else acc0 = mfma32(xq[r & 1][i], wq[r][i], acc0);
+                        if ((i & 1) && W::NACC == 2) acc1 = mfma32(xq[r & 1][i], b[i], acc1);
+                        else acc0 = mfma32(xq[r & 1][i], b[i], acc0);
                     }
-                    if (s + MOE_RING < nsteps) w_load(s + MOE_RING, wq[r]);  // the slot is consumed: refill it in place
+                    if (s + RING < nsteps) src_w.load(s + RING, wq[r]);  // the slot is consumed: refill it in place
                 }
             }
         }
-        const f32x16 acc = acc0 + acc1;
+        const f32x16 acc = W::NACC == 2 ? acc0 + acc1 : acc0;
         // ---- k-parts through LDS, summed in the fixed order 0..WK-1 ----------------------------------------------------
         __syncthreads();  // (the previous slab's exchange has been read)
         {
@@ -268,8 +359,9 @@ int moe_check_routing(const char* fn, int64_t T, int64_t E, int64_t top_k) {
     return TGIS_OK;
 }
 
+// G == 0: 16-bit images of tgis_dense_prepare; G >= 1: int4 images of tgis_gptq_prepare with G groups.
 int moe_check_gemm(const char* fn, const void* x, int64_t ldx, const void* images, int64_t stride, const void* offsets,
-                   const void* slot_rows, int64_t T, int64_t K, int64_t N, int64_t E, int64_t top_k, int dtype) {
+                   const void* slot_rows, int64_t T, int64_t K, int64_t N, int64_t E, int64_t top_k, int dtype, int64_t G = 0) {
     const int rc = moe_check_routing(fn, T, E, top_k);
     if (rc != TGIS_OK) return rc;
     TGIS_CHECK_ARG(x && images && offsets && slot_rows, "%s: null tensor", fn);
@@ -277,9 +369,23 @@ int moe_check_gemm(const char* fn, const void* x, int64_t ldx, const void* image
     TGIS_CHECK_ARG(K > 0 && N > 0 && K % 8 == 0 && K < (1ll << 30) && N < (1ll << 30), "%s: K (%ld) must be a positive multiple of 8, N (%ld) positive",
                    fn, (long)K, (long)N);
     TGIS_CHECK_ARG(ldx >= K && ldx % 8 == 0 && ((uintptr_t)x % 16) == 0, "%s: rows of the activation must be 16-byte aligned", fn);
-    TGIS_CHECK_ARG(stride >= cdiv64(N, 32) * cdiv64(K, 64) * 4096 && stride % 16 == 0 && ((uintptr_t)images % 16) == 0,
+    const int64_t image_bytes = G == 0 ? cdiv64(N, 32) * cdiv64(K, 64) * 4096 : gptq::prep_layout(K, N, G).total;
+    TGIS_CHECK_ARG(stride >= image_bytes && stride % 16 == 0 && ((uintptr_t)images % 16) == 0,
                    "%s: the expert stride (%ld) must hold one prepared image", fn, (long)stride);
     TGIS_CHECK_ARG(cdiv64(N, 32) <= 0x7fffffff / 32, "%s: N too large", fn);
+    return TGIS_OK;
+}
+
+// The shapes the int4 weight source serves: whole k64-steps and column tiles, and a {scale, zero} pair per lane and step —
+// one group, or groups of 64 * 2^n rows.  Groups of 32 rows and act-order permutations have no form here.
+int moe_check_gptq_shape(const char* fn, int64_t K, int64_t N, int64_t G, int dtype) {
+    TGIS_CHECK_ARG(dtype == TGIS_F16, "%s: int4 expert images are served in f16 only", fn);
+    TGIS_CHECK_ARG(K > 0 && N > 0 && K % 64 == 0 && N % 32 == 0, "%s: K (%ld) must be a multiple of 64 and N (%ld) of 32", fn,
+                   (long)K, (long)N);
+    TGIS_CHECK_ARG(G >= 1 && K % G == 0, "%s: %ld groups do not divide K (%ld)", fn, (long)G, (long)K);
+    const int64_t gs = K / G;
+    TGIS_CHECK_ARG(G == 1 || (gs % 64 == 0 && ((gs / 64) & (gs / 64 - 1)) == 0),
+                   "%s: groups of %ld rows are not served (one group, or 64 * 2^n rows)", fn, (long)gs);
     return TGIS_OK;
 }
 
@@ -290,6 +396,25 @@ void moe_fill(MoeArgs& a, const void* x, int64_t ldx, const void* images, int64_
     a.offsets = offsets, a.slot_rows = slot_rows, a.expert_w = expert_w;
     a.out = out, a.ldo = ldo;
     a.K = (int)K, a.N = (int)N, a.NT = (int)cdiv64(N, 32), a.KS = (int)cdiv64(K, 64), a.top_k = top_k, a.form = form;
+    a.KSI = 0, a.G = 0, a.spg_shift = 0, a.offB = 0;
+}
+
+// the int4 fields, for a shape moe_check_gptq_shape has admitted
+void moe_fill_gptq(MoeArgs& a, int64_t K, int64_t N, int64_t G) {
+    const gptq::PrepLayout p = gptq::prep_layout(K, N, G);
+    a.KSI = (int)p.KS, a.G = (int)G, a.offB = p.offB;
+    a.spg_shift = 30;
+    if (G > 1)
+        for (a.spg_shift = 0; (64ll << a.spg_shift) < K / G; ++a.spg_shift) {}
+}
+
+// What both down entry points ask of their arguments beyond moe_check_gemm; scratch is checked by the caller once T > 0.
+int moe_check_down(const char* fn, const float* expert_w, int64_t T, int64_t N, int top_k, int form, const void* out, int64_t ldo) {
+    TGIS_CHECK_ARG(form == 0 || form == 1, "%s: form must be 0 (slabs) or 1 (finished)", fn);
+    TGIS_CHECK_ARG(expert_w, "%s: null expert_w", fn);
+    TGIS_CHECK_ARG(form == 1 || cdiv64(T, 32) * top_k * 32 < (1ll << 31), "%s: T too large for the slab form", fn);
+    TGIS_CHECK_ARG(form == 0 || (out && ldo >= N && N % 4 == 0), "%s: the finished form needs `out` with rows of N (a multiple of 4) elements", fn);
+    return TGIS_OK;
 }
 
 }  // namespace
@@ -318,11 +443,31 @@ extern "C" int tgis_moe_gemm_up(const void* x, int64_t ldx, const void* images, 
     moe_fill(a, x, ldx, images, expert_stride, offsets, slot_rows, nullptr, h, ldh, K, N, top_k, 0);
     TgisTimedScope timed(TGIS_OP_DENSE_GEMM, (hipStream_t)stream);
     return by_dtype(dtype, [&](auto t) {
-        hipLaunchKernelGGL((moe_gemm_kernel<type_of<decltype(t)>, true>), dim3((unsigned)a.NT, (unsigned)E), dim3(MOE_THREADS),
-                           0, (hipStream_t)stream, a);
+        using T_ = type_of<decltype(t)>;
+        hipLaunchKernelGGL((moe_gemm_kernel<T_, true, DenseSource<T_>>), dim3((unsigned)a.NT, (unsigned)E), dim3(MOE_THREADS), 0,
+                           (hipStream_t)stream, a);
         TGIS_CHECK_LAUNCH();
         return TGIS_OK;
     });
+}
+
+extern "C" int tgis_moe_gptq_gemm_up(const void* x, int64_t ldx, const void* images, int64_t expert_stride, const int32_t* offsets,
+                                     const int32_t* slot_rows, void* h, int64_t ldh, int64_t T, int64_t K, int64_t N,
+                                     int64_t groups, int E, int top_k, int dtype, void* stream) {
+    int rc = moe_check_gptq_shape("tgis_moe_gptq_gemm_up", K, N, groups, dtype);
+    if (rc != TGIS_OK) return rc;
+    rc = moe_check_gemm("tgis_moe_gptq_gemm_up", x, ldx, images, expert_stride, offsets, slot_rows, T, K, N, E, top_k, dtype, groups);
+    if (rc != TGIS_OK) return rc;
+    TGIS_CHECK_ARG(h && ldh >= N / 2, "tgis_moe_gptq_gemm_up: h rows must hold N / 2 elements");
+    if (T == 0) return TGIS_OK;
+    MoeArgs a;
+    moe_fill(a, x, ldx, images, expert_stride, offsets, slot_rows, nullptr, h, ldh, K, N, top_k, 0);
+    moe_fill_gptq(a, K, N, groups);
+    TgisTimedScope timed(TGIS_OP_GPTQ_GEMM, (hipStream_t)stream);
+    hipLaunchKernelGGL((moe_gemm_kernel<f16, true, Int4Source>), dim3((unsigned)a.NT, (unsigned)E), dim3(MOE_THREADS), 0,
+                       (hipStream_t)stream, a);
+    TGIS_CHECK_LAUNCH();
+    return TGIS_OK;
 }
 
 extern "C" int64_t tgis_moe_gemm_down_bytes(int64_t T, int64_t N, int top_k, int form) {
@@ -337,10 +482,8 @@ extern "C" int tgis_moe_gemm_down(const void* h, int64_t ldh, const void* images
                                   void* stream) {
     const int rc = moe_check_gemm("tgis_moe_gemm_down", h, ldh, images, expert_stride, offsets, slot_rows, T, K, N, E, top_k, dtype);
     if (rc != TGIS_OK) return rc;
-    TGIS_CHECK_ARG(form == 0 || form == 1, "tgis_moe_gemm_down: form must be 0 (slabs) or 1 (finished)");
-    TGIS_CHECK_ARG(expert_w, "tgis_moe_gemm_down: null expert_w");
-    TGIS_CHECK_ARG(form == 1 || cdiv64(T, 32) * top_k * 32 < (1ll << 31), "tgis_moe_gemm_down: T too large for the slab form");
-    TGIS_CHECK_ARG(form == 0 || (out && ldo >= N && N % 4 == 0), "tgis_moe_gemm_down: the finished form needs `out` with rows of N (a multiple of 4) elements");
+    const int rc2 = moe_check_down("tgis_moe_gemm_down", expert_w, T, N, top_k, form, out, ldo);
+    if (rc2 != TGIS_OK) return rc2;
     if (T == 0) return TGIS_OK;
     TGIS_CHECK_ARG(scratch && ((uintptr_t)scratch % 16) == 0 && scratch_bytes >= tgis_moe_gemm_down_bytes(T, N, top_k, form),
                    "tgis_moe_gemm_down: scratch too small (%ld < %ld)", (long)scratch_bytes,
@@ -352,7 +495,7 @@ extern "C" int tgis_moe_gemm_down(const void* h, int64_t ldh, const void* images
     TgisTimedScope timed(TGIS_OP_DENSE_GEMM, st);
     return by_dtype(dtype, [&](auto t) {
         using T_ = type_of<decltype(t)>;
-        hipLaunchKernelGGL((moe_gemm_kernel<T_, false>), dim3((unsigned)a.NT, (unsigned)E), dim3(MOE_THREADS), 0, st, a);
+        hipLaunchKernelGGL((moe_gemm_kernel<T_, false, DenseSource<T_>>), dim3((unsigned)a.NT, (unsigned)E), dim3(MOE_THREADS), 0, st, a);
         TGIS_CHECK_LAUNCH();
         if (form == 1) {
             const int64_t work = T * (N / 4);
@@ -362,6 +505,35 @@ extern "C" int tgis_moe_gemm_down(const void* h, int64_t ldh, const void* images
         }
         return TGIS_OK;
     });
+}
+
+extern "C" int tgis_moe_gptq_gemm_down(const void* h, int64_t ldh, const void* images, int64_t expert_stride,
+                                       const int32_t* offsets, const int32_t* slot_rows, const float* expert_w, int64_t T,
+                                       int64_t K, int64_t N, int64_t groups, int E, int top_k, int dtype, int form, float* scratch,
+                                       int64_t scratch_bytes, void* out, int64_t ldo, void* stream) {
+    int rc = moe_check_gptq_shape("tgis_moe_gptq_gemm_down", K, N, groups, dtype);
+    if (rc != TGIS_OK) return rc;
+    rc = moe_check_gemm("tgis_moe_gptq_gemm_down", h, ldh, images, expert_stride, offsets, slot_rows, T, K, N, E, top_k, dtype, groups);
+    if (rc != TGIS_OK) return rc;
+    rc = moe_check_down("tgis_moe_gptq_gemm_down", expert_w, T, N, top_k, form, out, ldo);
+    if (rc != TGIS_OK) return rc;
+    if (T == 0) return TGIS_OK;
+    TGIS_CHECK_ARG(scratch && ((uintptr_t)scratch % 16) == 0 && scratch_bytes >= tgis_moe_gemm_down_bytes(T, N, top_k, form),
+                   "tgis_moe_gptq_gemm_down: scratch too small (%ld < %ld)", (long)scratch_bytes,
+                   (long)tgis_moe_gemm_down_bytes(T, N, top_k, form));
+    hipStream_t st = (hipStream_t)stream;
+    MoeArgs a;
+    moe_fill(a, h, ldh, images, expert_stride, offsets, slot_rows, expert_w, scratch, N, K, N, top_k, form);  // (N % 32 == 0)
+    moe_fill_gptq(a, K, N, groups);
+    TgisTimedScope timed(TGIS_OP_GPTQ_GEMM, st);
+    hipLaunchKernelGGL((moe_gemm_kernel<f16, false, Int4Source>), dim3((unsigned)a.NT, (unsigned)E), dim3(MOE_THREADS), 0, st, a);
+    TGIS_CHECK_LAUNCH();
+    if (form == 1) {
+        hipLaunchKernelGGL(moe_combine_kernel<f16>, dim3((unsigned)cdiv64(T * (N / 4), 256)), dim3(256), 0, st, scratch, (f16*)out,
+                           ldo, T, (int)N, top_k);
+        TGIS_CHECK_LAUNCH();
+    }
+    return TGIS_OK;
 }
 
 // The launch plan of the expert GEMMs without a launch (host-only debug export, kept out of include/tgis_hip.h like
@@ -381,5 +553,18 @@ extern "C" int tgis_debug_moe_plan(int which, int64_t T, int64_t K, int64_t N, i
     info[9] = which == 2 ? (int)cdiv64(T * (N / 4), 256) : 0;
     const int64_t bytes = which == 0 ? 0 : tgis_moe_gemm_down_bytes(T, N, top_k, which - 1);
     info[10] = (int)(bytes & 0x7fffffff), info[11] = (int)(bytes >> 31);
+    return TGIS_OK;
+}
+
+// The same for the int4 entry points (G groups): tgis_debug_moe_plan's info with info[5] the int4 ring and, in addition,
+//   12 bytes between expert images, tgis_gptq_prepared_bytes (low 31 bits)   13 those bytes >> 31
+extern "C" int tgis_debug_moe_gptq_plan(int which, int64_t T, int64_t K, int64_t N, int64_t G, int E, int top_k, int* info) {
+    int rc = tgis_debug_moe_plan(which, T, K, N, E, top_k, info);
+    if (rc != TGIS_OK) return rc;
+    rc = moe_check_gptq_shape("tgis_debug_moe_gptq_plan", K, N, G, TGIS_F16);
+    if (rc != TGIS_OK) return rc;
+    const int64_t stride = gptq::prep_layout(K, N, G).total;
+    info[5] = MOE_GPTQ_RING;
+    info[12] = (int)(stride & 0x7fffffff), info[13] = (int)(stride >> 31);
     return TGIS_OK;
 }

@@ -109,9 +109,13 @@ class MixtralConfig:
         self.pad_token_id, self.bos_token_id, self.eos_token_id = None, 1, 2
 
 
-def mixtral_tensors(config, seed: int, device="cpu", dtype=torch.bfloat16, head_scale: float = 1.0) -> Dict[str, torch.Tensor]:
+def mixtral_tensors(config, seed: int, device="cpu", dtype=torch.bfloat16, head_scale: float = 1.0,
+                    quantize: Optional[str] = None, groupsize: int = 128) -> Dict[str, torch.Tensor]:
     """Seeded full Mixtral checkpoint under the published names (block_sparse_moe.gate, experts.N.w1 / w3 / w2 = gate, up,
-    down): N(0, 1/sqrt(fan_in)) linears, so that the router's logits spread over the experts, unit RMSNorms."""
+    down): N(0, 1/sqrt(fan_in)) linears, so that the router's logits spread over the experts, unit RMSNorms.
+    quantize="gptq": q/k/v/o and every expert's w1 / w3 / w2 as 4-bit qweight / qzeros / scales / g_idx (_random_gptq); the
+    router and the head stay dense, as AutoGPTQ leaves them."""
+    assert quantize in (None, "gptq"), quantize
     g = torch.Generator(device=device).manual_seed(seed)
     E, I, V = config.hidden_size, config.intermediate_size, config.vocab_size
     D = getattr(config, "head_dim", None) or E // config.num_attention_heads
@@ -121,18 +125,24 @@ def mixtral_tensors(config, seed: int, device="cpu", dtype=torch.bfloat16, head_
     def lin(name, n, k, scale=1.0):
         t[f"{name}.weight"] = (torch.randn(n, k, generator=g, device=device) * (k ** -0.5 * scale)).to(dtype)
 
+    def qlin(name, n, k):
+        if quantize == "gptq":
+            _random_gptq(t, name, n, k, g, device, groupsize, 4)
+        else:
+            lin(name, n, k)
+
     t["model.embed_tokens.weight"] = torch.randn(V, E, generator=g, device=device).to(dtype)
     for i in range(config.num_hidden_layers):
         p = f"model.layers.{i}"
-        lin(f"{p}.self_attn.q_proj", H * D, E)
-        lin(f"{p}.self_attn.k_proj", Hkv * D, E)
-        lin(f"{p}.self_attn.v_proj", Hkv * D, E)
-        lin(f"{p}.self_attn.o_proj", E, H * D)
+        qlin(f"{p}.self_attn.q_proj", H * D, E)
+        qlin(f"{p}.self_attn.k_proj", Hkv * D, E)
+        qlin(f"{p}.self_attn.v_proj", Hkv * D, E)
+        qlin(f"{p}.self_attn.o_proj", E, H * D)
         lin(f"{p}.block_sparse_moe.gate", config.num_local_experts, E)
         for e in range(config.num_local_experts):
-            lin(f"{p}.block_sparse_moe.experts.{e}.w1", I, E)
-            lin(f"{p}.block_sparse_moe.experts.{e}.w3", I, E)
-            lin(f"{p}.block_sparse_moe.experts.{e}.w2", E, I)
+            qlin(f"{p}.block_sparse_moe.experts.{e}.w1", I, E)
+            qlin(f"{p}.block_sparse_moe.experts.{e}.w3", I, E)
+            qlin(f"{p}.block_sparse_moe.experts.{e}.w2", E, I)
         t[f"{p}.input_layernorm.weight"] = torch.ones(E, device=device, dtype=dtype)
         t[f"{p}.post_attention_layernorm.weight"] = torch.ones(E, device=device, dtype=dtype)
     t["model.norm.weight"] = torch.ones(E, device=device, dtype=dtype)

@@ -9,7 +9,12 @@ One forward of the block is four launches — router GEMM, route, up, down — t
 captured decode or verify step holds them.  The same function has a second implementation, the loop path: one host read of
 the expert counts, then for each expert that was hit index_select, the dense act 2 and plain GEMMs on that expert's image,
 a scale and index_add_ in fp32.  Captured steps always take the kernels; an eager forward takes them up to
-MOE_FUSED_MAX_TOKENS tokens and the loop above (TGIS_MOE_PATH=fused / loop forces either on eager forwards).
+MOE_FUSED_MAX_TOKENS tokens (MOE_GPTQ_FUSED_MAX_TOKENS for GPTQ experts) and the loop above (TGIS_MOE_PATH=fused / loop
+forces either on eager forwards).
+
+GPTQ checkpoints (4 bits, one group or groups of 64 * 2^n rows, no act-order; q/k/v/o as Llama's): every expert's w1 | w3 and
+w2 are int4 images (native.MoeGptqWeights) and the block takes native.moe_gptq_gemm_up / _down, the same kernel over another
+weight source; its loop path runs gptq_gemm(act=2) and gptq_gemm on views of the same images.  The router stays 16-bit.
 
 Tensor parallelism: every expert's intermediate size is split across ranks (w1 and w3 by rows, w2 by columns, as Llama's
 MLP), the router is replicated, and the block's output is all-reduced once."""
@@ -28,6 +33,11 @@ from tgis_amd.utils.layers import DEFER_REDUCE, TensorParallelEmbedding, TensorP
 # (profiles/mixtral_bench.jsonl): the kernels win at 64 rows (0.50 against 0.81 ms) and lose at 128
 # (0.86 against 0.79 ms) — they re-read an expert's weights once per 32 of its rows, the loop's GEMMs once per 64.
 MOE_FUSED_MAX_TOKENS = int(os.getenv("TGIS_MOE_FUSED_MAX_TOKENS", "64"))
+# the same threshold for GPTQ experts.  It differs because the int4 crossover does: on the same shapes
+# (profiles/mixtral_gptq_bench.jsonl) the int4 kernels still win at 128 rows (0.48 against 0.55 - 0.66 ms for the loop, whose
+# per-expert gptq_gemm launches and host read cost what they cost at f16 while the kernels read a quarter of the bytes) and
+# lose at 256 (0.93 against 0.76 ms).
+MOE_GPTQ_FUSED_MAX_TOKENS = int(os.getenv("TGIS_MOE_GPTQ_FUSED_MAX_TOKENS", "128"))
 
 
 def moe_path_override():
@@ -38,12 +48,36 @@ def moe_path_override():
     return None if v == "auto" else v
 
 
-def check_mixtral_config(config, quantize=None):
-    """(E, top_k) of a Mixtral config, or the refusal: GPTQ, another activation, expert counts the route kernel has no
-    form for.  Called before any weight is read."""
+def gptq_params_of(weights):
+    """(bits, group size) of a GPTQ checkpoint as its weights object knows them before any weight is read, or None."""
+    get = getattr(weights, "_get_gptq_params", None)
+    if get is None:
+        return None
+    try:
+        bits, groupsize = get()
+    except (RuntimeError, AttributeError, TypeError):
+        return None
+    return (bits, groupsize) if isinstance(bits, int) and isinstance(groupsize, int) else None
+
+
+def refuse_gptq(what: str):
+    raise NotImplementedError(f"Mixtral: GPTQ checkpoints are served at 4 bits, one group or groups of 64 * 2^n rows, "
+                              f"without act-order, under the published tensor names: {what}")
+
+
+def check_mixtral_config(config, quantize=None, gptq_params=None):
+    """(E, top_k) of a Mixtral config, or the refusal: a GPTQ form without a kernel, another activation, expert counts the
+    route kernel has no form for.  Called before any weight is read; gptq_params = (bits, group size) of a GPTQ checkpoint
+    (gptq_params_of), None when they are not known."""
     if quantize == "gptq":
-        raise NotImplementedError("Mixtral is served from f16 / bf16 expert weights: GPTQ Mixtral checkpoints have no kernel")
-    if quantize is not None:
+        if gptq_params is None:
+            refuse_gptq("the bits and group size of this checkpoint are not known")
+        bits, groupsize = gptq_params
+        if bits != 4:
+            refuse_gptq(f"{bits}-bit experts have no kernel")
+        if not native.moe_gptq_group_ok(groupsize):
+            refuse_gptq(f"groups of {groupsize} rows have no form in the expert kernels")
+    elif quantize is not None:
         raise NotImplementedError(f"Mixtral: quantization `{quantize}` is not implemented")
     act = getattr(config, "hidden_act", None)
     if act != "silu":
@@ -61,8 +95,8 @@ class ExpertTensors:
       fused       {prefix}.mlp.gate.weight, ...mlp.experts.gate_up_proj [E, 2 I, hidden], ...mlp.experts.down_proj [E, hidden, I]
                   (transformers >= 5 in memory; what it saves carries the published names again)."""
 
-    def __init__(self, prefix: str, weights, I: int):
-        self.weights, self.I = weights, I
+    def __init__(self, prefix: str, weights, I: int, quantize=None):
+        self.weights, self.I, self.quantize = weights, I, quantize
         tp, self.rank = weights.process_group.size(), weights.process_group.rank()
         if I % tp != 0:
             raise ValueError(f"intermediate_size {I} must be divisible by the shard count {tp}")
@@ -71,6 +105,8 @@ class ExpertTensors:
         self.base = f"{prefix}.block_sparse_moe" if self.published else f"{prefix}.mlp"
         if not self.published and not weights.has(f"{self.base}.experts.gate_up_proj"):
             raise RuntimeError(f"weight {prefix}.block_sparse_moe.gate.weight does not exist (nor {self.base}.experts.gate_up_proj)")
+        if quantize == "gptq" and not self.published:
+            refuse_gptq(f"{self.base}.experts carries the fused in-memory names, which hold no GPTQ tensors")
         self._fused = {}
 
     def router(self) -> torch.Tensor:
@@ -99,16 +135,49 @@ class ExpertTensors:
         return w._finish(self._fused_full("down_proj")[e][:, lo:lo + self.Il])
 
 
+    def _gptq_bundle(self, name: str, bundle):
+        """(qweight, qzeros, scales, g_idx, bits, groupsize) of one expert matrix as Llama's MLP loader sliced (and, for a
+        row shard, regrouped) it, or the refusal of what the expert kernels have no form for, naming the tensor."""
+        qweight, qzeros, scales, g_idx, bits, groupsize = bundle[:6]
+        K, G = qweight.shape[0] * (32 // bits), qzeros.shape[0]
+        if bits != 4:
+            refuse_gptq(f"{name} holds {bits}-bit codes")
+        if g_idx is not None:
+            trivial = not isinstance(g_idx, tuple) and g_idx.numel() == K and K % G == 0
+            if trivial:
+                gi = g_idx.to("cpu", torch.int64)
+                trivial = torch.equal(gi, torch.arange(K) // (K // G)) or (G == 1 and not bool(gi.any()))
+            if not trivial:
+                refuse_gptq(f"{name} is an act-order matrix (its g_idx permutes the rows)")
+        if K % 64 != 0 or K % G != 0 or not native.moe_gptq_group_ok(K // G, K):
+            refuse_gptq(f"{name}: {K} rows per rank in {G} groups (the checkpoint's group size is {groupsize})")
+        return qweight, qzeros, scales, g_idx, bits, K // G
+
+    def gate_up_gptq(self, e: int):
+        """The GPTQ bundle of [w1 | w3]: this rank's columns of each, side by side (Llama's gate_up_proj read)."""
+        names = [f"{self.base}.experts.{e}.w1", f"{self.base}.experts.{e}.w3"]
+        return self._gptq_bundle(names[0] + " | w3", self.weights.get_multi_weights_col(names, "gptq", dim=1))
+
+    def down_gptq(self, e: int):
+        """The GPTQ bundle of w2: this rank's rows (Llama's down_proj read, regrouped when a group straddles the ranks)."""
+        name = f"{self.base}.experts.{e}.w2"
+        return self._gptq_bundle(name, self.weights.get_multi_weights_row(name, "gptq"))
+
+
 class ExpertWeights:
     """The expert weights of one layer as the kernels read them: the gate|up images and the down images of all experts
-    (native.MoeWeights: E calls of tgis_dense_prepare into one buffer each).  The checkpoint-layout tensors are released as
-    their images are made."""
+    (native.MoeWeights: E calls of tgis_dense_prepare into one buffer each; native.MoeGptqWeights and tgis_gptq_prepare for
+    a GPTQ checkpoint).  The checkpoint-layout tensors are released as their images are made."""
 
     def __init__(self, tensors: ExpertTensors, E: int):
         if tensors.Il % 16 != 0:
             raise NotImplementedError(f"Mixtral: intermediate size per rank ({tensors.Il}) must be a multiple of 16")
-        self.gate_up = native.MoeWeights(tensors.gate_up, E, gate_up=True)
-        self.down = native.MoeWeights(tensors.down, E)
+        if tensors.quantize == "gptq":
+            self.gate_up = native.MoeGptqWeights(tensors.gate_up_gptq, E, gate_up=True)
+            self.down = native.MoeGptqWeights(tensors.down_gptq, E)
+        else:
+            self.gate_up = native.MoeWeights(tensors.gate_up, E, gate_up=True)
+            self.down = native.MoeWeights(tensors.down, E)
         # one expert's images as dense weights (views): the loop path's operands
         self.gate_up_experts = [self.gate_up.expert(e) for e in range(E)]
         self.down_experts = [self.down.expert(e) for e in range(E)]
@@ -116,12 +185,13 @@ class ExpertWeights:
 
 class MixtralSparseMoe:
     def __init__(self, prefix: str, config, weights):
-        self.E, self.top_k = check_mixtral_config(config, getattr(config, "quantize", None))
+        self.quantize = getattr(config, "quantize", None)
+        self.E, self.top_k = check_mixtral_config(config, self.quantize, gptq_params_of(weights))
         self.hidden = config.hidden_size
         if self.hidden % 8 != 0:
             raise NotImplementedError(f"Mixtral: hidden_size {self.hidden} must be a multiple of 8")
         self.process_group = weights.process_group
-        tensors = ExpertTensors(prefix, weights, config.intermediate_size)
+        tensors = ExpertTensors(prefix, weights, config.intermediate_size, self.quantize)
         self.router = native.DenseWeight(tensors.router().contiguous())  # replicated
         assert (self.router.N, self.router.K) == (self.E, self.hidden)
         self.experts = ExpertWeights(tensors, self.E)
@@ -132,6 +202,9 @@ class MixtralSparseMoe:
         return native.moe_route(logits, self.top_k)
 
     def fused(self, x: torch.Tensor, r: native.Routing, partial: bool):
+        if self.quantize == "gptq":
+            h = native.moe_gptq_gemm_up(x, self.experts.gate_up, r)
+            return native.moe_gptq_gemm_down(h, self.experts.down, r, partial=partial)
         h = native.moe_gemm_up(x, self.experts.gate_up, r)
         return native.moe_gemm_down(h, self.experts.down, r, partial=partial)
 
@@ -147,8 +220,12 @@ class MixtralSparseMoe:
                 continue
             slots = r.slot_rows[offsets[e]:offsets[e + 1]].long()
             tokens = torch.div(slots, k, rounding_mode="floor")  # (distinct inside one expert: the adds below never collide)
-            h = native.dense_gemm(x.index_select(0, tokens), self.experts.gate_up_experts[e], ws, act=2)
-            y = native.dense_gemm(h, self.experts.down_experts[e], ws, out_f32=True)
+            if self.quantize == "gptq":  # the int4 GEMM leaves f16: scaled and added in fp32 all the same
+                h = native.gptq_gemm(x.index_select(0, tokens), self.experts.gate_up_experts[e], ws, act=2)
+                y = native.gptq_gemm(h, self.experts.down_experts[e], ws).float()
+            else:
+                h = native.dense_gemm(x.index_select(0, tokens), self.experts.gate_up_experts[e], ws, act=2)
+                y = native.dense_gemm(h, self.experts.down_experts[e], ws, out_f32=True)
             out.index_add_(0, tokens, y * flat_w.index_select(0, slots).unsqueeze(1))
         return out.to(x.dtype)
 
@@ -157,7 +234,7 @@ class MixtralSparseMoe:
         next add + RMSNorm finishes."""
         T = x.shape[0]
         tp = self.process_group.size()
-        use_fused = T <= MOE_FUSED_MAX_TOKENS
+        use_fused = T <= (MOE_GPTQ_FUSED_MAX_TOKENS if self.quantize == "gptq" else MOE_FUSED_MAX_TOKENS)
         if torch.cuda.is_current_stream_capturing():
             use_fused = True  # a captured step cannot read the routing
         else:
@@ -228,7 +305,7 @@ class FlashMixtralModel:
 
 class FlashMixtralForCausalLM(FlashForCausalLM):
     def __init__(self, config, weights):
-        check_mixtral_config(config, getattr(config, "quantize", None))  # before any weight is read
+        check_mixtral_config(config, getattr(config, "quantize", None), gptq_params_of(weights))  # before any weight is read
         if not hasattr(config, "num_key_value_heads") or config.num_key_value_heads is None:
             config.num_key_value_heads = config.num_attention_heads
         self.config = config

@@ -78,6 +78,10 @@ SIGNATURES = {
     "tgis_moe_gemm_down_bytes": (_c_i64, [_c_i64, _c_i64, _c_int, _c_int]),
     "tgis_moe_gemm_down": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int,
                                     _c_int, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "tgis_moe_gptq_gemm_up": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int,
+                                       _c_int, _c_int, _vp]),
+    "tgis_moe_gptq_gemm_down": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int,
+                                         _c_int, _c_int, _vp, _c_i64, _vp, _c_i64, _vp]),
     "tgis_rmsnorm_residual":(_c_int, [_vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_f, _c_int, _vp]),
     "tgis_rmsnorm_residual_partial": (_c_int, [_vp, _c_int, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_f,
                                                _c_int, _vp]),
@@ -727,6 +731,91 @@ def moe_gemm_down(h: torch.Tensor, w: MoeWeights, r: Routing, partial: bool = Fa
     p = Partial(scratch, r.top_k, (w.N + 31) // 32 * 32, r.T, w.N, None)
     p.dtype = w.dtype
     return p
+
+
+# group sizes the int4 expert kernels have a form for (rows per group; a single group, written -1 or K, is served too)
+MOE_GPTQ_GROUP_SIZES = tuple(64 << n for n in range(9))
+
+
+def moe_gptq_group_ok(groupsize: int, K: Optional[int] = None) -> bool:
+    """Whether tgis_moe_gptq_gemm_* serve this group size: one group (-1, or the whole K), or 64 * 2^n rows dividing K."""
+    if groupsize == -1 or (K is not None and groupsize == K):
+        return True
+    return groupsize in MOE_GPTQ_GROUP_SIZES and (K is None or K % groupsize == 0)
+
+
+class MoeGptqWeights:
+    """The int4 twin of MoeWeights: E images of tgis_gptq_prepare in one [E, stride] buffer.  `expert_bundle(e)` returns expert
+    e's (qweight, qzeros, scales, g_idx, bits, groupsize) on the GPU; the bundle is dropped as soon as its image is made.
+    gate_up=True: the columns are [gate | up] (w1 | w3) and the image interleaves the pairs (flags bit 0)."""
+
+    def __init__(self, expert_bundle, E: int, gate_up: bool = False):
+        lib = load_library()
+        self.E, self.flags = E, (1 if gate_up else 0)
+        self.dtype = torch.float16
+        self.image = None
+        for e in range(E):
+            qweight, qzeros, scales, g_idx, bits, groupsize = expert_bundle(e)[:6]
+            if bits != 4:
+                raise TgisHipError(f"Mixtral expert {e}: GPTQ experts are served at 4 bits, not {bits}")
+            K, N, G = qweight.shape[0] * 8, qweight.shape[1], qzeros.shape[0]
+            if K % 64 or N % 32:
+                raise TgisHipError(f"Mixtral expert {e}: int4 expert matrices need K % 64 == 0 and N % 32 == 0, got K {K}, N {N}")
+            if K % G or not moe_gptq_group_ok(K // G, K):
+                raise TgisHipError(f"Mixtral expert {e}: the int4 expert kernels have no form for groups of "
+                                   f"{K // G if K % G == 0 else groupsize} rows (one group, or 64 * 2^n rows)")
+            if g_idx is not None:
+                if isinstance(g_idx, tuple) or g_idx.numel() != K:
+                    raise TgisHipError(f"Mixtral expert {e}: act-order (permuted) GPTQ experts are not served")
+                gi = g_idx.to("cpu", torch.int64)
+                if not (torch.equal(gi, torch.arange(K) // (K // G)) or (G == 1 and not bool(gi.any()))):
+                    raise TgisHipError(f"Mixtral expert {e}: act-order GPTQ experts (a non-trivial g_idx) are not served")
+            if self.image is None:
+                self.K, self.N, self.groups = K, N, G
+                self.stride = lib.tgis_gptq_prepared_bytes(K, N, G)
+                self.image = torch.empty((E, self.stride), dtype=torch.uint8, device=qweight.device)
+            assert (K, N, G) == (self.K, self.N, self.groups), "every expert of a layer has the same quantised shape"
+            _check(lib.tgis_gptq_prepare(_ptr(qweight.contiguous()), _ptr(qzeros.contiguous()),
+                                         _ptr(scales.to(torch.float16).contiguous()), None, None, K, N, G, self.flags,
+                                         _ptr(self.image[e]), _stream()), "tgis_gptq_prepare")
+            torch.cuda.current_stream().synchronize()  # (the bundle goes out of scope here)
+
+    def expert(self, e: int) -> GptqWeight:
+        """Expert e's image as a GptqWeight (a view, nothing is copied): what gptq_gemm takes on the loop path."""
+        w = GptqWeight.__new__(GptqWeight)
+        w.K, w.N, w.groups, w.flags, w.image = self.K, self.N, self.groups, self.flags, self.image[e]
+        w.answers, w.partial_plan, w.perm, w.in_features = {}, {}, None, self.K
+        return w
+
+
+def moe_gptq_gemm_up(x: torch.Tensor, w: MoeGptqWeights, r: Routing, out=None) -> torch.Tensor:
+    """moe_gemm_up over int4 expert images: h [T top_k, I] in f16."""
+    assert x.dim() == 2 and x.stride(1) == 1 and x.shape == (r.T, w.K) and w.flags & 1 and w.E == r.E
+    if out is None:
+        out = torch.empty((r.T * r.top_k, w.N // 2), dtype=x.dtype, device=x.device)
+    _check(load_library().tgis_moe_gptq_gemm_up(_ptr(x), x.stride(0), _ptr(w.image), w.stride, _ptr(r.offsets),
+                                                _ptr(r.slot_rows), _ptr(out), out.stride(0), r.T, w.K, w.N, w.groups, w.E,
+                                                r.top_k, dtype_code(x.dtype), _stream()), "tgis_moe_gptq_gemm_up")
+    return out
+
+
+def moe_gptq_gemm_down(h: torch.Tensor, w: MoeGptqWeights, r: Routing, partial: bool = False):
+    """moe_gemm_down over int4 expert images: a Partial with S = top_k (partial, T <= PARTIAL_MAX_M) or the finished f16
+    [T, hidden] tensor."""
+    assert h.dim() == 2 and h.stride(1) == 1 and h.shape == (r.T * r.top_k, w.K)
+    assert not (w.flags & 1) and w.E == r.E
+    lib = load_library()
+    form = 0 if partial else 1
+    assert not partial or r.T <= PARTIAL_MAX_M
+    nbytes = lib.tgis_moe_gemm_down_bytes(r.T, w.N, r.top_k, form)
+    scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=h.device)
+    out = None if partial else torch.empty((r.T, w.N), dtype=h.dtype, device=h.device)
+    _check(lib.tgis_moe_gptq_gemm_down(_ptr(h), h.stride(0), _ptr(w.image), w.stride, _ptr(r.offsets), _ptr(r.slot_rows),
+                                       _ptr(r.expert_w), r.T, w.K, w.N, w.groups, w.E, r.top_k, dtype_code(h.dtype), form,
+                                       _ptr(scratch), nbytes, _ptr(out), w.N, _stream()), "tgis_moe_gptq_gemm_down")
+    if not partial:
+        return out
+    return Partial(scratch, r.top_k, w.N, r.T, w.N, None)
 
 
 def clear_error() -> None:

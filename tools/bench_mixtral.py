@@ -12,7 +12,16 @@ mean context 1024.  One JSON line per configuration (keep them under profiles/):
 
 Both sides of every comparison run in this one process on one device, after a warm-up, as medians.
 
-    python tools/bench_mixtral.py [--layers 8 --steps 32 --warmup 3 --blocks 3 --dtypes bf16,f16 --batches 1,8,32]"""
+    python tools/bench_mixtral.py [--layers 8 --steps 32 --warmup 3 --blocks 3 --dtypes bf16,f16 --batches 1,8,32]
+
+--quantize gptq: the same rows for a synthetic int4 GPTQ checkpoint (4 bits, group size 128, f16: q/k/v/o and the experts
+quantised, router and head dense) AND, first, for the f16 model it is compared with, in the same run; every line carries
+"quantize".  The roofline counts the bytes the int4 kernels read: half a byte per weight plus 4 bytes per (group, column).
+Keep the lines in profiles/mixtral_gptq_bench.jsonl.  --moe-tokens 64,128,256 replaces the row counts of the "moe" lines (the
+crossover behind MOE_FUSED_MAX_TOKENS); --ring N loads lib/libtgis_hip_ring<N>.so, a library built with another int4 weight
+ring (TGIS_LIB_SUFFIX=_ring<N> tools/build.sh -DTGIS_MOE_GPTQ_RING=<N>), for the sweep of DESIGN.md section 6.
+
+    python tools/bench_mixtral.py --quantize gptq [--skip-steps] [--moe-tokens 1,8,32] [--ring 16]"""
 import argparse
 import json
 import os
@@ -47,6 +56,11 @@ def timed_ms(fn, iters, rounds=5):
     return statistics.median(out)
 
 
+def weight_bytes(K, N, quantize, groupsize=128):
+    """Bytes a GEMM reads of a [K, N] weight: 2 per element, or the int4 image's nibbles and {scale, zero} pairs."""
+    return K * N // 2 + (K // groupsize) * N * 4 if quantize == "gptq" else K * N * 2
+
+
 def moe_alone(moe, T, dtype, device, seed):
     """One layer's routed block at T rows: each launch alone, the four together, and the loop path."""
     from tgis_amd import native
@@ -57,21 +71,23 @@ def moe_alone(moe, T, dtype, device, seed):
     ws = workspace(device)
     logits = native.dense_gemm(x, moe.router, ws, out_f32=True)
     r = native.moe_route(logits, moe.top_k)
-    h = native.moe_gemm_up(x, moe.experts.gate_up, r)
+    up, down = ((native.moe_gptq_gemm_up, native.moe_gptq_gemm_down) if moe.quantize == "gptq" else
+                (native.moe_gemm_up, native.moe_gemm_down))
+    h = up(x, moe.experts.gate_up, r)
     partial = T <= native.PARTIAL_MAX_M
     iters = 20 if T <= 64 else 5
     hit = int((r.counts > 0).sum())
     res = {
-        "kind": "moe", "rows": T, "dtype": str(dtype).replace("torch.", ""), "experts_hit": hit,
+        "kind": "moe", "rows": T, "dtype": str(dtype).replace("torch.", ""), "quantize": moe.quantize, "experts_hit": hit,
         "down_form": "slabs" if partial else "finished",
         "router_gemm_ms": timed_ms(lambda: native.dense_gemm(x, moe.router, ws, out_f32=True), iters),
         "route_ms": timed_ms(lambda: native.moe_route(logits, moe.top_k), iters),
-        "up_ms": timed_ms(lambda: native.moe_gemm_up(x, moe.experts.gate_up, r), iters),
-        "down_ms": timed_ms(lambda: native.moe_gemm_down(h, moe.experts.down, r, partial=partial), iters),
+        "up_ms": timed_ms(lambda: up(x, moe.experts.gate_up, r), iters),
+        "down_ms": timed_ms(lambda: down(h, moe.experts.down, r, partial=partial), iters),
         "fused_ms": timed_ms(lambda: moe.fused(x, moe.route(x), partial), iters),
         "loop_ms": timed_ms(lambda: moe.loop(x, moe.route(x)), iters),
     }
-    expert_bytes = hit * 3 * moe.hidden * moe.experts.down.K * 2
+    expert_bytes = hit * 3 * weight_bytes(moe.hidden, moe.experts.down.K, moe.quantize)
     res["expert_weight_bytes_hit"] = expert_bytes
     res["fused_frac_of_hbm_peak"] = round(expert_bytes / HBM_PEAK * 1e3 / res["fused_ms"], 4)
     return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in res.items()}
@@ -107,7 +123,18 @@ def main():
     ap.add_argument("--dtypes", default="bf16,f16")
     ap.add_argument("--batches", default="1,8,32")
     ap.add_argument("--skip-moe", action="store_true", help="only the decode steps")
+    ap.add_argument("--skip-steps", action="store_true", help="only the routed block alone")
+    ap.add_argument("--quantize", default=None, choices=("gptq",),
+                    help="f16 only: the f16 model, then the synthetic int4 GPTQ model (group size 128), in one run")
+    ap.add_argument("--moe-tokens", default=None, help="row counts of the routed block alone, e.g. 64,128,256")
+    ap.add_argument("--ring", type=int, default=None, choices=(4, 8, 16),
+                    help="load lib/libtgis_hip_ring<N>.so: the library built with an int4 weight ring of N k64-steps")
     args = ap.parse_args()
+    if args.ring is not None:  # before tgis_amd.native is imported: it reads TGIS_HIP_LIB once
+        lib = os.path.join(ROOT, "text-generation-inference_amd", "lib", f"libtgis_hip_ring{args.ring}.so")
+        if not os.path.exists(lib):
+            sys.exit(f"{lib} not found: TGIS_LIB_SUFFIX=_ring{args.ring} tools/build.sh -DTGIS_MOE_GPTQ_RING={args.ring}")
+        os.environ["TGIS_HIP_LIB"] = lib
 
     from tgis_amd.inference_engine.synthetic import InferenceEngine, MixtralConfig, mixtral_tensors
     from tgis_amd.models.custom_modeling import flash_mixtral_modeling as fm
@@ -121,21 +148,34 @@ def main():
     batches = [int(b) for b in args.batches.split(",")]
     L_in = max(1, args.ctx - W - K // 2 - 1)
     total_len = L_in + W + K + 10
-    for name in args.dtypes.split(","):
+    moe_rows = MOE_ROWS if args.moe_tokens is None else tuple(int(t) for t in args.moe_tokens.split(","))
+    configs = [(name, None) for name in args.dtypes.split(",")] if args.quantize is None else [("f16", None), ("f16", "gptq")]
+    ring = None
+    if args.quantize is not None:
+        import ctypes
+
+        from tgis_amd import native
+
+        info = (ctypes.c_int * 16)()
+        native.load_library().tgis_debug_moe_gptq_plan(0, 1, 4096, 64, 32, 8, 2, info)
+        ring = info[5]
+        assert args.ring in (None, ring), f"the loaded library's int4 ring is {ring}, not {args.ring}"
+    for name, quantize in configs:
         dtype = {"bf16": torch.bfloat16, "f16": torch.float16}[name]
         cfg = MixtralConfig(num_hidden_layers=args.layers)
         tok = SyntheticTokenizer(cfg.vocab_size)
-        tensors = mixtral_tensors(cfg, seed=1234, device=device, dtype=dtype)
-        eng = InferenceEngine(tensors, cfg, dtype, None, tokenizer=tok)
+        tensors = mixtral_tensors(cfg, seed=1234, device=device, dtype=dtype, quantize=quantize)
+        eng = InferenceEngine(tensors, cfg, dtype, quantize, tokenizer=tok, gptq_groupsize=128)
         tensors.clear()
         del tensors
-        lm = FlashCausalLM("synthetic", None, "synthetic", dtype, None, engine=eng,
+        lm = FlashCausalLM("synthetic", None, "synthetic", dtype, quantize, engine=eng,
                            kv_cache_pages=max(batches) * PagedKVCache.pages_for(total_len) + 8)
         torch.cuda.empty_cache()
         E, I, L, H = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers, cfg.num_attention_heads
         Hkv, D = cfg.num_key_value_heads, cfg.hidden_size // cfg.num_attention_heads
-        dense_bytes = (L * ((H + 2 * Hkv) * D * E + E * H * D + cfg.num_local_experts * E) + cfg.vocab_size * E) * 2
-        for B in batches:
+        dense_bytes = (L * (weight_bytes(E, (H + 2 * Hkv) * D, quantize) + weight_bytes(H * D, E, quantize)
+                            + cfg.num_local_experts * E * 2) + cfg.vocab_size * E * 2)
+        for B in ([] if args.skip_steps else batches):
             blocks = []
             with lm.context_manager():
                 batch = None
@@ -158,15 +198,15 @@ def main():
                 batch.release()
             ms = statistics.median(blocks)
             ctx_mean = L_in + W + (K + 1) / 2
-            expert_bytes = int(L * hit * 3 * E * I * 2)
+            expert_bytes = int(L * hit * 3 * weight_bytes(E, I, quantize))
             kv_bytes = int(L * 2 * Hkv * D * 2 * B * ctx_mean)
             roof_ms = (dense_bytes + expert_bytes + kv_bytes) / HBM_PEAK * 1e3
             print(json.dumps({
                 "kind": "step", "metric": f"decode ms per step (Mixtral-8x7B layer shapes, {L} layers, {name})",
-                "dtype": name, "layers": L, "batch": B, "mean_ctx": ctx_mean, "steps": K, "warmup": W,
+                "dtype": name, "quantize": quantize, "int4_ring": ring, "layers": L, "batch": B, "mean_ctx": ctx_mean, "steps": K, "warmup": W,
                 "ms_per_step": round(ms, 4), "ms_per_step_blocks": [round(b, 4) for b in blocks],
                 "tokens_per_s": round(B / ms * 1e3, 2), "hip_graph": bool(lm.use_graphs),
-                "experts_hit_per_layer": round(hit, 3), "moe_fused_max_tokens": fm.MOE_FUSED_MAX_TOKENS,
+                "experts_hit_per_layer": round(hit, 3), "moe_fused_max_tokens": fm.MOE_GPTQ_FUSED_MAX_TOKENS if quantize == "gptq" else fm.MOE_FUSED_MAX_TOKENS,
                 "step_roofline": {"dense_weight_bytes": dense_bytes, "expert_weight_bytes_hit": expert_bytes,
                                   "kv_read_bytes": kv_bytes, "ms_at_hbm_peak": round(roof_ms, 4),
                                   "frac_of_hbm_peak": round(roof_ms / ms, 4)},
@@ -174,8 +214,8 @@ def main():
             }), flush=True)
         if not args.skip_moe:
             moe = lm.model.model.layers[0].moe
-            for T in MOE_ROWS:
-                print(json.dumps(moe_alone(moe, T, dtype, device, seed=T)), flush=True)
+            for T in moe_rows:
+                print(json.dumps(dict(moe_alone(moe, T, dtype, device, seed=T), int4_ring=ring)), flush=True)
         del lm, eng
         torch.cuda.empty_cache()
 
