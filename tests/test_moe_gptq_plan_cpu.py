@@ -6,6 +6,7 @@ import ctypes
 
 import pytest
 
+from tests import moe_cases as mc
 from tests import moe_gptq_cases as gc
 
 
@@ -23,9 +24,9 @@ def lib():
     return lib
 
 
-def _plan(lib, which, T, K, N, G):
+def _plan(lib, which, T, K, N, G, E=gc.E, top_k=gc.TOP_K):
     info = (ctypes.c_int * 16)()
-    rc = lib.tgis_debug_moe_gptq_plan(which, T, K, N, G, gc.E, gc.TOP_K, info)
+    rc = lib.tgis_debug_moe_gptq_plan(which, T, K, N, G, E, top_k, info)
     return rc, list(info)
 
 
@@ -44,6 +45,20 @@ def test_plan_equals_the_restatement(lib, K, N, gs):
             assert info[14:] == [0, 0]
     # the stride is tgis_gptq_prepared_bytes, which is what MoeGptqWeights allocates per expert
     assert lib.tgis_gptq_prepared_bytes(K, N, G) == gc.prepared_bytes(K, N, G)
+
+
+def test_plan_of_every_edge_launch_equals_the_restatement(lib):
+    """Every launch of tests/test_moe_gptq_edges_gpu.py: group sizes 128 to 16384 at K up to 32768, (E, top_k) from (2, 1) to
+    (64, 8), the identity's 128 and 256 rows, the far images' five experts."""
+    cases = gc.edge_cases()
+    assert len(cases) == len(set(cases)) > 100
+    assert {c[5:] for c in cases} >= {(2, 1), (64, 8), (5, 2)} and {c[4] for c in cases} >= {1, 2, 3, 5, 28}
+    for which, T, K, N, G, E, top_k in cases:
+        rc, info = _plan(lib, which, T, K, N, G, E, top_k)
+        assert rc == 0, lib.tgis_last_error()
+        assert info[:14] == gc.plan(which, T, K, N, G, E, top_k), (which, T, K, N, G, E, top_k)
+        assert info[14:] == [0, 0]
+        assert info[4] == max(mc.k_parts(K)) and lib.tgis_gptq_prepared_bytes(K, N, G) == gc.prepared_bytes(K, N, G)
 
 
 def test_k_parts_of_the_gpu_cases(lib):
