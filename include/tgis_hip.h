@@ -287,6 +287,35 @@ int tgis_moe_gptq_gemm_down(const void* h, int64_t ldh, const void* images, int6
                             int E, int top_k, int dtype, int form, float* scratch, int64_t scratch_bytes, void* out,
                             int64_t ldo, void* stream);
 
+/* ---- per-request LoRA adapters (csrc/lora.hip) ----
+ * A wrapped linear computes y[t] = W x[t] + scale_s B_s (A_s x[t]) with s = slot[t]; a row with slot[t] = -1 keeps W x[t].
+ * Shared limits: 0 <= T <= 64 rows, 1 <= S <= 32 slots, 1 <= P <= 3 projections fused into the base linear, max_rank a
+ * multiple of 16 up to 64, dtype TGIS_F16 / TGIS_BF16, K % 8 == 0, N % 8 == 0; anything else is TGIS_EINVAL with a message,
+ * before the device is touched.  Nothing is read on the host, no float atomics: the same input gives the same bytes.
+ *
+ * Slot images of one linear (S of each, a fixed byte stride apart, at fixed addresses; an adapter is loaded by a
+ * stream-ordered copy), with ranks int32 [S] (0: the slot holds nothing for this linear) and scales f32 [S] (alpha / r):
+ *   A  [P][max_rank][K] row-major in the model dtype (tgis_lora_a_bytes), rows rank .. round_up(rank, 16) - 1 zero;
+ *   B  [max_rank / 16][N][16] in the model dtype (tgis_lora_b_bytes): granule g holds columns 16 g .. 16 g + 15 of
+ *      B [N, r], zero from column rank on.
+ * A step reads round_up(rank, 16) rows of A and as many columns of B of a slot that some row names, and nothing else. */
+int64_t tgis_lora_a_bytes(int64_t K, int P, int max_rank);
+int64_t tgis_lora_b_bytes(int64_t N, int max_rank);
+/* slot int32 [T] with values -1 .. S-1 -> counts int32 [S], offsets int32 [S + 1] (exclusive prefix sum) and rows int32 [T]:
+ * the rows that name a slot, grouped by slot and ascending inside each (offsets[S] of them).  Once per forward. */
+int tgis_lora_group(const int32_t* slot, int64_t T, int S, int32_t* counts, int32_t* offsets, int32_t* rows, void* stream);
+/* v[t, p, 0 .. round_up(rank_s, 16)) = A_s[p] x[t] in fp32 for every row t of the lists; v is fp32 [T, P, max_rank] and the
+ * rest of it is left alone.  x [T, K] in the model dtype, row stride ldx (a multiple of 8), 16-byte aligned. */
+int tgis_lora_shrink(const void* x, int64_t ldx, const void* a_images, int64_t a_stride, const int32_t* ranks,
+                     const int32_t* offsets, const int32_t* rows, float* v, int64_t T, int64_t K, int P, int S, int max_rank,
+                     int dtype, void* stream);
+/* y[t, n] = T(float(y[t, n]) + scale_s * sum_r v[t, p(n), r] B_s[n, r]) in place for every row t of the lists, r ascending
+ * in fp32; p(n) is the segment of n under the P + 1 column bounds (a host array: bounds[0] = 0 < ... < bounds[P] = N, all
+ * multiples of 8).  y [T, N] in the model dtype, row stride ldy.  Rows outside the lists are not touched. */
+int tgis_lora_expand(const float* v, const void* b_images, int64_t b_stride, const int32_t* ranks, const float* scales,
+                     const int32_t* offsets, const int32_t* rows, const int64_t* bounds, void* y, int64_t ldy, int64_t T,
+                     int64_t N, int P, int S, int max_rank, int dtype, void* stream);
+
 /* ---- fused residual-add + RMSNorm / LayerNorm (replaces dropout_layer_norm.dropout_add_ln_fwd,
  *      custom_modeling/flash_llama_modeling.py:132-152, utils/layers.py:376-396) ---------------- */
 /* res_out = x (+ residual); y = res_out * rsqrt(mean(res_out^2) + eps) * weight.

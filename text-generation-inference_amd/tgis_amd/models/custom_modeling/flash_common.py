@@ -122,12 +122,16 @@ class FlashForCausalLM:
         return len(self.model.layers)
 
     def forward(self, input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds=None, kv: KVArgs = None,
-                lm_head_indices: Optional[torch.Tensor] = None, return_embeds: bool = False):
+                lm_head_indices: Optional[torch.Tensor] = None, return_embeds: bool = False, lora=None):
         """position_ids int32 [T]; returns fp32 logits [T or len(lm_head_indices), vocab]; with `return_embeds` (the
-        reference's paged_llama_modeling.py:443-462) the pair (logits, hidden_states), the rows that went into lm_head."""
+        reference's paged_llama_modeling.py:443-462) the pair (logits, hidden_states), the rows that went into lm_head.
+        lora: a utils.lora.LoraArgs when rows of this forward carry adapters (the Llama class alone takes one)."""
         if input_ids is not None and inputs_embeds is not None:
             raise ValueError("You cannot specify both input_ids and inputs_embeds at the same time")
-        hidden_states = self.model(input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds, kv)
+        if lora is not None:
+            hidden_states = self.model(input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds, kv, lora)
+        else:
+            hidden_states = self.model(input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds, kv)
         if lm_head_indices is not None:
             hidden_states = hidden_states.index_select(0, lm_head_indices)
         logits = self.lm_head(hidden_states)

@@ -147,11 +147,22 @@ class FlashLlamaAttention:
         return attend(qkv, kv, layer_id, self.num_heads, self.num_key_value_heads, self.head_size, self.softmax_scale,
                       cu_seqlens_q, frag_out=frag_rows(self.o_proj, qkv.shape[0], kv))
 
-    def forward(self, hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id: int, kv: KVArgs):
+    def forward(self, hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id: int, kv: KVArgs, lora=None):
+        if lora is not None:
+            return self.forward_lora(hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id, kv, lora)
         qkv = self.project_qkv(hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id, kv)
         attn_output = self.attend(qkv, cu_seqlens_q, layer_id, kv)
         # may be a native.Partial: the following fused add+RMSNorm finishes the split-K sum
         return self.o_proj(attn_output, partial=True)
+
+    def forward_lora(self, hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id: int, kv: KVArgs, lora):
+        """A step that carries adapter rows (utils/lora.py): the plain GEMMs, each followed by its delta, which must land
+        before the rotation and before the add + norm — none of the fused forms."""
+        H, Hkv, D = self.num_heads, self.num_key_value_heads, self.head_size
+        qkv = self.query_key_value.forward_lora(hidden_states, lora)
+        qkv = write_kv(qkv, kv, layer_id, H, Hkv, D, D, cos, sin, position_ids, cu_seqlens_q)
+        attn_output = attend(qkv, kv, layer_id, H, Hkv, D, self.softmax_scale, cu_seqlens_q)
+        return self.o_proj.forward_lora(attn_output, lora)
 
     __call__ = forward
 
@@ -169,7 +180,12 @@ class LlamaMLP:
         # dense: it runs while down_proj stages its operand.  Reference: eager ops at :332-335.
         self.fused_epilogue = self.intermediate_size % 16 == 0 and self.gate_up_proj.fuse_gate_up()
 
-    def forward(self, hidden_states):
+    def forward(self, hidden_states, lora=None):
+        if lora is not None:
+            # unfused [T, 2 I] -> delta -> SiLU * up -> down_proj on the activated tensor, the operand of its shrink too
+            gate_up_states = self.gate_up_proj.forward_lora(hidden_states, lora)
+            act = native.act_mul(gate_up_states, self.intermediate_size)
+            return self.down_proj.forward_lora(act, lora)
         if self.fused_epilogue:
             if isinstance(hidden_states, native.FragAct):  # decode: SiLU * up leaves in the layout down_proj reads
                 rows = hidden_states.shape[0]
@@ -194,7 +210,12 @@ class FlashLlamaLayer:
         self.post_attention_layernorm = LlamaRMSNorm(prefix=f"{prefix}.post_attention_layernorm", weights=weights,
                                                      eps=config.rms_norm_eps)
 
-    def forward(self, hidden_states, residual, cos, sin, position_ids, cu_seqlens_q, kv: KVArgs):
+    def forward(self, hidden_states, residual, cos, sin, position_ids, cu_seqlens_q, kv: KVArgs, lora=None):
+        if lora is not None:  # (utils/lora.py LoraArgs: row-major activations throughout, the shrink reads them)
+            normed_hidden_states, res = self.input_layernorm(hidden_states, residual)
+            attn_output = self.self_attn(normed_hidden_states, cos, sin, position_ids, cu_seqlens_q, self.layer_id, kv, lora)
+            normed_attn_res_output, attn_res = self.post_attention_layernorm(attn_output, res)
+            return self.mlp(normed_attn_res_output, lora), attn_res
         rows = hidden_states.shape[0]
         att = self.self_attn
         # decode steps of <= 64 rows hand the int4 GEMMs their operands in fragment order (native.FragAct): the qkv + rotary
@@ -229,12 +250,12 @@ class FlashLlamaModel:
         self.max_positions = grow_max_positions(self.config, self.max_positions, max_s)
         return self.layers[0].self_attn.rotary_emb.tables(dtype, device, self.max_positions)
 
-    def forward(self, input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds, kv: KVArgs):
+    def forward(self, input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds, kv: KVArgs, lora=None):
         hidden_states = inputs_embeds if inputs_embeds is not None else self.embed_tokens(input_ids)
         cos, sin = self.rope_tables(hidden_states.dtype, hidden_states.device, max_s)
         residual = None
         for layer in self.layers:
-            hidden_states, residual = layer(hidden_states, residual, cos, sin, position_ids, cu_seqlens_q, kv)
+            hidden_states, residual = layer(hidden_states, residual, cos, sin, position_ids, cu_seqlens_q, kv, lora)
         hidden_states, _ = self.norm(hidden_states, residual)
         return hidden_states
 
@@ -251,3 +272,28 @@ class FlashLlamaForCausalLM(FlashForCausalLM):
 
     def get_input_embeddings(self):
         return self.model.embed_tokens
+
+    def enable_lora(self, slots: int, max_rank: int, dtype, device):
+        """Before post_init: wraps the four projections of every layer in a utils.lora.LoraLinear with `slots` adapter
+        slots (allocated here, once) and takes the SiLU * up epilogue out of gate_up, whose delta must land in front of it.
+        Returns the wrappers."""
+        from tgis_amd.utils.lora import LoraLinear
+
+        cfg, wrapped = self.config, []
+        for layer in self.model.layers:
+            att, mlp = layer.self_attn, layer.mlp
+            E, q, kvw, inter = cfg.hidden_size, att.num_heads * att.head_size, att.num_key_value_heads * att.head_size, \
+                mlp.intermediate_size
+            mlp.gate_up_proj.linear.unfuse_gate_up()
+            mlp.fused_epilogue = False
+
+            def wrap(proj, modules, bounds, K):
+                w = LoraLinear(proj, layer.layer_id, modules, bounds, K, slots, max_rank, dtype, device)
+                wrapped.append(w)
+                return w
+
+            att.query_key_value = wrap(att.query_key_value, ("q_proj", "k_proj", "v_proj"), (0, q, q + kvw, q + 2 * kvw), E)
+            att.o_proj = wrap(att.o_proj, ("o_proj",), (0, E), q)
+            mlp.gate_up_proj = wrap(mlp.gate_up_proj, ("gate_proj", "up_proj"), (0, inter, 2 * inter), E)
+            mlp.down_proj = wrap(mlp.down_proj, ("down_proj",), (0, E), inter)
+        return wrapped

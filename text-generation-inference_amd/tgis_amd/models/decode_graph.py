@@ -252,6 +252,39 @@ class _DecodeGraph:
         return self.logits, self.ids, self.logprobs
 
 
+LORA_KEY = "lora"  # the trailing marker of the graph key of a step in which some row carries a LoRA adapter
+
+
+class _LoraDecodeGraph(_DecodeGraph):
+    """The decode step of a batch in which some request carries a LoRA adapter (utils/lora.py), for a (batch-size bucket,
+    table width, LORA_KEY) key: the plain step's buffers plus a static `lora_slots` int32 [bucket], staged per run with the
+    inactive rows at -1.  The captured step groups the rows by slot on the device (tgis_lora_group) and every wrapped linear
+    adds its delta from the slot images, so a replay follows whatever slots, and whatever adapters in them, a step brings."""
+
+    def __init__(self, lm, B: int, width: int, marker: str = LORA_KEY):
+        assert marker == LORA_KEY
+        super().__init__(lm, B, width)
+        self.lora_slots = torch.full((B,), -1, dtype=torch.int32, device=lm.device)
+        self.staged_slots = None
+
+    def _forward(self, ids, positions, kv):
+        from tgis_amd.utils.lora import LoraArgs
+
+        lm = self.lm
+        return lm.model.forward(ids, positions, self.cu_q, self.max_ctx, None, kv,
+                                lora=LoraArgs.grouped(self.lora_slots, lm.lora_slots))
+
+    def run(self, input_ids, position_ids, block_tables, slots):
+        """One decode step of a batch of n <= rows sequences whose adapter slots are `slots` int32 [n] (device)."""
+        n = input_ids.numel()
+        if n < self.active:
+            self.lora_slots[n:self.active].fill_(-1)
+        if slots is not self.staged_slots or n != self.active:
+            self.lora_slots[:n].copy_(slots, non_blocking=True)
+            self.staged_slots = slots
+        return super().run(input_ids, position_ids, block_tables)
+
+
 class _VerifyGraph(_DecodeGraph):
     """The verify step of speculative decoding for a (batch-size bucket, table width, K) triple: K + 1 rows per request, its
     latest token and its K drafts, through the generic q_len > 1 forward (rotary and cache write per token, the attention's

@@ -27,7 +27,8 @@ import torch
 
 from tgis_amd import native
 from tgis_amd.models.custom_modeling.flash_common import KVArgs
-from tgis_amd.models.decode_graph import _DecodeGraph, _TreeVerifyGraph, _VerifyGraph, renew_unheld_pool
+from tgis_amd.models.decode_graph import (LORA_KEY, _DecodeGraph, _LoraDecodeGraph, _TreeVerifyGraph, _VerifyGraph,
+                                          renew_unheld_pool)
 from tgis_amd.models.model import Model
 from tgis_amd.models.speculation import LookupDrafter, MLPDrafter, spec_step
 from tgis_amd.models.types import Batch, GenerateError
@@ -36,6 +37,8 @@ from tgis_amd.utils import mlp_speculator
 from tgis_amd.utils.kv_cache import (KV_SCALES_HEADROOM, PAGE, OutOfPages, PagedKVCache, agree_kv_cache_dtype,
                                      agree_kv_prefix_reuse, agree_kv_scales, kv_pool_dtype, kv_scales_stats,
                                      pages_for_budget, parse_kv_cache_dtype, parse_kv_prefix_reuse)
+from tgis_amd.utils.lora import (LoraAdapter, LoraArgs, LoraSlots, check_lora_model, check_lora_world, module_shapes,
+                                 parse_lora_max_rank, parse_lora_slots, release_slots)
 from tgis_amd.utils.rank_group import RankGroup
 from tgis_amd.utils.sliding_window import check_window_options, parse_sliding_window
 from tgis_amd.utils.spec_decode import (check_spec_candidates, check_spec_world, check_tree_rows, fallback_cause,
@@ -97,6 +100,20 @@ class FlashCausalLMBatch(Batch):
     _spec_stale: bool = field(default=False, repr=False)
     # the host copy of `block_tables` (`_rebuild_block_tables`), which `grow_pages` edits and uploads again
     _bt_host: Optional[np.ndarray] = field(default=None, repr=False)
+    # LoRA adapters (utils/lora.py): per request the device slot its adapter is pinned in (-1: none), None when no request
+    # of the batch carries one; the slot table the pins go back to; and the slots on the device, int32 [B], made on demand
+    lora_slots: Optional[List[int]] = None
+    lora_table: Optional[Any] = None
+    _lora_dev: Optional[torch.Tensor] = field(default=None, repr=False)
+
+    def has_lora(self) -> bool:
+        return self.lora_slots is not None and any(s >= 0 for s in self.lora_slots)
+
+    def lora_slots_device(self) -> torch.Tensor:
+        """`lora_slots` as int32 [B] on the device; the same tensor until concatenate or prune change the batch."""
+        if self._lora_dev is None or self._lora_dev.numel() != len(self.lora_slots):
+            self._lora_dev = torch.tensor(self.lora_slots, dtype=torch.int32).to(self.position_ids.device, non_blocking=True)
+        return self._lora_dev
 
     def get_id(self) -> int:
         return self.batch_id
@@ -117,7 +134,9 @@ class FlashCausalLMBatch(Batch):
         # deterministic function of the two, so every rank maps the same pages.
         shared = [[] for _ in need]
         if getattr(kv_cache, "prefix_reuse", False) and self.reuse_lookup_ok():
-            shared = [kv_cache.match(ids) for ids in self.prompt_token_ids]
+            # (a request that carries a LoRA adapter neither looks up nor registers pages: its keys differ)
+            adapted = self.lora_slots or [-1] * len(need)
+            shared = [kv_cache.match(ids) if s < 0 else [] for ids, s in zip(self.prompt_token_ids, adapted)]
         own = [n - len(s) for n, s in zip(need, shared)]
         try:
             flat = kv_cache.alloc(sum(own))  # raises OutOfPages before anything is taken
@@ -148,8 +167,10 @@ class FlashCausalLMBatch(Batch):
         ids, self.prompt_token_ids = self.prompt_token_ids, None
         if ids is None or self.inputs_embeds is not None or not getattr(self.kv_cache, "prefix_reuse", False):
             return
-        for pages, toks in zip(self.pages, ids):
-            self.kv_cache.register(pages, toks)
+        adapted = self.lora_slots or [-1] * len(ids)
+        for pages, toks, s in zip(self.pages, ids, adapted):
+            if s < 0:
+                self.kv_cache.register(pages, toks)
 
     def grow_pages(self, ahead: int = 0):
         """Before a decode step: every sequence owns the page its next token (position input_length - 1) lands on, and
@@ -232,6 +253,8 @@ class FlashCausalLMBatch(Batch):
                 self.kv_cache.free(p)
         self.pages = None
         self.block_tables = None
+        slots, self.lora_slots = self.lora_slots, None
+        release_slots(self.lora_table, slots)
 
     def __del__(self):
         try:
@@ -244,22 +267,40 @@ class FlashCausalLMBatch(Batch):
     def from_pb(cls, pb: generate_pb2.Batch, tokenizer, dtype: torch.dtype, device: torch.device,
                 embeddings_lookup: Optional, prefix_cache: Optional, use_position_ids: bool = True,
                 ) -> Tuple[Optional["FlashCausalLMBatch"], List[GenerateError]]:
+        lora_slots: List[int] = []  # the requests' LoRA slots, pinned as they are found: they go back if no batch results
+        try:
+            return cls._from_pb(pb, tokenizer, dtype, device, embeddings_lookup, prefix_cache, use_position_ids, lora_slots)
+        except BaseException:
+            release_slots(getattr(prefix_cache, "lora", None), lora_slots)
+            raise
+
+    @classmethod
+    def _from_pb(cls, pb, tokenizer, dtype, device, embeddings_lookup, prefix_cache, use_position_ids, lora_slots):
         errors: List[GenerateError] = []
         requests, batch_inputs, prefix_embeds_by_index = [], [], {}
         input_lengths, total_lengths = [], []
         cu_seqlens = [0]
+        lora_table = getattr(prefix_cache, "lora", None)
         for r in pb.requests:
             input_length = r.input_length
+            slot = -1
             if r.prefix_id:
                 try:
                     prefix_embeds = prefix_cache.get(r.prefix_id)
-                except Exception:
+                    if isinstance(prefix_embeds, LoraAdapter):
+                        # a LoRA adapter adds no tokens: the request pins a device slot (every slot pinned: an error)
+                        slot = lora_table.acquire(prefix_embeds)
+                except Exception as exc:
                     message = f"Prefix lookup error for request #{r.id}, prefix id {r.prefix_id}"
+                    if isinstance(exc, ValueError) and "LoRA" in str(exc):
+                        message += f": {exc}"  # (names the refused variant, the missing option or the busy slots)
                     logging.error(message)
                     errors.append(GenerateError(request_id=r.id, message=message))
                     continue  # the request is left out of the batch
-                prefix_embeds_by_index[len(requests)] = prefix_embeds
-                input_length += prefix_embeds.shape[0]  # input_lengths include the prefix
+                if slot < 0:
+                    prefix_embeds_by_index[len(requests)] = prefix_embeds
+                    input_length += prefix_embeds.shape[0]  # input_lengths include the prefix
+            lora_slots.append(slot)
             requests.append(r)
             batch_inputs.append(r.inputs)
             input_lengths.append(input_length)
@@ -312,6 +353,7 @@ class FlashCausalLMBatch(Batch):
             total_lengths=total_lengths, all_input_ids_tensor=all_input_ids_tensor,
             next_token_chooser=next_token_chooser, pad_token_id=tokenizer.pad_token_id,
             prompt_token_ids=prompt_token_ids,
+            lora_slots=list(lora_slots) if any(s >= 0 for s in lora_slots) else None, lora_table=lora_table,
         ), errors
 
     @classmethod
@@ -370,9 +412,13 @@ class FlashCausalLMBatch(Batch):
         except BaseException:
             merged.pages = None  # the sources still own them
             raise
+        if any(b.lora_slots is not None for b in batches):  # the pins change hands with the pages
+            merged.lora_slots = [s for b in batches for s in (b.lora_slots or [-1] * len(b))]
+            merged.lora_table = next(b.lora_table for b in batches if b.lora_slots is not None)
         for batch in batches:
             batch.pages = None
             batch.block_tables = None
+            batch.lora_slots = None
         merged.redraft()
         return merged
 
@@ -391,6 +437,9 @@ class FlashCausalLMBatch(Batch):
             if i not in keep:
                 batch.kv_cache.free(p)
         pick = (lambda l: [l[i] for i in keep_indices])
+        if batch.lora_slots is not None:  # the completed requests' adapter slots are unpinned
+            release_slots(batch.lora_table, [s for i, s in enumerate(batch.lora_slots) if i not in keep])
+            batch.lora_slots, batch._lora_dev = pick(batch.lora_slots), None
         batch.pages = pick(batch.pages)
         batch.input_lengths = pick(batch.input_lengths)
         batch.total_lengths = pick(batch.total_lengths)
@@ -449,6 +498,11 @@ class FlashCausalLM(Model):
     spec_candidates = 1
     # sliding-window attention: W keys per q row (config.sliding_window, Mistral), None = causal (set by the constructor)
     sliding_window = None
+    # LoRA adapters per request (utils/lora.py; set by the constructor): S device slots (0 = off) for ranks up to
+    # lora_max_rank, and the table that maps adapter ids to them
+    lora_slots = 0
+    lora_max_rank = 64
+    lora_table = None
 
     def __init__(self, model_name: str, revision: Optional[str], deployment_framework: str, dtype: torch.dtype,
                  quantize: Optional[str], model_config: Union[Any] = None, auto_model_class=None,
@@ -456,7 +510,8 @@ class FlashCausalLM(Model):
                  kv_cache_dtype: Optional[str] = None, kv_scales: Union[None, str, dict] = None,
                  kv_prefix_reuse: Optional[bool] = None, spec_tokens: Optional[int] = None,
                  spec_ngram: Optional[int] = None, speculator: Union[None, str, Any] = None,
-                 spec_sampling: Optional[bool] = None, spec_candidates: Optional[int] = None):
+                 spec_sampling: Optional[bool] = None, spec_candidates: Optional[int] = None,
+                 lora_slots: Optional[int] = None, lora_max_rank: Optional[int] = None):
         # KV cache element: "auto" (the model dtype) or "fp8_e4m3" (one byte, utils/kv_cache.py); None reads
         # TGIS_KV_CACHE_DTYPE.  Checked before anything is loaded — except on a rank of a tensor-parallel group, which loads
         # its shard and then tells its peers (agree_kv_cache_dtype below): they sit in a collective only it can release.
@@ -487,6 +542,13 @@ class FlashCausalLM(Model):
         # chain, 2 .. 4).  It needs spec_tokens > 0, the lookup drafter and no spec_sampling.
         self.spec_candidates = parse_spec_candidates(spec_candidates)
         check_spec_candidates(self.spec_candidates, self.spec_tokens, spec_ckpt is not None, self.spec_sampling)
+        # lora_slots: S > 0 lets every request name a LoRA adapter with its prefix_id (utils/lora.py): S adapters are
+        # resident on the device at once, requests with different adapters or none share a batch; None reads TGIS_LORA_SLOTS
+        # (0 / unset = off, 1 .. 32).  lora_max_rank: the largest rank a slot holds (TGIS_LORA_MAX_RANK, default 64, a
+        # multiple of 16 up to 64).  Llama class only; not under tensor parallelism, not with spec_tokens.
+        self.lora_slots = parse_lora_slots(lora_slots)
+        self.lora_max_rank = parse_lora_max_rank(lora_max_rank)
+        check_lora_world(self.lora_slots, getattr(engine, "world_size", 1) or 1, self.spec_tokens)
         # kv_scales: the calibrated per-layer scales of a one-byte cache, the contents of a kv_cache_scales.json or its path
         # (utils/kv_cache.py, resolve_kv_scales); None looks at TGIS_KV_SCALES, then next to the weights, else they stay 1.0
         if not torch.cuda.is_available():
@@ -517,12 +579,22 @@ class FlashCausalLM(Model):
         self.num_kv_heads = inner.num_key_value_heads
         self.head_size = inner.head_size
         self.num_layers = len(inner.layers)
+        if self.lora_slots:
+            # before post_init (the gate_up image loses its SiLU * up epilogue) and before the pool is sized: the slot
+            # images are allocated here, once, and their bytes come out of the page budget
+            check_lora_model(self.lora_slots, self.model)
+            self.lora_linears = self.model.enable_lora(self.lora_slots, self.lora_max_rank, dtype, self.device)
+            self.lora_table = LoraSlots(self.lora_slots, self.lora_max_rank, module_shapes(self.config), self.num_layers, dtype,
+                                        upload=self._load_adapter)
+            if self.prefix_cache is not None:
+                self.prefix_cache.lora = self.lora_table
         if hasattr(self.model, "post_init"):
             self.model.post_init()
         # what tensor-parallel ranks must agree on, in this order on every rank: cache dtype, prefix reuse, pages, scales,
         # graph mode, seed
         self.ranks = RankGroup(engine, self.device)
         check_spec_world(self.spec_tokens, self.ranks.world)
+        check_lora_world(self.lora_slots, self.ranks.world, self.spec_tokens)
         check_tree_rows(self.spec_candidates, self.spec_tokens, self.num_heads, self.num_kv_heads)
         self._spec_stats = new_stats()
         if spec_ckpt is not None:
@@ -711,14 +783,37 @@ class FlashCausalLM(Model):
                     num_splits=native.attn_q_splits(len(lens), self.num_kv_heads, self.num_heads, max_q, max_ctx),
                     past_lens=native.past_lens_tensor(hits, dev) if FRESH_PREFILL_KV else None)
         return self._forward_prefill(batch.input_ids.index_select(0, up(take)), up(positions), cu_q, batch.max_seqlen, None,
-                                     kv, (cu_q[1:] - 1).long())
+                                     kv, (cu_q[1:] - 1).long(), lora=self._prefill_lora(batch, suffix))
 
-    def _forward_prefill(self, *args):
+    def _forward_prefill(self, *args, lora=None):
         """(logits, hidden rows or None): the model's forward; a drafter that needs them also gets the rows that went into
-        lm_head (`return_embeds`)."""
+        lm_head (`return_embeds`).  lora: the LoraArgs of a prefill that carries adapter rows."""
+        if lora is not None:
+            return self.model.forward(*args, lora=lora), None
         if self.drafter is not None and self.drafter.needs_hidden:
             return self.model.forward(*args, return_embeds=True)
         return self.model.forward(*args), None
+
+    def _load_adapter(self, slot: int, adapter: LoraAdapter):
+        """The slot table's upload: the adapter's tensors into `slot` of every wrapped linear, as copies on the current
+        stream (a captured decode graph reads the slot images at fixed addresses and sees them on its next replay)."""
+        for lin in self.lora_linears:
+            lin.load(slot, adapter)
+
+    def _prefill_lora(self, batch: FlashCausalLMBatch, rows_per_request: List[int]) -> Optional[LoraArgs]:
+        """The LoraArgs of a prefill whose request i brings rows_per_request[i] rows, None when no request carries an
+        adapter.  Up to 64 rows take the kernels (grouped on the device); longer forwards loop on the host over the
+        requests that carry one, whose rows are contiguous."""
+        if not batch.has_lora():
+            return None
+        slots = np.repeat(np.asarray(batch.lora_slots, dtype=np.int32), rows_per_request)
+        dev_slots = torch.from_numpy(slots).to(self.device, non_blocking=True)
+        if slots.size <= native.LORA_MAX_T:
+            return LoraArgs.grouped(dev_slots, self.lora_slots)
+        starts = np.concatenate([[0], np.cumsum(rows_per_request)])
+        ranges = [(int(starts[i]), int(starts[i + 1]), s) for i, s in enumerate(batch.lora_slots)
+                  if s >= 0 and rows_per_request[i] > 0]
+        return LoraArgs(slots=dev_slots, ranges=ranges)
 
     def _prefill_fresh_forward(self, batch: FlashCausalLMBatch):
         lens = batch.input_lengths
@@ -733,7 +828,8 @@ class FlashCausalLM(Model):
                     window=self.sliding_window)
         lm_head_indices = None if self._need_all_logits else (batch.cu_seqlens[1:] - 1).long()
         return self._forward_prefill(batch.input_ids, batch.position_ids.to(torch.int32), batch.cu_seqlens,
-                                     batch.max_seqlen, batch.inputs_embeds, kv, lm_head_indices)
+                                     batch.max_seqlen, batch.inputs_embeds, kv, lm_head_indices,
+                                     lora=self._prefill_lora(batch, lens))
 
     def _decode_forward(self, batch: FlashCausalLMBatch):
         verify = self.spec_tokens > 0 and self._grow_for_verify(batch)
@@ -743,15 +839,23 @@ class FlashCausalLM(Model):
         tree = verify and self.spec_candidates > 1
         if verify:
             key += (self.spec_tokens, self.spec_candidates) if tree else (self.spec_tokens,)
+        # a step in which some row carries a LoRA adapter runs its own graph (the unfused linears plus the deltas, over a
+        # static slot buffer); batches without adapters keep the plain key and the plain graph
+        lora = self.lora_slots > 0 and batch.has_lora()
+        if lora:
+            key += (LORA_KEY,)
         g = self._graphs.get(key)
         if g is None:
             while len(self._graphs) >= self.max_graphs:
                 self._graphs.popitem(last=False)
             renew_unheld_pool(self)
-            g = self._graphs[key] = (_TreeVerifyGraph if tree else _VerifyGraph if verify else _DecodeGraph)(self, *key)
+            kind = _LoraDecodeGraph if lora else _TreeVerifyGraph if tree else _VerifyGraph if verify else _DecodeGraph
+            g = self._graphs[key] = kind(self, *key)
         else:
             self._graphs.move_to_end(key)
-        if verify:
+        if lora:
+            logits, ids, lps = g.run(batch.input_ids, batch.position_ids, batch.block_tables, batch.lora_slots_device())
+        elif verify:
             logits, ids, lps = g.run(batch.input_ids, batch.position_ids, batch.block_tables, batch.spec_drafts)
         else:
             logits, ids, lps = g.run(batch.input_ids, batch.position_ids, batch.block_tables)

@@ -82,6 +82,13 @@ SIGNATURES = {
                                        _c_int, _c_int, _vp]),
     "tgis_moe_gptq_gemm_down": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int,
                                          _c_int, _c_int, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "tgis_lora_a_bytes": (_c_i64, [_c_i64, _c_int, _c_int]),
+    "tgis_lora_b_bytes": (_c_i64, [_c_i64, _c_int]),
+    "tgis_lora_group": (_c_int, [_vp, _c_i64, _c_int, _vp, _vp, _vp, _vp]),
+    "tgis_lora_shrink": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int, _c_int,
+                                  _c_int, _vp]),
+    "tgis_lora_expand": (_c_int, [_vp, _vp, _c_i64, _vp, _vp, _vp, _vp, ctypes.POINTER(_c_i64), _vp, _c_i64, _c_i64, _c_i64,
+                                  _c_int, _c_int, _c_int, _c_int, _vp]),
     "tgis_rmsnorm_residual":(_c_int, [_vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_f, _c_int, _vp]),
     "tgis_rmsnorm_residual_partial": (_c_int, [_vp, _c_int, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_f,
                                                _c_int, _vp]),
@@ -816,6 +823,104 @@ def moe_gptq_gemm_down(h: torch.Tensor, w: MoeGptqWeights, r: Routing, partial: 
     if not partial:
         return out
     return Partial(scratch, r.top_k, w.N, r.T, w.N, None)
+
+
+# ---- per-request LoRA adapters (csrc/lora.hip) -----------------------------------------------------------
+LORA_MAX_T, LORA_MAX_SLOTS, LORA_MAX_RANK = 64, 32, 64  # rows of the kernel path, slots, rank cap
+
+
+class LoraImages:
+    """The slot images of one linear (tgis_hip.h): A [S, P, max_rank, K] and B [S, max_rank / 16, N, 16] in the model dtype,
+    ranks int32 [S] and scales f32 [S], allocated once, at fixed addresses.  `bounds`: the P + 1 column bounds of the P
+    projections fused into the linear.  `host_ranks` / `host_scales` mirror the device arrays for the host loop of long
+    prefills."""
+
+    def __init__(self, K: int, bounds, S: int, max_rank: int, dtype, device):
+        self.K, self.N, self.P, self.S, self.max_rank, self.dtype = K, bounds[-1], len(bounds) - 1, S, max_rank, dtype
+        self.bounds = tuple(int(b) for b in bounds)
+        self._bounds_c = (_c_i64 * 4)(*(self.bounds + (self.N,) * (4 - len(self.bounds))))
+        self.A = torch.zeros((S, self.P, max_rank, K), dtype=dtype, device=device)
+        self.B = torch.zeros((S, max_rank // 16, self.N, 16), dtype=dtype, device=device)
+        self.ranks = torch.zeros(S, dtype=torch.int32, device=device)
+        self.scales = torch.zeros(S, dtype=torch.float32, device=device)
+        self.host_ranks, self.host_scales = [0] * S, [0.0] * S
+        self.host_present = [(False,) * self.P for _ in range(S)]  # which of the P projections a slot's adapter targets
+        self.a_stride = self.A.stride(0) * self.A.element_size()
+        self.b_stride = self.B.stride(0) * self.B.element_size()
+
+    @property
+    def nbytes(self) -> int:
+        return self.A.numel() * self.A.element_size() + self.B.numel() * self.B.element_size() + 8 * self.S
+
+    @staticmethod
+    def pack(As, Bs, bounds, K: int, dtype):
+        """(rank, a [P, r16, K], b [r16 / 16, N, 16]) on the CPU from P pairs (A [r, K], B [n_p, r]), a pair None where the
+        adapter leaves the projection out; zero from the rank up to the next multiple of 16.  rank 0: nothing to load."""
+        rank = max((a.shape[0] for a in As if a is not None), default=0)
+        if rank == 0:
+            return 0, None, None
+        r16, N = (rank + 15) // 16 * 16, bounds[-1]
+        a = torch.zeros((len(As), r16, K), dtype=dtype)
+        b = torch.zeros((N, r16), dtype=dtype)
+        for p, (ap, bp) in enumerate(zip(As, Bs)):
+            if ap is not None:
+                a[p, :rank] = ap.to(dtype)
+                b[bounds[p]:bounds[p + 1], :rank] = bp.to(dtype)
+        return rank, a, b.view(N, r16 // 16, 16).permute(1, 0, 2).contiguous()
+
+    def load(self, s: int, As, Bs, scale: float) -> None:
+        """An adapter's share of this linear into slot s: copies on the current stream, so a captured graph sees it on its
+        next replay.  What the slot held beyond the new rank (rounded up to 16) stays and is never read."""
+        assert 0 <= s < self.S and len(As) == len(Bs) == self.P
+        rank, a, b = self.pack(As, Bs, self.bounds, self.K, self.dtype)
+        assert rank <= self.max_rank
+        if rank:
+            self.A[s, :, :a.shape[1]].copy_(a)
+            self.B[s, :b.shape[0]].copy_(b)
+        self.ranks[s:s + 1].copy_(torch.tensor([rank], dtype=torch.int32))
+        self.scales[s:s + 1].copy_(torch.tensor([scale if rank else 0.0], dtype=torch.float32))
+        self.host_ranks[s], self.host_scales[s] = rank, float(scale) if rank else 0.0
+        self.host_present[s] = tuple(a is not None for a in As)
+
+
+class LoraGroup:
+    """What lora_group leaves on the device for T rows and S slots: counts int32 [S], offsets int32 [S + 1], rows int32 [T]."""
+
+    def __init__(self, T: int, S: int, device):
+        self.T, self.S = T, S
+        self.lists = torch.empty(2 * S + 1, dtype=torch.int32, device=device)
+        self.counts, self.offsets = self.lists[:S], self.lists[S:]
+        self.rows = torch.empty(T, dtype=torch.int32, device=device)
+
+
+def lora_group(slot: torch.Tensor, S: int) -> LoraGroup:
+    """The rows of `slot` (int32 [T], -1 .. S-1) grouped by slot, all on the device."""
+    assert slot.dim() == 1 and slot.dtype == torch.int32 and slot.is_contiguous()
+    g = LoraGroup(slot.numel(), S, slot.device)
+    _check(load_library().tgis_lora_group(_ptr(slot), g.T, S, _ptr(g.counts), _ptr(g.offsets), _ptr(g.rows), _stream()),
+           "tgis_lora_group")
+    return g
+
+
+def lora_shrink(x: torch.Tensor, w: LoraImages, g: LoraGroup, v=None) -> torch.Tensor:
+    """v fp32 [T, P, max_rank]: A_s[p] x[t] for the rows of the lists, up to each slot's rank rounded up to 16."""
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == w.dtype and x.shape == (g.T, w.K) and g.S == w.S
+    if v is None:
+        v = torch.empty((g.T, w.P, w.max_rank), dtype=torch.float32, device=x.device)
+    _check(load_library().tgis_lora_shrink(_ptr(x), x.stride(0), _ptr(w.A), w.a_stride, _ptr(w.ranks), _ptr(g.offsets),
+                                           _ptr(g.rows), _ptr(v), g.T, w.K, w.P, w.S, w.max_rank, dtype_code(w.dtype),
+                                           _stream()), "tgis_lora_shrink")
+    return v
+
+
+def lora_expand(v: torch.Tensor, w: LoraImages, g: LoraGroup, y: torch.Tensor) -> torch.Tensor:
+    """y[t] += scale_s B_s v[t] in place for the rows of the lists (one rounding to the model dtype); other rows untouched."""
+    assert y.dim() == 2 and y.stride(1) == 1 and y.dtype == w.dtype and y.shape == (g.T, w.N) and g.S == w.S
+    assert v.dtype == torch.float32 and v.is_contiguous() and v.shape == (g.T, w.P, w.max_rank)
+    _check(load_library().tgis_lora_expand(_ptr(v), _ptr(w.B), w.b_stride, _ptr(w.ranks), _ptr(w.scales), _ptr(g.offsets),
+                                           _ptr(g.rows), w._bounds_c, _ptr(y), y.stride(0), g.T, w.N, w.P, w.S, w.max_rank,
+                                           dtype_code(w.dtype), _stream()), "tgis_lora_expand")
+    return y
 
 
 def clear_error() -> None:

@@ -28,6 +28,8 @@ from typing import Optional, Tuple
 
 import torch
 
+from tgis_amd.utils.lora import check_adapter_config, read_adapter_config
+
 logger = logging.getLogger(__name__)
 
 VALID_PREFIX_ID = re.compile(r"[/\w\-]+")
@@ -65,12 +67,24 @@ class PrefixCache:
         self._lock = threading.Lock()
 
     # ---- lookups ------------------------------------------------------------------------------------------------
-    def get(self, prefix_id: str) -> torch.Tensor:
-        """The `[n_virtual, hidden]` prompt tensor for `prefix_id`, loading and caching it on first use."""
+    # the model's LoRA slot table (utils/lora.py LoraSlots) when it serves adapters (lora_slots > 0), else None
+    lora = None
+
+    def get(self, prefix_id: str):
+        """The `[n_virtual, hidden]` prompt tensor for `prefix_id`, loading and caching it on first use.  An id whose
+        directory holds a LoRA adapter (`adapter_config.json` with `"peft_type": "LORA"`) answers a checked
+        `utils.lora.LoraAdapter` instead: it adds no tokens, `from_pb` pins a device slot for it.  Adapters are not kept
+        here: the slot table knows the resident ones."""
         hit = self._touch(prefix_id)
         if hit is not None:
             return hit
+        if self.lora is not None:
+            adapter = self.lora.resident(prefix_id)
+            if adapter is not None:
+                return adapter
         tensor = self._load(prefix_id)
+        if not torch.is_tensor(tensor):
+            return tensor
         return self._insert(prefix_id, tensor)
 
     def __len__(self) -> int:
@@ -121,6 +135,9 @@ class PrefixCache:
     def _load(self, prefix_id: str) -> torch.Tensor:
         d = self._dir(prefix_id)
         raw = None
+        lora_cfg = read_adapter_config(d) if d.is_dir() else None
+        if lora_cfg is not None:
+            return self._load_lora(prefix_id, d, lora_cfg)
         if d.is_dir() and any(f.stem == "adapter_model" for f in d.iterdir()):  # peft.save_pretrained() layout
             data = self._read(d / "adapter_model.safetensors")
             if data is None:
@@ -137,6 +154,19 @@ class PrefixCache:
         if self.zero is not None:
             return self.zero.expand(prefix.shape)
         return prefix.to(self.device, non_blocking=True)
+
+    def _load_lora(self, prefix_id: str, d: Path, cfg: dict):
+        """A LoRA adapter directory: config and tensors checked against the base model, on the CPU."""
+        if self.lora is None:
+            raise ValueError(f"Prefix id {prefix_id} is a LoRA adapter: the model was started without adapter slots, set "
+                             "lora_slots (TGIS_LORA_SLOTS) to serve it")
+        check_adapter_config(prefix_id, cfg, self.lora.max_rank)  # (before the tensors are read)
+        data = self._read(d / "adapter_model.safetensors")
+        if data is None:
+            data = self._read(d / "adapter_model.bin")
+        if data is None:
+            raise PrefixNotFound(f"LoRA adapter {prefix_id}: no adapter_model.safetensors or adapter_model.bin")
+        return self.lora.build(prefix_id, cfg, data)
 
     def _validate(self, prefix) -> torch.Tensor:
         if not torch.is_tensor(prefix) or prefix.dim() != 2:

@@ -22,6 +22,7 @@ from tgis_amd.cache import Cache
 from tgis_amd.models.model import Model
 from tgis_amd.pb import generate_pb2, generate_pb2_grpc
 from tgis_amd.utils.kv_cache import OutOfPages
+from tgis_amd.utils.lora import LoraAdapter
 from tgis_amd.utils.memory_characterizer import ESTIMATE_MEMORY, MemoryScalingModel, characterize_paged
 
 HEALTHCHECK_BATCH_ID = (1 << 64) - 1
@@ -87,7 +88,10 @@ class TextGenerationService(generate_pb2_grpc.TextGenerationServiceServicer):
                 prefix = None
         if prefix is None:
             await context.abort(grpc.StatusCode.NOT_FOUND, f"prefix id \"{request.prefix_id}\" not found")
-        n = len(prefix) if torch.is_tensor(prefix) else sum(len(t) for t in prefix if t is not None)
+        if isinstance(prefix, LoraAdapter):
+            n = 0  # a LoRA adapter (loaded and checked by the lookup) adds no tokens
+        else:
+            n = len(prefix) if torch.is_tensor(prefix) else sum(len(t) for t in prefix if t is not None)
         return generate_pb2.PrefixLookupResponse(prefix_length=n)
 
     def _prune_cached(self, cbatch) -> Optional[object]:

@@ -66,6 +66,10 @@ class Linear:
         returns SiLU(gate) * up [M, I] from its own epilogue; False: not offered, it keeps returning [M, 2 I]."""
         return False
 
+    def unfuse_gate_up(self) -> None:
+        """Takes `fuse_gate_up` back, before the first forward: `forward` returns [M, 2 I] again.  Asked by a model that
+        serves LoRA adapters, whose delta must land between the GEMM and SiLU * up."""
+
     def declare_rope_heads(self, H: int, Hkv: int, D: int) -> None:
         """Told once by FlashLlamaAttention to its fused qkv projection: the (query heads, kv heads, head size) of this shard.
         A class with a fused qkv + rotary + cache-write launch builds its `rope_handle` from this (here or in post_init)."""
@@ -104,6 +108,11 @@ class FastLinear(Linear):
             self.gate_up = True
             self.prepared = native.DenseWeight(self.weight, gate_up=True)
         return True
+
+    def unfuse_gate_up(self) -> None:
+        if self.gate_up:
+            self.gate_up = False
+            self.prepared = native.DenseWeight(self.weight)
 
     def declare_rope_heads(self, H: int, Hkv: int, D: int) -> None:
         """Builds the rope image (a second copy of the weight with rotation pairs inside each tile) for
@@ -221,6 +230,10 @@ class Ex4bitLinearV2(GptqLinear):
         assert self.q_handle is None, "the [gate | up] image is chosen before post_init"
         self.gate_up = True
         return True
+
+    def unfuse_gate_up(self) -> None:
+        assert self.q_handle is None, "the [gate | up] image is chosen before post_init"
+        self.gate_up = False
 
     def _prepare(self):
         q_handle = native.GptqWeight(self.qweight, self.qzeros, self.scales, self.g_idx, self.bits, self.groupsize,
