@@ -423,6 +423,32 @@ int tgis_rope_kv_write_prefill_at_kv8(void* qkv, int64_t ld_qkv, const void* cos
                                       int D, int rot_dim, int dtype, void* stream, int kv_dtype, float k_scale,
                                       float v_scale, const int32_t* past_lens);
 
+/* The cache writers for models with a per-head RMSNorm of q and k between the qkv projection and the rotation (Qwen3's
+ * self_attn.q_norm / k_norm; transformers' Qwen3Attention.forward): every q head and every k head is normalised over its D
+ * elements in fp32, rstd = rsqrt(mean_d(x^2) + eps), y = x rstd w[d] with w = q_norm_w / k_norm_w [D] of the model dtype,
+ * then rotated in fp32 over dims [0, rot_dim) and rounded to the model dtype once, at the store; dims in [rot_dim, D) are
+ * normalised and not rotated, v heads are copied.  x is the model-dtype activation (for slabs: the rounded sum + bias of
+ * tgis_rope_kv_write_partial).  Each entry point carries every option of the plain writers in one signature:
+ *   tgis_rope_kv_write_qknorm: per token (decode and verify steps, any forward that is not page-wise).  slabs == NULL: in
+ *     place on qkv; else qkv receives the reduced, normalised, rotated activation (num_slabs, slab_ld, bias as in
+ *     tgis_rope_kv_write_partial; a bias needs slabs).  Hkv = 0 with null pools: q heads only.
+ *   tgis_rope_kv_write_prefill_qknorm: page-wise (tgis_rope_kv_write_prefill; past_lens non-null:
+ *     tgis_rope_kv_write_prefill_at).  k / v inside `qkv` are left as they came.
+ *   kv_dtype, k_scale, v_scale: TGIS_KV_MODEL (scales ignored) or TGIS_KV_FP8_E4M3, as in the _kv8 writers.
+ * D must be 64, 96 or 128; rot_dim a positive multiple of 16 <= D; both norm weights, cos, sin and positions non-null;
+ * eps > 0.  T == 0 (B == 0) is TGIS_OK and touches nothing.  Both forms write the same bits for the same token. */
+int tgis_rope_kv_write_qknorm(void* qkv, int64_t ld_qkv, const float* slabs, int num_slabs, int64_t slab_ld,
+                              const void* bias, const void* q_norm_w, const void* k_norm_w, float eps, const void* cos,
+                              const void* sin, const int32_t* positions, const int32_t* slots, void* k_pool, void* v_pool,
+                              int64_t T, int H, int Hkv, int D, int rot_dim, int dtype, int kv_dtype, float k_scale,
+                              float v_scale, void* stream);
+int tgis_rope_kv_write_prefill_qknorm(void* qkv, int64_t ld_qkv, const void* q_norm_w, const void* k_norm_w, float eps,
+                                      const void* cos, const void* sin, const int32_t* positions,
+                                      const int32_t* cu_seqlens, const int32_t* past_lens, const int32_t* block_tables,
+                                      int64_t max_pages, void* k_pool, void* v_pool, int64_t B, int64_t T, int64_t max_len,
+                                      int H, int Hkv, int D, int rot_dim, int dtype, int kv_dtype, float k_scale,
+                                      float v_scale, void* stream);
+
 /* ---- paged attention, prefill and decode (replaces flash_attn_2_cuda.varlen_fwd,
  *      utils/flash_attn.py:43-78) ---------------------------------------------------------------- */
 /* Number of key-range splits the launcher will use for this shape (so callers can size workspace). */

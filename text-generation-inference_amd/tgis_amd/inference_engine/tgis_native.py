@@ -2,7 +2,7 @@
 (mirrors inference_engine/tgis_native.py:23-139 of the reference; model families of the configs in
 BASELINE.json: llama, and gpt_bigcode when flash_santacoder_modeling is present; gpt_neox; mistral, whose tensors carry
 Llama's names and whose sliding window FlashCausalLM reads from the config; mixtral, which is mistral around a routed expert
-MLP)."""
+MLP; qwen2 and qwen3, which are Llama with a q/k/v bias resp. a per-head q/k RMSNorm)."""
 import os
 from typing import Any, Optional
 
@@ -14,7 +14,7 @@ from tgis_amd.utils.dist import initialize_torch_distributed
 from tgis_amd.utils.hub import local_weight_files
 from tgis_amd.utils.weights import Weights
 
-FLASH_TYPES = ["llama", "gpt_bigcode", "gpt_neox", "mistral", "mixtral"]
+FLASH_TYPES = ["llama", "gpt_bigcode", "gpt_neox", "mistral", "mixtral", "qwen2", "qwen3"]
 
 
 def _barrier(group):
@@ -27,7 +27,8 @@ def _barrier(group):
 def model_class_for(config):
     model_type = config.model_type
     aliases = None
-    if model_type in ("llama", "mistral"):
+    if model_type in ("llama", "mistral", "qwen2", "qwen3"):  # (the Qwen families: Llama's tensor names, config.model_type
+        # decides the biases and the q / k norm inside FlashLlamaAttention)
         if getattr(config, "tie_word_embeddings", False):
             aliases = {"lm_head.weight": ["model.embed_tokens.weight"]}
         from tgis_amd.models.custom_modeling.flash_llama_modeling import FlashLlamaForCausalLM

@@ -17,7 +17,7 @@ from tgis_amd.models.model import Model
 # grads are never needed in a serving shard (reference models/__init__.py:28)
 torch.set_grad_enabled(False)
 
-FLASH_MODEL_TYPES = ("llama", "gpt_bigcode", "gpt_neox", "mistral", "mixtral")
+FLASH_MODEL_TYPES = ("llama", "gpt_bigcode", "gpt_neox", "mistral", "mixtral", "qwen2", "qwen3")
 
 
 def _flash_supports(model_type: str, config: Optional[dict]) -> bool:

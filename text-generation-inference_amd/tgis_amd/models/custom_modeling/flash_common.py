@@ -41,12 +41,16 @@ def layer_pools(kv: KVArgs, layer_id: int):
     return cache.k_pool(layer_id), cache.v_pool(layer_id), scales
 
 
-def write_kv(qkv, kv: KVArgs, layer_id: int, H: int, Hkv: int, D: int, rot_dim: int, cos, sin, position_ids, cu_seqlens_q):
+def write_kv(qkv, kv: KVArgs, layer_id: int, H: int, Hkv: int, D: int, rot_dim: int, cos, sin, position_ids, cu_seqlens_q,
+             qk_norm=None):
     """Rotates q and k of `qkv` [T, (H + 2 Hkv) D] (cos is None: no rotary) and scatters k and v to their page slots;
     returns the activation whose first H D columns attention reads.  A fresh prefill writes page-wise, and so does one
     behind reused pages (`past_lens`); everything else per token, which at decode sizes also finishes the split-K sum (and
-    the bias) of a `native.Partial`."""
+    the bias) of a `native.Partial`.  qk_norm = (q_w, k_w, eps): the per-head RMSNorm of q and k in front of the rotation
+    (Qwen3), done by the same launch in each of the three forms."""
     k_pool, v_pool, scales = layer_pools(kv, layer_id)
+    if qk_norm is not None:
+        scales = dict(scales, qk_norm=qk_norm)
     if kv.fresh_prefill and not isinstance(qkv, native.Partial):
         return native.rope_kv_write_prefill(qkv, cos, sin, position_ids, cu_seqlens_q, kv.block_tables, k_pool, v_pool,
                                             kv.max_q_len, H, Hkv, D, rot_dim, **scales)

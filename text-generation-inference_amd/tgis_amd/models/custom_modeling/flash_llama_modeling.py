@@ -102,6 +102,21 @@ def rope_settings(config):
     raise ValueError(f"rope_scaling of type {kind} is not supported")
 
 
+def attention_biases(config):
+    """(q/k/v bias, o_proj bias).  llama and mistral carry one switch, `attention_bias`, for all four projections; Qwen2 has a
+    bias on q, k and v and none on o_proj, whatever its config says; Qwen3 follows its `attention_bias` (false in every
+    released checkpoint) like llama."""
+    if getattr(config, "model_type", None) == "qwen2":
+        return True, False
+    bias = bool(getattr(config, "attention_bias", False))  # (a Mistral config carries neither bias field)
+    return bias, bias
+
+
+def has_qk_norm(config) -> bool:
+    """Qwen3: a per-head RMSNorm (self_attn.q_norm / k_norm, eps rms_norm_eps) between the qkv projection and the rotation."""
+    return getattr(config, "model_type", None) == "qwen3"
+
+
 class FlashLlamaAttention:
     def __init__(self, prefix: str, config, weights):
         self.num_heads = config.num_attention_heads
@@ -119,13 +134,24 @@ class FlashLlamaAttention:
         assert config.num_key_value_heads % tp == 0, "num_key_value_heads must be divisible by the shard count"
         self.num_heads = self.num_heads // tp
         self.num_key_value_heads = config.num_key_value_heads // tp
-        attention_bias = getattr(config, "attention_bias", False)  # (a Mistral config carries neither bias field)
+        qkv_bias, o_bias = attention_biases(config)
         self.query_key_value = TensorParallelColumnLinear.load_multi(
             config, prefixes=[f"{prefix}.q_proj", f"{prefix}.k_proj", f"{prefix}.v_proj"], dim=0, weights=weights,
-            bias=attention_bias)
-        self.o_proj = TensorParallelRowLinear.load(config, prefix=f"{prefix}.o_proj", weights=weights, bias=attention_bias)
-        # where the linear has that launch, decode steps of up to 64 rows rotate q / k and write the cache in the GEMM epilogue
-        self.query_key_value.declare_rope_heads(self.num_heads, self.num_key_value_heads, self.head_size)
+            bias=qkv_bias)
+        self.o_proj = TensorParallelRowLinear.load(config, prefix=f"{prefix}.o_proj", weights=weights, bias=o_bias)
+        self.qk_norm = None
+        if has_qk_norm(config):
+            # [head_dim] each, the same on every tensor-parallel rank, never quantised.  The norm sits between the GEMM and
+            # the rotation, so the GEMM + rope launch (and the fragment-order operands it is chosen with) cannot serve this
+            # model: no rope heads are declared, every step takes write_kv, whose launches carry the norm.
+            self.qk_norm = (weights.get_tensor(f"{prefix}.q_norm.weight").contiguous(),
+                            weights.get_tensor(f"{prefix}.k_norm.weight").contiguous(), float(config.rms_norm_eps))
+            if self.head_size not in (64, 96, 128):
+                raise NotImplementedError(f"q_norm / k_norm with head_dim {self.head_size}: the kernels serve 64, 96 and 128")
+        else:
+            # where the linear has that launch, decode steps of up to 64 rows rotate q / k and write the cache in the GEMM
+            # epilogue
+            self.query_key_value.declare_rope_heads(self.num_heads, self.num_key_value_heads, self.head_size)
 
     def project_qkv(self, hidden_states, cos, sin, position_ids, cu_seqlens_q, layer_id: int, kv: KVArgs):
         """qkv GEMM, rotation of q and k in place, k and v scattered to their page slots (reference :251-268,282)."""
@@ -139,7 +165,7 @@ class FlashLlamaAttention:
                                                      **scales)
         # [T, (H + 2 Hkv) D]; at decode sizes the split-K sum of the GPTQ GEMM is finished inside the rope kernel
         qkv = self.query_key_value(hidden_states, partial=True)
-        return write_kv(qkv, kv, layer_id, H, Hkv, D, D, cos, sin, position_ids, cu_seqlens_q)
+        return write_kv(qkv, kv, layer_id, H, Hkv, D, D, cos, sin, position_ids, cu_seqlens_q, qk_norm=self.qk_norm)
 
     def attend(self, qkv, cu_seqlens_q, layer_id: int, kv: KVArgs):
         """Attention of the rotated q over the layer's cache pages (reference :271-295): [T, H D]."""

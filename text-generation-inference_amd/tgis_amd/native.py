@@ -115,6 +115,11 @@ SIGNATURES = {
                                                _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "tgis_rope_kv_write_prefill_at_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64,
                                                    _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _vp] + _KV8_ARGS + [_vp]),
+    "tgis_rope_kv_write_qknorm": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _vp, _vp, _vp, _c_f, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int] + _KV8_ARGS + [_vp]),
+    "tgis_rope_kv_write_prefill_qknorm": (_c_int, [_vp, _c_i64, _vp, _vp, _c_f, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp,
+                                                   _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int]
+                                          + _KV8_ARGS + [_vp]),
     "tgis_attn_num_splits": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _c_i64]),
     "tgis_attn_num_splits_q": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _c_i64]),
     "tgis_attn_workspace_bytes": (_c_i64, [_c_i64, _c_int, _c_int, _c_int, _c_int]),
@@ -211,6 +216,15 @@ def _call_kv(name: str, args: tuple, k_pool, v_pool, kv_scales, tail: tuple = ()
         name += "_kv8"
         args += (KV_FP8_E4M3, float(k_scale), float(v_scale))
     _check(getattr(load_library(), name)(*(args + tail)), name)
+
+
+def _kv_args(k_pool, v_pool, kv_scales) -> tuple:
+    """(kv_dtype, k_scale, v_scale) of an entry point that takes the cache element in its one signature."""
+    if not kv_is8(k_pool):
+        return (KV_MODEL, 1.0, 1.0)
+    assert kv_is8(v_pool) and k_pool.dtype == v_pool.dtype, "k and v pools must both hold e4m3 codes"
+    k_scale, v_scale = (1.0, 1.0) if kv_scales is None else kv_scales
+    return (KV_FP8_E4M3, float(k_scale), float(v_scale))
 
 
 def dtype_code(dt: torch.dtype) -> int:
@@ -1020,11 +1034,47 @@ def layernorm2_residual(residual, a, b, w1, b1, eps: float, w2=None, b2=None, re
 
 
 # ---- rope + kv write, attention --------------------------------------------------------------------------
+def _qk_norm_args(qk_norm, D: int, dtype) -> tuple:
+    """(q_w, k_w, eps) of a `qk_norm` keyword as the arguments of the *_qknorm entry points."""
+    q_w, k_w, eps = qk_norm
+    for w in (q_w, k_w):
+        assert w.dtype == dtype and w.is_contiguous() and w.numel() == D, "q / k norm weights are [head_dim] of the model dtype"
+    return (_ptr(q_w), _ptr(k_w), float(eps))
+
+
+def _rope_kv_write_qknorm(qkv, qk_norm, cos, sin, positions, slots, k_pool, v_pool, H, Hkv, D, rot_dim, kv_scales):
+    if isinstance(qkv, Partial):
+        out = torch.empty((qkv.M, qkv.N), dtype=qkv.dtype, device=qkv.device)
+        src = (_ptr(qkv.slabs), qkv.S, qkv.ld, _ptr(qkv.bias))
+    else:
+        assert qkv.dim() == 2 and qkv.stride(1) == 1
+        out, src = qkv, (None, 0, 0, None)
+    _check(load_library().tgis_rope_kv_write_qknorm(
+        _ptr(out), out.stride(0), *src, *_qk_norm_args(qk_norm, D, out.dtype), _ptr(cos), _ptr(sin), _ptr(positions),
+        _ptr(slots), _ptr(k_pool), _ptr(v_pool), out.shape[0], H, Hkv, D, rot_dim, dtype_code(out.dtype),
+        *_kv_args(k_pool, v_pool, kv_scales), _stream()), "tgis_rope_kv_write_qknorm")
+    return out
+
+
+def _rope_kv_write_prefill_qknorm(qkv, qk_norm, cos, sin, positions, cu_seqlens, past_lens, block_tables, k_pool, v_pool,
+                                  max_len, H, Hkv, D, rot_dim, kv_scales):
+    _check(load_library().tgis_rope_kv_write_prefill_qknorm(
+        _ptr(qkv), qkv.stride(0), *_qk_norm_args(qk_norm, D, qkv.dtype), _ptr(cos), _ptr(sin), _ptr(positions),
+        _ptr(cu_seqlens), _ptr(past_lens), _ptr(block_tables), block_tables.shape[1], _ptr(k_pool), _ptr(v_pool),
+        block_tables.shape[0], qkv.shape[0], max_len, H, Hkv, D, rot_dim, dtype_code(qkv.dtype),
+        *_kv_args(k_pool, v_pool, kv_scales), _stream()), "tgis_rope_kv_write_prefill_qknorm")
+    return qkv
+
+
 def rope_kv_write(qkv, cos, sin, positions, slots, k_pool, v_pool, H: int, Hkv: int, D: int, rot_dim: int,
-                  kv_scales=(1.0, 1.0)):
+                  kv_scales=(1.0, 1.0), qk_norm=None):
     """Rotates q,k in place and writes k,v to the cache.  `qkv` may be a Partial: the reduced, rotated activation is
     then materialised into a fresh [T, (H+2Hkv)D] tensor, which is returned (the plain form returns qkv itself).
-    One-byte pools (kv_is8) receive e4m3 codes of k / k_scale and v / v_scale, kv_scales = (k_scale, v_scale)."""
+    One-byte pools (kv_is8) receive e4m3 codes of k / k_scale and v / v_scale, kv_scales = (k_scale, v_scale).
+    qk_norm = (q_w, k_w, eps): every q and k head is RMS-normalised over its D elements in front of the rotation
+    (tgis_rope_kv_write_qknorm; Qwen3)."""
+    if qk_norm is not None:
+        return _rope_kv_write_qknorm(qkv, qk_norm, cos, sin, positions, slots, k_pool, v_pool, H, Hkv, D, rot_dim, kv_scales)
     if isinstance(qkv, Partial):
         T = qkv.M
         out = torch.empty((T, qkv.N), dtype=qkv.dtype, device=qkv.device)
@@ -1042,9 +1092,12 @@ def rope_kv_write(qkv, cos, sin, positions, slots, k_pool, v_pool, H: int, Hkv: 
 
 
 def rope_kv_write_prefill(qkv, cos, sin, positions, cu_seqlens, block_tables, k_pool, v_pool, max_len: int, H: int,
-                          Hkv: int, D: int, rot_dim: int, kv_scales=(1.0, 1.0)):
+                          Hkv: int, D: int, rot_dim: int, kv_scales=(1.0, 1.0), qk_norm=None):
     """rope_kv_write for a fresh prefill (token i of a sequence = cache position i): page-wise cache writes."""
     assert qkv.dim() == 2 and qkv.stride(1) == 1 and block_tables.is_contiguous()
+    if qk_norm is not None:
+        return _rope_kv_write_prefill_qknorm(qkv, qk_norm, cos, sin, positions, cu_seqlens, None, block_tables, k_pool,
+                                             v_pool, max_len, H, Hkv, D, rot_dim, kv_scales)
     B = block_tables.shape[0]
     args = (_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(positions), _ptr(cu_seqlens), _ptr(block_tables),
             block_tables.shape[1], _ptr(k_pool), _ptr(v_pool), B, qkv.shape[0], max_len, H, Hkv, D, rot_dim,
@@ -1062,7 +1115,7 @@ def past_lens_tensor(past_lens, device) -> torch.Tensor:
 
 
 def rope_kv_write_prefill_at(qkv, cos, sin, positions, cu_seqlens, block_tables, k_pool, v_pool, max_len: int, H: int,
-                             Hkv: int, D: int, rot_dim: int, past_lens, kv_scales=(1.0, 1.0)):
+                             Hkv: int, D: int, rot_dim: int, past_lens, kv_scales=(1.0, 1.0), qk_norm=None):
     """rope_kv_write_prefill behind a cached prefix: token i of sequence b = cache position past_lens[b] + i.  `past_lens`
     is a list of host ints or the tensor `past_lens_tensor` made of one (a forward makes it once for all its layers);
     `cu_seqlens` and `max_len` describe the suffix tokens in `qkv`.  Pages in front of past_lens[b] / 32 are not written."""
@@ -1071,6 +1124,9 @@ def rope_kv_write_prefill_at(qkv, cos, sin, positions, cu_seqlens, block_tables,
         past_lens = past_lens_tensor(past_lens, qkv.device)
     B = block_tables.shape[0]
     assert past_lens.dtype == torch.int32 and past_lens.is_contiguous() and past_lens.numel() == B
+    if qk_norm is not None:
+        return _rope_kv_write_prefill_qknorm(qkv, qk_norm, cos, sin, positions, cu_seqlens, past_lens, block_tables, k_pool,
+                                             v_pool, max_len, H, Hkv, D, rot_dim, kv_scales)
     args = (_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(positions), _ptr(cu_seqlens), _ptr(block_tables),
             block_tables.shape[1], _ptr(k_pool), _ptr(v_pool), B, qkv.shape[0], max_len, H, Hkv, D, rot_dim,
             dtype_code(qkv.dtype), _stream())

@@ -56,7 +56,13 @@ def check_lora_world(lora_slots: int, tp_world: int, spec_tokens: int) -> None:
 
 
 def check_lora_model(lora_slots: int, model) -> None:
-    """Adapters are served by the Llama model class alone (model types llama and mistral)."""
+    """Adapters are served by the Llama model class alone, for the model types llama and mistral: not for qwen2 / qwen3, which
+    it serves too."""
+    model_type = getattr(getattr(model, "config", None), "model_type", None)
+    if lora_slots > 0 and model_type in ("qwen2", "qwen3"):
+        raise NotImplementedError(
+            f"lora_slots={lora_slots}: LoRA adapters are not served for model type {model_type}: the adapter forward "
+            "(forward_lora) does not carry its q/k/v bias split and q / k norm (DESIGN.md §8); set lora_slots=0")
     if lora_slots > 0 and not hasattr(model, "enable_lora"):
         raise NotImplementedError(
             f"lora_slots={lora_slots}: {type(model).__name__} does not serve LoRA adapters, only the Llama class (llama, "

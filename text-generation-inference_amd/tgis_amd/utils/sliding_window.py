@@ -6,8 +6,29 @@ the window on, FlashCausalLM sets it on the KVArgs of the fresh prefill and of t
 from typing import Optional
 
 
+USE_FLAG_TYPES = ("qwen2", "qwen3")
+
+
+def use_sliding_window(config) -> bool:
+    """Whether `config.sliding_window` is to be read at all.  Qwen2 / Qwen3 configs carry `sliding_window` next to
+    `use_sliding_window: false`: for these two model types the window counts only when the flag is true, and then the model is
+    refused, because it windows some layers and not others (`max_window_layers` / `layer_types`), which no launch here does
+    (DESIGN.md section 8).  Every other model type: true."""
+    if getattr(config, "model_type", None) not in USE_FLAG_TYPES:
+        return True
+    if not getattr(config, "use_sliding_window", False):
+        return False
+    raise NotImplementedError(
+        f"{config.model_type} with use_sliding_window = true is not served: its `layer_types` / `max_window_layers` window "
+        "some layers and not others, and per-layer windows are out of scope (DESIGN.md section 8); serve the checkpoint with "
+        "use_sliding_window = false")
+
+
 def parse_sliding_window(config) -> Optional[int]:
-    """W keys per q row, or None: `sliding_window` absent, null or 0 is off."""
+    """W keys per q row, or None: `sliding_window` absent, null or 0 is off, and so is one that `use_sliding_window` says is
+    not in use."""
+    if not use_sliding_window(config):
+        return None
     w = getattr(config, "sliding_window", None)
     if w is None or w == 0:
         return None
