@@ -287,6 +287,35 @@ int tgis_moe_gptq_gemm_down(const void* h, int64_t ldh, const void* images, int6
                             int E, int top_k, int dtype, int form, float* scratch, int64_t scratch_bytes, void* out,
                             int64_t ldo, void* stream);
 
+/* ---- routed expert MLP for up to 128 experts (Qwen3-MoE; csrc/moe_tiles.h) ----
+ * tgis_moe_route_tiles: tgis_moe_route's contract and its five arrays for 2 <= E <= 128, 1 <= top_k <= min(E, 8), in three
+ * launches whose grids depend on T alone (a token per wave; per-block expert histograms; one scan block; a scatter that ranks
+ * each block's slots by ballot and popcount).  renorm 1: the chosen probabilities are divided by their sum (for E <= 64 all
+ * five arrays are bit-identical to tgis_moe_route's); renorm 0: the probabilities of the full softmax are left as they are
+ * (norm_topk_prob false).  It also writes the TILE LIST the tile GEMMs walk: tiles is int32 [1 + tile_bound][4],
+ * tiles[0] = {n_tiles, rows per tile (64), 0, 0}, tiles[1 + i] = {expert, first position in slot_rows, rows (1 .. 64), 0}:
+ * every expert's range of slot_rows cut into consecutive tiles, experts ascending.  tile_bound >= tgis_moe_tile_bound(T, E,
+ * top_k) = ceil(T top_k / 64) + min(E, T top_k), which bounds n_tiles without reading anything (at most 65535: cut longer
+ * prefills into chunks).  workspace: tgis_moe_route_tiles_bytes bytes (the [blocks][E] histogram). */
+int64_t tgis_moe_tile_bound(int64_t T, int E, int top_k);
+int64_t tgis_moe_route_tiles_bytes(int64_t T, int E, int top_k);
+int tgis_moe_route_tiles(const float* logits, int64_t ld, int64_t T, int E, int top_k, int renorm, int32_t* expert_ids,
+                         float* expert_w, int32_t* counts, int32_t* offsets, int32_t* slot_rows, int32_t* tiles,
+                         int64_t tile_bound, int32_t* workspace, int64_t workspace_bytes, void* stream);
+/* The contracts of tgis_moe_gemm_up / tgis_moe_gemm_down (same images, same epilogues, same slabs and scratch sizes, same
+ * run-to-run bytes; f16 / bf16) for E <= 128 over a routing of tgis_moe_route_tiles.  Grid (ceil(N / 128), tile_bound): a
+ * block past n_tiles returns at once, the others own 64 rows of one expert x 128 image columns, gather the tile's activation
+ * rows once per k64-step into LDS in fragment order and stream each wave's 32 columns of weights over the whole k range.  Up
+ * to a few tokens (a host rule on T, K, N, E, top_k alone) both launch tgis_moe_gemm_*'s kernel over grid (N / 32, E) instead. */
+int tgis_moe_tile_gemm_up(const void* x, int64_t ldx, const void* images, int64_t expert_stride, const int32_t* offsets,
+                          const int32_t* slot_rows, const int32_t* tiles, int64_t tile_bound, void* h, int64_t ldh, int64_t T,
+                          int64_t K, int64_t N, int E, int top_k, int dtype, void* stream);
+int64_t tgis_moe_tile_gemm_down_bytes(int64_t T, int64_t N, int top_k, int form);
+int tgis_moe_tile_gemm_down(const void* h, int64_t ldh, const void* images, int64_t expert_stride, const int32_t* offsets,
+                            const int32_t* slot_rows, const int32_t* tiles, int64_t tile_bound, const float* expert_w,
+                            int64_t T, int64_t K, int64_t N, int E, int top_k, int dtype, int form, float* scratch,
+                            int64_t scratch_bytes, void* out, int64_t ldo, void* stream);
+
 /* ---- per-request LoRA adapters (csrc/lora.hip) ----
  * A wrapped linear computes y[t] = W x[t] + scale_s B_s (A_s x[t]) with s = slot[t]; a row with slot[t] = -1 keeps W x[t].
  * Shared limits: 0 <= T <= 64 rows, 1 <= S <= 32 slots, 1 <= P <= 3 projections fused into the base linear, max_rank a

@@ -351,8 +351,9 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(const float* __restric
     for (int j = 0; j < 4; ++j) out[t * ldo + c4 + j] = dense::finish_out<T>(v[j], 0);
 }
 
-int moe_check_routing(const char* fn, int64_t T, int64_t E, int64_t top_k) {
-    TGIS_CHECK_ARG(E >= 2 && E <= MOE_MAX_E, "%s: 2 <= E <= %d (E=%ld)", fn, MOE_MAX_E, (long)E);
+// max_e: MOE_MAX_E for the entry points of this file, TILE_MAX_E for those of moe_tiles.h
+int moe_check_routing(const char* fn, int64_t T, int64_t E, int64_t top_k, int max_e = MOE_MAX_E) {
+    TGIS_CHECK_ARG(E >= 2 && E <= max_e, "%s: 2 <= E <= %d (E=%ld)", fn, max_e, (long)E);
     TGIS_CHECK_ARG(top_k >= 1 && top_k <= std::min<int64_t>(E, MOE_MAX_TOPK), "%s: 1 <= top_k <= min(E, %d) (top_k=%ld)", fn,
                    MOE_MAX_TOPK, (long)top_k);
     TGIS_CHECK_ARG(T >= 0 && T * top_k < (1ll << 31), "%s: T (%ld) must be >= 0 with T * top_k below 2^31", fn, (long)T);
@@ -361,8 +362,9 @@ int moe_check_routing(const char* fn, int64_t T, int64_t E, int64_t top_k) {
 
 // G == 0: 16-bit images of tgis_dense_prepare; G >= 1: int4 images of tgis_gptq_prepare with G groups.
 int moe_check_gemm(const char* fn, const void* x, int64_t ldx, const void* images, int64_t stride, const void* offsets,
-                   const void* slot_rows, int64_t T, int64_t K, int64_t N, int64_t E, int64_t top_k, int dtype, int64_t G = 0) {
-    const int rc = moe_check_routing(fn, T, E, top_k);
+                   const void* slot_rows, int64_t T, int64_t K, int64_t N, int64_t E, int64_t top_k, int dtype, int64_t G = 0,
+                   int max_e = MOE_MAX_E) {
+    const int rc = moe_check_routing(fn, T, E, top_k, max_e);
     if (rc != TGIS_OK) return rc;
     TGIS_CHECK_ARG(x && images && offsets && slot_rows, "%s: null tensor", fn);
     TGIS_CHECK_ARG(dtype == TGIS_F16 || dtype == TGIS_BF16, "%s: bad dtype", fn);
@@ -568,3 +570,6 @@ extern "C" int tgis_debug_moe_gptq_plan(int which, int64_t T, int64_t K, int64_t
     info[12] = (int)(stride & 0x7fffffff), info[13] = (int)(stride >> 31);
     return TGIS_OK;
 }
+
+// tgis_moe_route_tiles, tgis_moe_tile_gemm_up / _down: routing and grouped expert GEMMs for up to 128 experts
+#include "moe_tiles.h"

@@ -150,6 +150,59 @@ def mixtral_tensors(config, seed: int, device="cpu", dtype=torch.bfloat16, head_
     return t
 
 
+class Qwen3MoeConfig:
+    """The fields of HF's Qwen3MoeConfig that FlashQwen3MoeForCausalLM reads; the defaults are Qwen3-30B-A3B's."""
+    model_type = "qwen3_moe"
+
+    def __init__(self, vocab_size=151936, hidden_size=2048, moe_intermediate_size=768, num_hidden_layers=48,
+                 num_attention_heads=32, num_key_value_heads=4, head_dim=128, num_experts=128, num_experts_per_tok=8,
+                 norm_topk_prob=True, max_position_embeddings=40960, rms_norm_eps=1e-6, rope_theta=1e6):
+        self.vocab_size, self.hidden_size, self.moe_intermediate_size = vocab_size, hidden_size, moe_intermediate_size
+        self.num_hidden_layers, self.num_attention_heads = num_hidden_layers, num_attention_heads
+        self.num_key_value_heads, self.head_dim = num_key_value_heads, head_dim
+        self.num_experts, self.num_experts_per_tok, self.norm_topk_prob = num_experts, num_experts_per_tok, norm_topk_prob
+        self.max_position_embeddings, self.rms_norm_eps, self.rope_theta = max_position_embeddings, rms_norm_eps, rope_theta
+        self.intermediate_size = moe_intermediate_size  # (the benchmarks' byte accounting reads this name)
+        self.decoder_sparse_step, self.mlp_only_layers = 1, []
+        self.hidden_act, self.attention_bias = "silu", False
+        self.sliding_window, self.use_sliding_window = None, False
+        self.tie_word_embeddings = False
+        self.pad_token_id, self.bos_token_id, self.eos_token_id = None, 1, 2
+
+
+def qwen3_moe_tensors(config, seed: int, device="cpu", dtype=torch.bfloat16, head_scale: float = 1.0) -> Dict[str, torch.Tensor]:
+    """Seeded full Qwen3-MoE checkpoint under the published names (mlp.gate, mlp.experts.N.gate_proj / up_proj / down_proj,
+    self_attn.q_norm / k_norm): N(0, 1/sqrt(fan_in)) linears, so that the router's logits spread over the experts, unit
+    RMSNorms, q / k norm weights in [0.5, 2]."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    E, I, V = config.hidden_size, config.moe_intermediate_size, config.vocab_size
+    D, H, Hkv = config.head_dim, config.num_attention_heads, config.num_key_value_heads
+    t: Dict[str, torch.Tensor] = {}
+
+    def lin(name, n, k, scale=1.0):
+        t[f"{name}.weight"] = (torch.randn(n, k, generator=g, device=device) * (k ** -0.5 * scale)).to(dtype)
+
+    t["model.embed_tokens.weight"] = torch.randn(V, E, generator=g, device=device).to(dtype)
+    for i in range(config.num_hidden_layers):
+        p = f"model.layers.{i}"
+        lin(f"{p}.self_attn.q_proj", H * D, E)
+        lin(f"{p}.self_attn.k_proj", Hkv * D, E)
+        lin(f"{p}.self_attn.v_proj", Hkv * D, E)
+        lin(f"{p}.self_attn.o_proj", E, H * D)
+        for n in ("q_norm", "k_norm"):
+            t[f"{p}.self_attn.{n}.weight"] = (0.5 + 1.5 * torch.rand(D, generator=g, device=device)).to(dtype)
+        lin(f"{p}.mlp.gate", config.num_experts, E)
+        for e in range(config.num_experts):
+            lin(f"{p}.mlp.experts.{e}.gate_proj", I, E)
+            lin(f"{p}.mlp.experts.{e}.up_proj", I, E)
+            lin(f"{p}.mlp.experts.{e}.down_proj", E, I)
+        t[f"{p}.input_layernorm.weight"] = torch.ones(E, device=device, dtype=dtype)
+        t[f"{p}.post_attention_layernorm.weight"] = torch.ones(E, device=device, dtype=dtype)
+    t["model.norm.weight"] = torch.ones(E, device=device, dtype=dtype)
+    lin("lm_head", V, E, head_scale)
+    return t
+
+
 class BigCodeConfig:
     """The fields of HF's GPTBigCodeConfig that FlashSantacoderForCausalLM reads (multi-query attention)."""
     model_type = "gpt_bigcode"

@@ -2,7 +2,8 @@
 (mirrors inference_engine/tgis_native.py:23-139 of the reference; model families of the configs in
 BASELINE.json: llama, and gpt_bigcode when flash_santacoder_modeling is present; gpt_neox; mistral, whose tensors carry
 Llama's names and whose sliding window FlashCausalLM reads from the config; mixtral, which is mistral around a routed expert
-MLP; qwen2 and qwen3, which are Llama with a q/k/v bias resp. a per-head q/k RMSNorm)."""
+MLP; qwen2 and qwen3, which are Llama with a q/k/v bias resp. a per-head q/k RMSNorm; qwen3_moe, which is qwen3 around a routed expert MLP of up
+to 128 experts)."""
 import os
 from typing import Any, Optional
 
@@ -14,7 +15,7 @@ from tgis_amd.utils.dist import initialize_torch_distributed
 from tgis_amd.utils.hub import local_weight_files
 from tgis_amd.utils.weights import Weights
 
-FLASH_TYPES = ["llama", "gpt_bigcode", "gpt_neox", "mistral", "mixtral", "qwen2", "qwen3"]
+FLASH_TYPES = ["llama", "gpt_bigcode", "gpt_neox", "mistral", "mixtral", "qwen2", "qwen3", "qwen3_moe"]
 
 
 def _barrier(group):
@@ -40,6 +41,13 @@ def model_class_for(config):
         from tgis_amd.models.custom_modeling.flash_mixtral_modeling import FlashMixtralForCausalLM
 
         return FlashMixtralForCausalLM, aliases
+    if model_type == "qwen3_moe":
+        if getattr(config, "tie_word_embeddings", False):
+            aliases = {"lm_head.weight": ["model.embed_tokens.weight"]}
+        from tgis_amd.models.custom_modeling.flash_qwen3_moe_modeling import FlashQwen3MoeForCausalLM, check_qwen3_moe_config
+
+        check_qwen3_moe_config(config, getattr(config, "quantize", None))  # a config this class does not serve is refused here
+        return FlashQwen3MoeForCausalLM, aliases
     if model_type == "gpt_bigcode":
         from tgis_amd.models.custom_modeling.flash_santacoder_modeling import FlashSantacoderForCausalLM
 

@@ -113,8 +113,9 @@ def attention_biases(config):
 
 
 def has_qk_norm(config) -> bool:
-    """Qwen3: a per-head RMSNorm (self_attn.q_norm / k_norm, eps rms_norm_eps) between the qkv projection and the rotation."""
-    return getattr(config, "model_type", None) == "qwen3"
+    """Qwen3 and Qwen3-MoE: a per-head RMSNorm (self_attn.q_norm / k_norm, eps rms_norm_eps) between the qkv projection and the
+    rotation."""
+    return getattr(config, "model_type", None) in ("qwen3", "qwen3_moe")
 
 
 class FlashLlamaAttention:

@@ -274,13 +274,15 @@ class FlashMixtralLayer:
 
 
 class FlashMixtralModel:
+    layer_class = FlashMixtralLayer  # (flash_qwen3_moe_modeling.py walks its own layers with this class)
+
     def __init__(self, config, weights):
         self.config = config
         process_group = weights.process_group
         self.tp_rank = process_group.rank()
         self.tp_world_size = process_group.size()
         self.embed_tokens = TensorParallelEmbedding(prefix="model.embed_tokens", weights=weights)
-        self.layers = [FlashMixtralLayer(i, config, weights) for i in range(config.num_hidden_layers)]
+        self.layers = [self.layer_class(i, config, weights) for i in range(config.num_hidden_layers)]
         self.norm = LlamaRMSNorm(prefix="model.norm", weights=weights, eps=config.rms_norm_eps)
         self.head_size = self.layers[0].self_attn.head_size
         self.num_heads = self.layers[0].self_attn.num_heads

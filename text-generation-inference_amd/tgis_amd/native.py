@@ -82,6 +82,15 @@ SIGNATURES = {
                                        _c_int, _c_int, _vp]),
     "tgis_moe_gptq_gemm_down": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int,
                                          _c_int, _c_int, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "tgis_moe_tile_bound": (_c_i64, [_c_i64, _c_int, _c_int]),
+    "tgis_moe_route_tiles_bytes": (_c_i64, [_c_i64, _c_int, _c_int]),
+    "tgis_moe_route_tiles": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp,
+                                      _c_i64, _vp]),
+    "tgis_moe_tile_gemm_up": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _c_i64,
+                                       _c_int, _c_int, _c_int, _vp]),
+    "tgis_moe_tile_gemm_down_bytes": (_c_i64, [_c_i64, _c_i64, _c_int, _c_int]),
+    "tgis_moe_tile_gemm_down": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _c_int,
+                                         _c_int, _c_int, _c_int, _vp, _c_i64, _vp, _c_i64, _vp]),
     "tgis_lora_a_bytes": (_c_i64, [_c_i64, _c_int, _c_int]),
     "tgis_lora_b_bytes": (_c_i64, [_c_i64, _c_int]),
     "tgis_lora_group": (_c_int, [_vp, _c_i64, _c_int, _vp, _vp, _vp, _vp]),
@@ -701,6 +710,9 @@ class Routing:
     """What moe_route leaves on the device for T tokens: expert_ids int32 [T, top_k], expert_w f32 [T, top_k], counts int32
     [E], offsets int32 [E + 1], slot_rows int32 [T top_k] (slots t * top_k + k grouped by expert, ascending inside each)."""
 
+    tiles = None  # moe_route_tiles only: the tile list, int32 [1 + tile_bound, 4]
+    tile_bound = 0
+
     def __init__(self, T: int, E: int, top_k: int, device):
         self.T, self.E, self.top_k = T, E, top_k
         self.expert_ids = torch.empty((T, top_k), dtype=torch.int32, device=device)
@@ -752,6 +764,81 @@ def moe_gemm_down(h: torch.Tensor, w: MoeWeights, r: Routing, partial: bool = Fa
     p = Partial(scratch, r.top_k, (w.N + 31) // 32 * 32, r.T, w.N, None)
     p.dtype = w.dtype
     return p
+
+
+# ---- routed expert MLP for up to 128 experts (Qwen3-MoE; csrc/moe_tiles.h) ---------------------------------------------
+def moe_route_tiles(logits: torch.Tensor, top_k: int, renorm: bool = True) -> Routing:
+    """moe_route for 2 <= E <= 128 in three launches whose work is spread over the tokens, renormalising the chosen weights
+    or (renorm False: norm_topk_prob false) leaving the full softmax's.  The Routing also carries the tile list the tile
+    GEMMs walk: tiles[0] = (n_tiles, rows per tile, 0, 0), tiles[1 + i] = (expert, first position in slot_rows, rows, 0),
+    experts ascending, n_tiles <= tile_bound."""
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and (logits.shape[0] == 0 or logits.stride(1) == 1)
+    T, E = logits.shape
+    lib = load_library()
+    r = Routing(T, E, top_k, logits.device)
+    r.tile_bound = lib.tgis_moe_tile_bound(T, E, top_k)
+    r.tiles = torch.empty((1 + r.tile_bound, 4), dtype=torch.int32, device=logits.device)
+    nbytes = lib.tgis_moe_route_tiles_bytes(T, E, top_k)
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=logits.device)
+    _check(lib.tgis_moe_route_tiles(_ptr(logits), logits.stride(0), T, E, top_k, int(bool(renorm)), _ptr(r.expert_ids),
+                                    _ptr(r.expert_w), _ptr(r.counts), _ptr(r.offsets), _ptr(r.slot_rows), _ptr(r.tiles),
+                                    r.tile_bound, _ptr(ws), nbytes, _stream()), "tgis_moe_route_tiles")
+    return r
+
+
+def moe_tile_gemm_up(x: torch.Tensor, w: MoeWeights, r: Routing, out=None) -> torch.Tensor:
+    """moe_gemm_up over a routing of moe_route_tiles: h [T top_k, I]."""
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == w.dtype and x.shape == (r.T, w.K) and w.flags & 1 and w.E == r.E
+    assert r.tiles is not None, "the tile GEMMs need a routing of moe_route_tiles"
+    if out is None:
+        out = torch.empty((r.T * r.top_k, w.N // 2), dtype=w.dtype, device=x.device)
+    _check(load_library().tgis_moe_tile_gemm_up(_ptr(x), x.stride(0), _ptr(w.image), w.stride, _ptr(r.offsets),
+                                                _ptr(r.slot_rows), _ptr(r.tiles), r.tile_bound, _ptr(out), out.stride(0), r.T,
+                                                w.K, w.N, w.E, r.top_k, dtype_code(w.dtype), _stream()),
+           "tgis_moe_tile_gemm_up")
+    return out
+
+
+def moe_tile_gemm_down(h: torch.Tensor, w: MoeWeights, r: Routing, partial: bool = False):
+    """moe_gemm_down over a routing of moe_route_tiles: a Partial with S = top_k (partial, T <= PARTIAL_MAX_M) or the finished
+    [T, hidden] tensor in the model dtype, summed over k in fixed order."""
+    assert h.dim() == 2 and h.stride(1) == 1 and h.dtype == w.dtype and h.shape == (r.T * r.top_k, w.K)
+    assert not (w.flags & 1) and w.E == r.E and r.tiles is not None
+    lib = load_library()
+    form = 0 if partial else 1
+    assert not partial or r.T <= PARTIAL_MAX_M
+    nbytes = lib.tgis_moe_tile_gemm_down_bytes(r.T, w.N, r.top_k, form)
+    scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=h.device)
+    out = None if partial else torch.empty((r.T, w.N), dtype=w.dtype, device=h.device)
+    _check(lib.tgis_moe_tile_gemm_down(_ptr(h), h.stride(0), _ptr(w.image), w.stride, _ptr(r.offsets), _ptr(r.slot_rows),
+                                       _ptr(r.tiles), r.tile_bound, _ptr(r.expert_w), r.T, w.K, w.N, w.E, r.top_k,
+                                       dtype_code(w.dtype), form, _ptr(scratch), nbytes, _ptr(out), w.N, _stream()),
+           "tgis_moe_tile_gemm_down")
+    if not partial:
+        return out
+    p = Partial(scratch, r.top_k, (w.N + 31) // 32 * 32, r.T, w.N, None)
+    p.dtype = w.dtype
+    return p
+
+
+def moe_tile_plan(which: int, T: int, K: int, N: int, E: int, top_k: int) -> dict:
+    """tgis_debug_moe_tile_plan as a dict (which: 0 up, 1 down as slabs, 2 down finished); nothing is launched."""
+    info = (_c_int * 16)()
+    fn = load_library().tgis_debug_moe_tile_plan
+    fn.restype, fn.argtypes = _c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_int, _c_int, ctypes.POINTER(_c_int)]
+    _check(fn(which, T, K, N, E, top_k, info), "tgis_debug_moe_tile_plan")
+    names = ("grid_x", "grid_y", "threads", "lds_bytes", "rows", "columns", "slab_body", "combine_blocks", "scratch_lo",
+             "scratch_hi", "tile_bound", "route_blocks", "route_tokens", "route_bytes", "slab_max_tokens")
+    plan = dict(zip(names, info))
+    plan["scratch_bytes"] = plan.pop("scratch_lo") + (plan.pop("scratch_hi") << 31)
+    return plan
+
+
+def moe_tile_force(kernel: int) -> None:
+    """-1: the small-T rule; 0: the tile kernel; 1: the slab kernel body, whatever T (benchmarks and tests)."""
+    fn = load_library().tgis_debug_moe_tile_force
+    fn.restype, fn.argtypes = _c_int, [_c_int]
+    _check(fn(kernel), "tgis_debug_moe_tile_force")
 
 
 # group sizes the int4 expert kernels have a form for (rows per group; a single group, written -1 or K, is served too)

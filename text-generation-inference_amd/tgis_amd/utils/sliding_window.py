@@ -6,7 +6,7 @@ the window on, FlashCausalLM sets it on the KVArgs of the fresh prefill and of t
 from typing import Optional
 
 
-USE_FLAG_TYPES = ("qwen2", "qwen3")
+USE_FLAG_TYPES = ("qwen2", "qwen3", "qwen3_moe")
 
 
 def use_sliding_window(config) -> bool:
