@@ -344,6 +344,25 @@ int tgis_lora_shrink(const void* x, int64_t ldx, const void* a_images, int64_t a
 int tgis_lora_expand(const float* v, const void* b_images, int64_t b_stride, const int32_t* ranks, const float* scales,
                      const int32_t* offsets, const int32_t* rows, const int64_t* bounds, void* y, int64_t ldy, int64_t T,
                      int64_t N, int P, int S, int max_rank, int dtype, void* stream);
+/* The same delta for prefills of any length (csrc/lora_prefill.hip), over a TILE TABLE in place of the device grouping: a
+ * prefill's rows arrive request by request, so the host lists them.  tiles int32 [n_tiles][4] = (row0, nrows, slot, 0) on the
+ * device, 16-byte aligned: 1 <= nrows <= 64, rows row0 .. row0 + nrows - 1 all on `slot` (0 .. S-1); rows without an adapter
+ * are in no tile, and no row is in two.  A tile outside the T rows or the S slots is skipped.  Limits as above, but
+ * 0 <= T < 2^31 - 64 and 0 <= n_tiles <= 65535; T == 0 or n_tiles == 0 launches nothing.  The slot images, ranks, scales and
+ * bounds are the ones above, and so is the arithmetic: v stays fp32, base + delta is rounded to the model dtype once; the
+ * sums run in another order, so the two paths agree within the contract's bound, not bit for bit.  Grids are sized by
+ * n_tiles, nothing is read on the host, no float atomics: the same input gives the same bytes. */
+/* v[t, p, 0 .. round_up(rank_s, 16)) = A_s[p] x[t] in fp32 for every row t of the tiles; the rest of v fp32 [T, P, max_rank] is
+ * left alone.  One block per tile computes all P projections, so x is read once. */
+int tgis_lora_shrink_tiles(const void* x, int64_t ldx, const void* a_images, int64_t a_stride, const int32_t* ranks,
+                           const int32_t* tiles, int64_t n_tiles, float* v, int64_t T, int64_t K, int P, int S, int max_rank,
+                           int dtype, void* stream);
+/* y[t, n] = T(float(y[t, n]) + scale_s * sum_r v[t, p(n), r] B_s[n, r]) in place for every row t of the tiles, in fp32 on the
+ * fp32 matrix instructions.  Rows outside the tiles and columns at or past N are not touched; y is written in 16-byte
+ * vectors when its rows are 16-byte aligned (ldy % 8 == 0), element by element otherwise. */
+int tgis_lora_expand_tiles(const float* v, const void* b_images, int64_t b_stride, const int32_t* ranks, const float* scales,
+                           const int32_t* tiles, int64_t n_tiles, const int64_t* bounds, void* y, int64_t ldy, int64_t T,
+                           int64_t N, int P, int S, int max_rank, int dtype, void* stream);
 
 /* ---- fused residual-add + RMSNorm / LayerNorm (replaces dropout_layer_norm.dropout_add_ln_fwd,
  *      custom_modeling/flash_llama_modeling.py:132-152, utils/layers.py:376-396) ---------------- */

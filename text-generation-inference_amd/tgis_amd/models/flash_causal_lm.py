@@ -37,8 +37,8 @@ from tgis_amd.utils import mlp_speculator
 from tgis_amd.utils.kv_cache import (KV_SCALES_HEADROOM, PAGE, OutOfPages, PagedKVCache, agree_kv_cache_dtype,
                                      agree_kv_prefix_reuse, agree_kv_scales, kv_pool_dtype, kv_scales_stats,
                                      pages_for_budget, parse_kv_cache_dtype, parse_kv_prefix_reuse)
-from tgis_amd.utils.lora import (LoraAdapter, LoraArgs, LoraSlots, check_lora_model, check_lora_world, module_shapes,
-                                 parse_lora_max_rank, parse_lora_slots, release_slots)
+from tgis_amd.utils.lora import (LoraAdapter, LoraArgs, LoraSlots, check_lora_model, check_lora_world, lora_tile_table,
+                                 module_shapes, parse_lora_max_rank, parse_lora_slots, release_slots)
 from tgis_amd.utils.rank_group import RankGroup
 from tgis_amd.utils.sliding_window import check_window_options, parse_sliding_window
 from tgis_amd.utils.spec_decode import (check_spec_candidates, check_spec_world, check_tree_rows, fallback_cause,
@@ -802,18 +802,16 @@ class FlashCausalLM(Model):
 
     def _prefill_lora(self, batch: FlashCausalLMBatch, rows_per_request: List[int]) -> Optional[LoraArgs]:
         """The LoraArgs of a prefill whose request i brings rows_per_request[i] rows, None when no request carries an
-        adapter.  Up to 64 rows take the kernels (grouped on the device); longer forwards loop on the host over the
-        requests that carry one, whose rows are contiguous."""
+        adapter.  Up to 64 rows take the kernels that group them on the device; longer forwards take the tile kernels, over
+        a table of the requests that carry one (their rows are contiguous), built here and uploaded with the slots."""
         if not batch.has_lora():
             return None
         slots = np.repeat(np.asarray(batch.lora_slots, dtype=np.int32), rows_per_request)
         dev_slots = torch.from_numpy(slots).to(self.device, non_blocking=True)
         if slots.size <= native.LORA_MAX_T:
             return LoraArgs.grouped(dev_slots, self.lora_slots)
-        starts = np.concatenate([[0], np.cumsum(rows_per_request)])
-        ranges = [(int(starts[i]), int(starts[i + 1]), s) for i, s in enumerate(batch.lora_slots)
-                  if s >= 0 and rows_per_request[i] > 0]
-        return LoraArgs(slots=dev_slots, ranges=ranges)
+        tiles = native.LoraTiles(lora_tile_table(batch.lora_slots, rows_per_request), slots.size, self.device)
+        return LoraArgs(slots=dev_slots, tiles=tiles)
 
     def _prefill_fresh_forward(self, batch: FlashCausalLMBatch):
         lens = batch.input_lengths

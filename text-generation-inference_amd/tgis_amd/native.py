@@ -98,6 +98,10 @@ SIGNATURES = {
                                   _c_int, _vp]),
     "tgis_lora_expand": (_c_int, [_vp, _vp, _c_i64, _vp, _vp, _vp, _vp, ctypes.POINTER(_c_i64), _vp, _c_i64, _c_i64, _c_i64,
                                   _c_int, _c_int, _c_int, _c_int, _vp]),
+    "tgis_lora_shrink_tiles": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_int, _c_int,
+                                        _c_int, _c_int, _vp]),
+    "tgis_lora_expand_tiles": (_c_int, [_vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, ctypes.POINTER(_c_i64), _vp, _c_i64, _c_i64,
+                                        _c_i64, _c_int, _c_int, _c_int, _c_int, _vp]),
     "tgis_rmsnorm_residual":(_c_int, [_vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_f, _c_int, _vp]),
     "tgis_rmsnorm_residual_partial": (_c_int, [_vp, _c_int, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_f,
                                                _c_int, _vp]),
@@ -933,8 +937,7 @@ LORA_MAX_T, LORA_MAX_SLOTS, LORA_MAX_RANK = 64, 32, 64  # rows of the kernel pat
 class LoraImages:
     """The slot images of one linear (tgis_hip.h): A [S, P, max_rank, K] and B [S, max_rank / 16, N, 16] in the model dtype,
     ranks int32 [S] and scales f32 [S], allocated once, at fixed addresses.  `bounds`: the P + 1 column bounds of the P
-    projections fused into the linear.  `host_ranks` / `host_scales` mirror the device arrays for the host loop of long
-    prefills."""
+    projections fused into the linear."""
 
     def __init__(self, K: int, bounds, S: int, max_rank: int, dtype, device):
         self.K, self.N, self.P, self.S, self.max_rank, self.dtype = K, bounds[-1], len(bounds) - 1, S, max_rank, dtype
@@ -944,8 +947,6 @@ class LoraImages:
         self.B = torch.zeros((S, max_rank // 16, self.N, 16), dtype=dtype, device=device)
         self.ranks = torch.zeros(S, dtype=torch.int32, device=device)
         self.scales = torch.zeros(S, dtype=torch.float32, device=device)
-        self.host_ranks, self.host_scales = [0] * S, [0.0] * S
-        self.host_present = [(False,) * self.P for _ in range(S)]  # which of the P projections a slot's adapter targets
         self.a_stride = self.A.stride(0) * self.A.element_size()
         self.b_stride = self.B.stride(0) * self.B.element_size()
 
@@ -980,8 +981,6 @@ class LoraImages:
             self.B[s, :b.shape[0]].copy_(b)
         self.ranks[s:s + 1].copy_(torch.tensor([rank], dtype=torch.int32))
         self.scales[s:s + 1].copy_(torch.tensor([scale if rank else 0.0], dtype=torch.float32))
-        self.host_ranks[s], self.host_scales[s] = rank, float(scale) if rank else 0.0
-        self.host_present[s] = tuple(a is not None for a in As)
 
 
 class LoraGroup:
@@ -1021,6 +1020,38 @@ def lora_expand(v: torch.Tensor, w: LoraImages, g: LoraGroup, y: torch.Tensor) -
     _check(load_library().tgis_lora_expand(_ptr(v), _ptr(w.B), w.b_stride, _ptr(w.ranks), _ptr(w.scales), _ptr(g.offsets),
                                            _ptr(g.rows), w._bounds_c, _ptr(y), y.stride(0), g.T, w.N, w.P, w.S, w.max_rank,
                                            dtype_code(w.dtype), _stream()), "tgis_lora_expand")
+    return y
+
+
+class LoraTiles:
+    """The tile table of a prefill of T rows on the device (tgis_hip.h): int32 [n, 4] = (row0, nrows, slot, 0), built on the
+    host by utils.lora.lora_tile_table."""
+
+    def __init__(self, table, T: int, device):
+        self.n, self.T = int(table.shape[0]), int(T)
+        self.table = torch.from_numpy(table).to(device, non_blocking=True) if self.n else None
+
+
+def lora_shrink_tiles(x: torch.Tensor, w: LoraImages, tiles: LoraTiles, v=None) -> torch.Tensor:
+    """v fp32 [T, P, max_rank]: A_s[p] x[t] for the rows of the tiles, up to each slot's rank rounded up to 16."""
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == w.dtype and x.shape == (tiles.T, w.K)
+    if v is None:
+        v = torch.empty((tiles.T, w.P, w.max_rank), dtype=torch.float32, device=x.device)
+    assert v.dtype == torch.float32 and v.is_contiguous() and v.shape == (tiles.T, w.P, w.max_rank)
+    _check(load_library().tgis_lora_shrink_tiles(_ptr(x), x.stride(0), _ptr(w.A), w.a_stride, _ptr(w.ranks), _ptr(tiles.table),
+                                                 tiles.n, _ptr(v), tiles.T, w.K, w.P, w.S, w.max_rank, dtype_code(w.dtype),
+                                                 _stream()), "tgis_lora_shrink_tiles")
+    return v
+
+
+def lora_expand_tiles(v: torch.Tensor, w: LoraImages, tiles: LoraTiles, y: torch.Tensor) -> torch.Tensor:
+    """y[t] += scale_s B_s v[t] in place for the rows of the tiles (one rounding to the model dtype); other rows untouched."""
+    assert y.dim() == 2 and y.stride(1) == 1 and y.dtype == w.dtype and y.shape == (tiles.T, w.N)
+    assert v.dtype == torch.float32 and v.is_contiguous() and v.shape == (tiles.T, w.P, w.max_rank)
+    _check(load_library().tgis_lora_expand_tiles(_ptr(v), _ptr(w.B), w.b_stride, _ptr(w.ranks), _ptr(w.scales),
+                                                 _ptr(tiles.table), tiles.n, w._bounds_c, _ptr(y), y.stride(0), tiles.T, w.N,
+                                                 w.P, w.S, w.max_rank, dtype_code(w.dtype), _stream()),
+           "tgis_lora_expand_tiles")
     return y
 
 

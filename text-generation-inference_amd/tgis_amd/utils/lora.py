@@ -1,7 +1,8 @@
 """Per-request LoRA adapters on the Llama flash path, the host side: the options, reading and checking a peft
 adapter directory, the slot table (adapter id -> device slot, least recently used replacement, a pin count per slot for live
 requests) and the wrapper that adds an adapter's delta behind whatever `Linear` it is given.  The kernels are tgis_lora_group
-/ tgis_lora_shrink / tgis_lora_expand (csrc/lora.hip).  Everything up to `LoraLinear` needs no GPU.
+/ tgis_lora_shrink / tgis_lora_expand (csrc/lora.hip) for up to 64 rows and tgis_lora_shrink_tiles / tgis_lora_expand_tiles
+(csrc/lora_prefill.hip) for longer prefills.  Everything up to `LoraLinear` needs no GPU.
 
 A request names an adapter with its `prefix_id`: a directory under $PREFIX_STORE_PATH whose `adapter_config.json` says
 `"peft_type": "LORA"` (prompt_cache.py).  Tensors are peft's:
@@ -255,15 +256,39 @@ def release_slots(table: Optional[LoraSlots], slots: Optional[List[int]]) -> Non
 
 
 # ---- the forward ----------------------------------------------------------------------------------------------------------
+LORA_TILE_ROWS = 64
+
+
+def lora_tile_table(lora_slots, rows_per_request):
+    """The tile table of a prefill whose request i brings rows_per_request[i] contiguous rows on slot lora_slots[i]: int32
+    [n_tiles, 4] = (row0, nrows, slot, 0), every request with a slot cut into tiles of up to 64 rows, none for a request
+    at -1 or without rows."""
+    import numpy as np
+
+    slots, rows = np.asarray(lora_slots, dtype=np.int64), np.asarray(rows_per_request, dtype=np.int64)
+    starts = np.cumsum(rows) - rows
+    keep = (slots >= 0) & (rows > 0)
+    slots, rows, starts = slots[keep], rows[keep], starts[keep]
+    per = (rows + LORA_TILE_ROWS - 1) // LORA_TILE_ROWS  # tiles of each request
+    req = np.repeat(np.arange(rows.size), per)
+    first = (np.arange(req.size) - np.repeat(np.cumsum(per) - per, per)) * LORA_TILE_ROWS  # the tile's first row in its request
+    table = np.zeros((req.size, 4), dtype=np.int32)
+    table[:, 0], table[:, 1], table[:, 2] = starts[req] + first, np.minimum(LORA_TILE_ROWS, rows[req] - first), slots[req]
+    return table
+
+
 @dataclass
 class LoraArgs:
     """What a forward that carries adapter rows hands the layers: `slots` int32 [T] on the device (-1: no adapter) and
-    either `groups`, the device grouping of tgis_lora_group for every run of up to 64 rows as (row0, row1, LoraGroup) (the
-    kernel path: prefills of up to 64 rows and every decode step), or, for longer prefills, the host's `ranges` (row0,
-    row1, slot) of the requests that carry an adapter (their rows are contiguous)."""
+    either `groups`, the device grouping of tgis_lora_group for every run of up to 64 rows as (row0, row1, LoraGroup)
+    (prefills of up to 64 rows and every decode step), or, for longer prefills, `tiles`, the native.LoraTiles of the
+    requests that carry an adapter (their rows are contiguous): tgis_lora_shrink_tiles / tgis_lora_expand_tiles.  `v`: the
+    fp32 [T, P, max_rank] scratch of the tile path, one per P, shared by the linears of a forward (they run in stream
+    order)."""
     slots: torch.Tensor
     groups: Optional[List[Tuple[int, int, object]]] = None
-    ranges: Optional[List[Tuple[int, int, int]]] = None
+    tiles: Optional[object] = None
+    v: Optional[Dict[int, torch.Tensor]] = None
 
     @classmethod
     def grouped(cls, slots: torch.Tensor, S: int) -> "LoraArgs":
@@ -312,20 +337,10 @@ class LoraLinear:
             for row0, row1, g in lora.groups:
                 native.lora_expand(native.lora_shrink(x[row0:row1], w, g), w, g, y[row0:row1])
             return y
-        # long prefills: two library GEMMs per projection the adapter targets and row range, in fp32 as the kernels' contract
-        # has it (v stays fp32, base + delta is rounded to the model dtype once)
-        for row0, row1, s in lora.ranges:
-            rank = w.host_ranks[s]
-            if rank == 0:
-                continue
-            r16 = (rank + 15) // 16 * 16
-            xs = x[row0:row1].float()
-            b = w.B[s, :r16 // 16].permute(1, 0, 2).reshape(w.N, r16).float()
-            for p in range(w.P):
-                if not w.host_present[s][p]:
-                    continue  # (the adapter leaves this projection out: its A and B are zero)
-                v = torch.matmul(xs, w.A[s, p, :r16].float().t())
-                n0, n1 = w.bounds[p], w.bounds[p + 1]
-                ys = y[row0:row1, n0:n1]
-                ys.copy_(torch.addmm(ys.float(), v, b[n0:n1].t(), alpha=w.host_scales[s]))
-        return y
+        # longer prefills: the two tile launches, once per linear
+        if lora.v is None:
+            lora.v = {}
+        v = lora.v.get(w.P)
+        if v is None:
+            v = lora.v[w.P] = torch.empty((lora.tiles.T, w.P, w.max_rank), dtype=torch.float32, device=x.device)
+        return native.lora_expand_tiles(native.lora_shrink_tiles(x, w, lora.tiles, v), w, lora.tiles, y)

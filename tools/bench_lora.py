@@ -10,7 +10,13 @@ and the shrink and expand launches alone on the four projections' shapes at 32 r
 made in memory (random f16 A and B) and pinned through the model's own slot table.  One JSON line per measurement on stdout,
 all of them together in --out.
 
-    python tools/bench_lora.py [--steps 20] [--blocks 5] [--dtypes f16,int4] [--out profiles/lora_bench.json]"""
+And what an adapter costs a prefill: one 2048-token prompt on the dense f16 model with the option off, under one r 16
+all-module adapter served by the host loop of library GEMMs that the tile kernels replaced (restated here), and served by
+tgis_lora_shrink_tiles / tgis_lora_expand_tiles, alternating in one process; plus the two tile launches alone on the four
+projections' shapes at 2048 rows.  These lines go to --prefill-out, one JSON object a line.
+
+    python tools/bench_lora.py [--steps 20] [--blocks 5] [--dtypes f16,int4] [--out profiles/lora_bench.json]
+                               [--only-prefill] [--prefill-reps 3] [--prefill-out profiles/lora_prefill_bench.jsonl]"""
 import argparse
 import json
 import os
@@ -33,6 +39,7 @@ from tgis_amd.utils import lora  # noqa: E402
 from tgis_amd.utils.kv_cache import PagedKVCache  # noqa: E402
 
 SLOTS, RANK, WARM = 8, 16, 10
+PREFILL_ROWS = 2048
 # (name, K, the column bounds) of the four wrapped linears of Llama-2-7B
 SHAPES = [("qkv", 4096, (0, 4096, 8192, 12288)), ("o", 4096, (0, 4096)), ("gate_up", 4096, (0, 11008, 22016)),
           ("down", 11008, (0, 4096))]
@@ -143,6 +150,107 @@ def steps(args, dev, dtype_s, emit):
     torch.cuda.empty_cache()
 
 
+def tile_launches(args, dev, emit):
+    """tgis_lora_shrink_tiles and tgis_lora_expand_tiles alone: PREFILL_ROWS rows of one request on one r 16 slot."""
+    T = PREFILL_ROWS
+    tiles = native.LoraTiles(lora.lora_tile_table([0], [T]), T, dev)
+    for name, K, bounds in SHAPES:
+        P, N = len(bounds) - 1, bounds[-1]
+        w = native.LoraImages(K, bounds, SLOTS, 64, torch.float16, dev)
+        w.load(0, [torch.randn(RANK, K) * K ** -0.5] * P, [torch.randn(bounds[p + 1] - bounds[p], RANK) for p in range(P)], 2.0)
+        x = (torch.randn((T, K), device=dev) * 0.1).half()
+        y = torch.zeros((T, N), dtype=torch.float16, device=dev)
+        v = native.lora_shrink_tiles(x, w, tiles)
+        sh = median_us(lambda: native.lora_shrink_tiles(x, w, tiles, v), args.warm, args.reps)
+        ex = median_us(lambda: native.lora_expand_tiles(v, w, tiles, y), args.warm, args.reps)
+        emit({"tile_launch": name, "K": K, "N": N, "P": P, "rows": T, "tiles": tiles.n, "rank": RANK,
+              "shrink_us": round(sh[0], 2), "shrink_p10_p90": [round(sh[1], 2), round(sh[2], 2)],
+              "expand_us": round(ex[0], 2), "expand_p10_p90": [round(ex[1], 2), round(ex[2], 2)]})
+        del w
+        torch.cuda.empty_cache()
+
+
+def host_loop(ranges, rank, scale):
+    """LoraLinear.add_delta as it served prefills of more than 64 rows before the tile kernels, restated for the comparison
+    alone: per request and projection two library GEMMs in fp32 around casts and copies.  ranges: (row0, row1, slot)."""
+    r16 = (rank + 15) // 16 * 16
+
+    def add_delta(self, x, y, _lora):
+        w = self.images
+        for row0, row1, s in ranges:
+            xs = x[row0:row1].float()
+            b = w.B[s, :r16 // 16].permute(1, 0, 2).reshape(w.N, r16).float()
+            for p in range(w.P):
+                v = torch.matmul(xs, w.A[s, p, :r16].float().t())
+                n0, n1 = w.bounds[p], w.bounds[p + 1]
+                ys = y[row0:row1, n0:n1]
+                ys.copy_(torch.addmm(ys.float(), v, b[n0:n1].t(), alpha=scale))
+        return y
+
+    return add_delta
+
+
+def prefill(args, dev, emit):
+    """One PREFILL_ROWS-token prompt on dense f16 Llama-2-7B: option off, under one r 16 all-module adapter with the host loop
+    of library GEMMs, and with the tile kernels; the three alternate block by block in one process."""
+    kw = bench.CONFIGS["llama2-7b-gptq"][0]
+    cfg = LlamaConfig(**kw)
+    tok = SyntheticTokenizer(cfg.vocab_size)
+    L, new = PREFILL_ROWS, 4
+    pages = PagedKVCache.pages_for(L + new) + 8
+
+    def model(slots):
+        tensors = llama_tensors(cfg, None, seed=1234, device=dev, dtype=torch.float16)
+        eng = InferenceEngine(tensors, cfg, torch.float16, None, tokenizer=tok)
+        del tensors
+        return FlashCausalLM("synthetic", None, "synthetic", torch.float16, None, engine=eng, kv_cache_pages=pages,
+                             lora_slots=slots)
+
+    off, on = model(0), model(SLOTS)
+    torch.cuda.empty_cache()
+    table = on.lora_table
+    table.release(table.acquire(adapter(cfg, "a0")))
+    tiles_delta = lora.LoraLinear.add_delta
+    loop_delta = host_loop([(0, L, table.slot_of("a0"))], RANK, 2.0)
+    bid = [0]
+
+    def once(lm, adapted, delta):
+        bid[0] += 1
+        b, errs = lm.batch_type.from_pb(make_batch_pb([L], max_new=new, batch_id=bid[0]), tok, lm.dtype, lm.device,
+                                        lm.word_embeddings, None, True)
+        assert not errs
+        if adapted:
+            b.lora_slots, b.lora_table = [table.acquire(table.resident("a0"))], table
+        lora.LoraLinear.add_delta = delta
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lm.generate_token(b, first=True)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+        finally:
+            lora.LoraLinear.add_delta = tiles_delta
+            b.release()
+
+    variants = [("off", off, False, tiles_delta), ("host_loop", on, True, loop_delta), ("tiles", on, True, tiles_delta)]
+    times = {name: [] for name, *_ in variants}
+    with off.context_manager():
+        for name, lm, adapted, delta in variants:
+            for _ in range(2):
+                once(lm, adapted, delta)
+        for _ in range(args.blocks):
+            for name, lm, adapted, delta in variants:
+                times[name] += [once(lm, adapted, delta) for _ in range(args.prefill_reps)]
+    base = statistics.median(times["off"])
+    for name, *_ in variants:
+        med = statistics.median(times[name])
+        emit({"prefill": "llama2-7b f16", "config": name, "prompt_tokens": L, "rank": RANK, "blocks": args.blocks,
+              "reps_per_block": args.prefill_reps, "ms": round(med, 3),
+              "ms_min_max": [round(min(times[name]), 3), round(max(times[name]), 3)], "over_off_ms": round(med - base, 3)})
+    del off, on, variants
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
@@ -152,6 +260,9 @@ def main():
     ap.add_argument("--dtypes", default="f16,int4")
     ap.add_argument("--skip-launches", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lora_bench.json"))
+    ap.add_argument("--only-prefill", action="store_true", help="the prefill comparison and the tile launches alone")
+    ap.add_argument("--prefill-reps", type=int, default=3)
+    ap.add_argument("--prefill-out", default=os.path.join(ROOT, "profiles", "lora_prefill_bench.jsonl"))
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
@@ -162,13 +273,21 @@ def main():
         rows.append(row)
         print(json.dumps(row), flush=True)
 
+    if not args.only_prefill:
+        if not args.skip_launches:
+            launches(args, dev, emit)
+        for dtype_s in [d for d in args.dtypes.split(",") if d]:
+            steps(args, dev, dtype_s, emit)
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(rows, fh, indent=1)
+    del rows[:]
     if not args.skip_launches:
-        launches(args, dev, emit)
-    for dtype_s in [d for d in args.dtypes.split(",") if d]:
-        steps(args, dev, dtype_s, emit)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as fh:
-        json.dump(rows, fh, indent=1)
+        tile_launches(args, dev, emit)
+    prefill(args, dev, emit)
+    os.makedirs(os.path.dirname(args.prefill_out), exist_ok=True)
+    with open(args.prefill_out, "w") as fh:
+        fh.writelines(json.dumps(row) + "\n" for row in rows)
 
 
 if __name__ == "__main__":
