@@ -740,6 +740,23 @@ int64_t tgis_argmax_scratch_bytes(int64_t B);
 int tgis_argmax_logprob(const void* logits, int64_t ld, int64_t B, int64_t V, int logits_f32, int dtype,
                         int64_t* ids_out, float* logprob_out, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ---- prompt-token scores from the head (details.input_toks: log_softmax + gather + rank compare over all prompt rows,
+ * utils/tokens.py:394-412) without the [T, V] logits -----------------------------------------------------------------
+ * z[t, v] = sum_k x[t, k] weight[v, k] in fp32, never stored.  x [T, K] model dtype, row stride ldx (the final-normed hidden
+ * rows); weight [V, K] row-major, the same dtype: the head's checkpoint tensor, not a prepared image; targets int64 [T], a
+ * value outside [0, V) (-1 by convention) = the row is not wanted.  Per row t, with g = targets[t]:
+ *   lse[t] = logsumexp_v z[t, v];  logprob[t] = z[t, g] - lse[t];  rank[t] = 1 + #{v != g : z[t, v] > z[t, g]} (int32);
+ *   an unwanted row gets logprob NaN and rank 0, its lse is computed all the same.
+ * z[t, g] is one fp32 dot product, used for logprob and for every comparison.  Three launches (target logits; the sweep over
+ * ceil(T / 128) row tiles x num_splits vocabulary ranges; a merge in fixed order), no atomics: same input, same bytes.
+ * workspace: tgis_head_logprobs_bytes(T, V, NULL) bytes, 16-byte aligned, no initialisation needed; *num_splits (may be
+ * NULL) receives the vocabulary splits the host rule picks for (T, V).  K % 16 == 0, V >= 1, T >= 0 (T = 0 returns
+ * TGIS_OK); x, weight and ldx * 2 bytes 16-byte aligned.  No allocation, no sync. */
+int64_t tgis_head_logprobs_bytes(int64_t T, int64_t V, int* num_splits);
+int tgis_head_logprobs(const void* x, int64_t ldx, const void* weight, const int64_t* targets, int64_t T, int64_t V, int64_t K,
+                       int dtype, float* logprob, int32_t* rank, float* lse, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
 /* ---- next-token chooser for a heterogeneous batch -------------------------------------------------
  * One launch for what HeterogeneousNextTokenChooser.__call__ (utils/tokens.py:242-270) does with the
  * Heterogeneous* processors (utils/logits_process.py:93-402) and Sampling / HeterogeneousSampling

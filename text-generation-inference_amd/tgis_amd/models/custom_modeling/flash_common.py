@@ -126,19 +126,24 @@ class FlashForCausalLM:
         return len(self.model.layers)
 
     def forward(self, input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds=None, kv: KVArgs = None,
-                lm_head_indices: Optional[torch.Tensor] = None, return_embeds: bool = False, lora=None):
+                lm_head_indices: Optional[torch.Tensor] = None, return_embeds: bool = False, lora=None,
+                return_all_hidden: bool = False):
         """position_ids int32 [T]; returns fp32 logits [T or len(lm_head_indices), vocab]; with `return_embeds` (the
         reference's paged_llama_modeling.py:443-462) the pair (logits, hidden_states), the rows that went into lm_head.
-        lora: a utils.lora.LoraArgs when rows of this forward carry adapters (the Llama class alone takes one)."""
+        lora: a utils.lora.LoraArgs when rows of this forward carry adapters (the Llama class alone takes one).
+        return_all_hidden: the result becomes (what it would have been, the final-normed hidden rows of all T positions);
+        lm_head still runs on the rows of `lm_head_indices` alone (utils/input_logprobs.py)."""
         if input_ids is not None and inputs_embeds is not None:
             raise ValueError("You cannot specify both input_ids and inputs_embeds at the same time")
         if lora is not None:
             hidden_states = self.model(input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds, kv, lora)
         else:
             hidden_states = self.model(input_ids, position_ids, cu_seqlens_q, max_s, inputs_embeds, kv)
+        all_hidden = hidden_states
         if lm_head_indices is not None:
             hidden_states = hidden_states.index_select(0, lm_head_indices)
         logits = self.lm_head(hidden_states)
-        return (logits, hidden_states) if return_embeds else logits
+        out = (logits, hidden_states) if return_embeds else logits
+        return (out, all_hidden) if return_all_hidden else out
 
     __call__ = forward

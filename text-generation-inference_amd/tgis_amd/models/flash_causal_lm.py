@@ -34,6 +34,8 @@ from tgis_amd.models.speculation import LookupDrafter, MLPDrafter, spec_step
 from tgis_amd.models.types import Batch, GenerateError
 from tgis_amd.pb import generate_pb2
 from tgis_amd.utils import mlp_speculator
+from tgis_amd.utils.input_logprobs import (batch_takes_fused, check_fused_input_world, fused_input_tokens, head_weight,
+                                           parse_fused_input_logprobs)
 from tgis_amd.utils.kv_cache import (KV_SCALES_HEADROOM, PAGE, OutOfPages, PagedKVCache, agree_kv_cache_dtype,
                                      agree_kv_prefix_reuse, agree_kv_scales, kv_pool_dtype, kv_scales_stats,
                                      pages_for_budget, parse_kv_cache_dtype, parse_kv_prefix_reuse)
@@ -503,6 +505,11 @@ class FlashCausalLM(Model):
     lora_slots = 0
     lora_max_rank = 64
     lora_table = None
+    # prompt-token details from the fused head kernel (utils/input_logprobs.py; set by the constructor)
+    fused_input_logprobs = False
+    # per prefill (`_prefill`): whether its prompt tokens take that path, and the hidden rows of all positions for it
+    _fused_input = False
+    _input_hidden = None
 
     def __init__(self, model_name: str, revision: Optional[str], deployment_framework: str, dtype: torch.dtype,
                  quantize: Optional[str], model_config: Union[Any] = None, auto_model_class=None,
@@ -511,7 +518,8 @@ class FlashCausalLM(Model):
                  kv_prefix_reuse: Optional[bool] = None, spec_tokens: Optional[int] = None,
                  spec_ngram: Optional[int] = None, speculator: Union[None, str, Any] = None,
                  spec_sampling: Optional[bool] = None, spec_candidates: Optional[int] = None,
-                 lora_slots: Optional[int] = None, lora_max_rank: Optional[int] = None):
+                 lora_slots: Optional[int] = None, lora_max_rank: Optional[int] = None,
+                 fused_input_logprobs: Optional[bool] = None):
         # KV cache element: "auto" (the model dtype) or "fp8_e4m3" (one byte, utils/kv_cache.py); None reads
         # TGIS_KV_CACHE_DTYPE.  Checked before anything is loaded — except on a rank of a tensor-parallel group, which loads
         # its shard and then tells its peers (agree_kv_cache_dtype below): they sit in a collective only it can release.
@@ -549,6 +557,11 @@ class FlashCausalLM(Model):
         self.lora_slots = parse_lora_slots(lora_slots)
         self.lora_max_rank = parse_lora_max_rank(lora_max_rank)
         check_lora_world(self.lora_slots, getattr(engine, "world_size", 1) or 1, self.spec_tokens)
+        # fused_input_logprobs: the prompt tokens of input_toks requests are scored by one tgis_head_logprobs call per prefill,
+        # from the hidden rows, in place of lm_head over all rows and three torch passes over [T, V] (utils/input_logprobs.py);
+        # None reads TGIS_FUSED_INPUT_LOGPROBS (true / false, default false).  Not under tensor parallelism.
+        self.fused_input_logprobs = parse_fused_input_logprobs(fused_input_logprobs)
+        check_fused_input_world(self.fused_input_logprobs, getattr(engine, "world_size", 1) or 1)
         # kv_scales: the calibrated per-layer scales of a one-byte cache, the contents of a kv_cache_scales.json or its path
         # (utils/kv_cache.py, resolve_kv_scales); None looks at TGIS_KV_SCALES, then next to the weights, else they stay 1.0
         if not torch.cuda.is_available():
@@ -595,6 +608,7 @@ class FlashCausalLM(Model):
         self.ranks = RankGroup(engine, self.device)
         check_spec_world(self.spec_tokens, self.ranks.world)
         check_lora_world(self.lora_slots, self.ranks.world, self.spec_tokens)
+        check_fused_input_world(self.fused_input_logprobs, self.ranks.world)
         check_tree_rows(self.spec_candidates, self.spec_tokens, self.num_heads, self.num_kv_heads)
         self._spec_stats = new_stats()
         if spec_ckpt is not None:
@@ -748,6 +762,11 @@ class FlashCausalLM(Model):
         before = self.kv_cache.reuse_stats() if self.kv_prefix_reuse else None
         batch.allocate_pages(self.kv_cache)
         self._need_all_logits = any(r.details.input_toks for r in batch.requests)
+        # with the option on, the prompt tokens are scored from the hidden rows and lm_head keeps to the last rows
+        self._fused_input = self.fused_input_logprobs and batch_takes_fused(batch.requests)
+        self._input_hidden = None
+        if self._fused_input:
+            self._need_all_logits = False
         if any(batch.reused_lengths):
             out = self._prefill_suffix_forward(batch)
         else:
@@ -787,12 +806,20 @@ class FlashCausalLM(Model):
 
     def _forward_prefill(self, *args, lora=None):
         """(logits, hidden rows or None): the model's forward; a drafter that needs them also gets the rows that went into
-        lm_head (`return_embeds`).  lora: the LoraArgs of a prefill that carries adapter rows."""
+        lm_head (`return_embeds`).  lora: the LoraArgs of a prefill that carries adapter rows.  A prefill whose prompt tokens
+        the fused head kernel scores leaves the hidden rows of all positions in `_input_hidden` for `_process_new_tokens`."""
+        kw = {"return_all_hidden": True} if self._fused_input else {}
         if lora is not None:
-            return self.model.forward(*args, lora=lora), None
-        if self.drafter is not None and self.drafter.needs_hidden:
-            return self.model.forward(*args, return_embeds=True)
-        return self.model.forward(*args), None
+            out = self.model.forward(*args, lora=lora, **kw)
+        elif self.drafter is not None and self.drafter.needs_hidden:
+            out = self.model.forward(*args, return_embeds=True, **kw)
+        else:
+            out = self.model.forward(*args, **kw)
+        if self._fused_input:
+            out, self._input_hidden = out
+        if lora is None and self.drafter is not None and self.drafter.needs_hidden:
+            return out
+        return out, None
 
     def _load_adapter(self, slot: int, adapter: LoraAdapter):
         """The slot table's upload: the adapter's tensors into `slot` of every wrapped linear, as copies on the current
@@ -955,6 +982,12 @@ class FlashCausalLM(Model):
         else:
             ids_host = next_token_ids.tolist()
             lps_host = next_logprobs.tolist() if any(ntc.return_logprobs) else None
+        fused_inputs = None
+        if prefill and self._fused_input:
+            # one tgis_head_logprobs call and one copy for the prompt tokens of the whole batch (before the lengths move)
+            hidden, self._input_hidden = self._input_hidden, None
+            fused_inputs = iter(fused_input_tokens(batch.requests, batch.input_lengths, batch.all_input_ids_tensor, hidden,
+                                                   head_weight(self.model)))
         for i, request in enumerate(batch.requests):
             try:
                 if not simple and (request.details.top_n_toks or request.details.ranks):
@@ -967,7 +1000,9 @@ class FlashCausalLM(Model):
                     if lps_host is not None and request.details.logprobs:
                         info.logprob = lps_host[i]
                 generated_tokens.append(info)
-                if prefill and request.details.input_toks:
+                if fused_inputs is not None and request.details.input_toks:
+                    input_token_infos.append(next(fused_inputs))
+                elif prefill and request.details.input_toks:
                     self._append_input_tokens(batch, out, i, request, input_token_infos)
             except Exception as e:
                 logging.exception(f"token decoding error for request #{request.id}")

@@ -171,6 +171,8 @@ SIGNATURES = {
     "tgis_spec_mlp_drafts": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp]),
     "tgis_argmax_logprob": (_c_int, [_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _c_i64, _vp]),
     "tgis_argmax_scratch_bytes": (_c_i64, [_c_i64]),
+    "tgis_head_logprobs_bytes": (_c_i64, [_c_i64, _c_i64, ctypes.POINTER(_c_int)]),
+    "tgis_head_logprobs": (_c_int, [_vp, _c_i64, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _vp, _c_i64, _vp]),
     "tgis_warp_sample": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64,
                                   _c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tgis_warp_sample_verify": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -1594,6 +1596,27 @@ def argmax_logprob(logits, ids_out=None, logprob_out=None, scratch=None):
                                            _ptr(logprob_out), _ptr(scratch), scratch.numel() if scratch is not None else 0,
                                            _stream()), "tgis_argmax_logprob")
     return ids_out, logprob_out
+
+
+def head_logprobs(x, weight, targets):
+    """Prompt-token scores straight from the head (tgis_head_logprobs): x [T, K] the final-normed hidden rows, weight [V, K]
+    the head's checkpoint tensor, targets int64 [T] (-1: row not wanted).  Returns (logprob f32 [T], rank int32 [T], lse f32
+    [T]) of z = x weight^T, which is never stored: the scratch is T (4 + 16 splits) bytes."""
+    assert x.dim() == 2 and x.stride(1) == 1 and weight.dim() == 2 and weight.is_contiguous()
+    assert weight.dtype == x.dtype and weight.shape[1] == x.shape[1] and weight.device == x.device
+    T, K = x.shape
+    V = weight.shape[0]
+    assert _is(targets, torch.int64, T) and targets.device == x.device
+    dev = x.device
+    logprob = torch.empty(T, dtype=torch.float32, device=dev)
+    rank = torch.empty(T, dtype=torch.int32, device=dev)
+    lse = torch.empty(T, dtype=torch.float32, device=dev)
+    lib = load_library()
+    scratch = torch.empty(max(16, lib.tgis_head_logprobs_bytes(T, V, None)), dtype=torch.uint8, device=dev)
+    _check(lib.tgis_head_logprobs(_ptr(x), x.stride(0), _ptr(weight), _ptr(targets), T, V, K, dtype_code(x.dtype),
+                                  _ptr(logprob), _ptr(rank), _ptr(lse), _ptr(scratch), scratch.numel(), _stream()),
+           "tgis_head_logprobs")
+    return logprob, rank, lse
 
 
 def warp_sample(logits, temperature=None, top_k=None, top_p_cut=None, typical_p=None, rep_penalty=None,
