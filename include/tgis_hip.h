@@ -315,6 +315,20 @@ int tgis_moe_tile_gemm_down(const void* h, int64_t ldh, const void* images, int6
                             const int32_t* slot_rows, const int32_t* tiles, int64_t tile_bound, const float* expert_w,
                             int64_t T, int64_t K, int64_t N, int E, int top_k, int dtype, int form, float* scratch,
                             int64_t scratch_bytes, void* out, int64_t ldo, void* stream);
+/* The contracts of tgis_moe_gptq_gemm_up / tgis_moe_gptq_gemm_down (the same int4 images of tgis_gptq_prepare, the same
+ * served shapes and refusals, the same epilogues, slabs with ld = N and run-to-run bytes; E <= 128) over a routing of
+ * tgis_moe_route_tiles, for prefills: `groups` sits where those entry points put it, the tile arguments where
+ * tgis_moe_tile_gemm_* put them, and scratch is tgis_moe_tile_gemm_down_bytes.  Grid (ceil(N / 128), tile_bound): a block
+ * owns one tile (up to 64 rows of one expert) x 128 image columns, gathers the rows once per k64-step into LDS and
+ * dequantises each wave's nibbles once for all of them: an expert's image is read once per 64 of its rows, where
+ * tgis_moe_gptq_gemm_* read it once per 32. */
+int tgis_moe_gptq_tile_gemm_up(const void* x, int64_t ldx, const void* images, int64_t expert_stride, const int32_t* offsets,
+                               const int32_t* slot_rows, const int32_t* tiles, int64_t tile_bound, void* h, int64_t ldh,
+                               int64_t T, int64_t K, int64_t N, int64_t groups, int E, int top_k, int dtype, void* stream);
+int tgis_moe_gptq_tile_gemm_down(const void* h, int64_t ldh, const void* images, int64_t expert_stride, const int32_t* offsets,
+                                 const int32_t* slot_rows, const int32_t* tiles, int64_t tile_bound, const float* expert_w,
+                                 int64_t T, int64_t K, int64_t N, int64_t groups, int E, int top_k, int dtype, int form,
+                                 float* scratch, int64_t scratch_bytes, void* out, int64_t ldo, void* stream);
 
 /* ---- per-request LoRA adapters (csrc/lora.hip) ----
  * A wrapped linear computes y[t] = W x[t] + scale_s B_s (A_s x[t]) with s = slot[t]; a row with slot[t] = -1 keeps W x[t].

@@ -573,3 +573,5 @@ extern "C" int tgis_debug_moe_gptq_plan(int which, int64_t T, int64_t K, int64_t
 
 // tgis_moe_route_tiles, tgis_moe_tile_gemm_up / _down: routing and grouped expert GEMMs for up to 128 experts
 #include "moe_tiles.h"
+// tgis_moe_gptq_tile_gemm_up / _down: the int4 images under the tile list (GPTQ Mixtral prefills)
+#include "moe_gptq_tiles.h"

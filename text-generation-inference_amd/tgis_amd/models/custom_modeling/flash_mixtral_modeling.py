@@ -15,6 +15,9 @@ forces either on eager forwards).
 GPTQ checkpoints (4 bits, one group or groups of 64 * 2^n rows, no act-order; q/k/v/o as Llama's): every expert's w1 | w3 and
 w2 are int4 images (native.MoeGptqWeights) and the block takes native.moe_gptq_gemm_up / _down, the same kernel over another
 weight source; its loop path runs gptq_gemm(act=2) and gptq_gemm on views of the same images.  The router stays 16-bit.
+An eager GPTQ forward above MOE_GPTQ_FUSED_MAX_TOKENS tokens takes neither: native.moe_route_tiles and the int4 tile GEMMs
+native.moe_gptq_tile_gemm_up / _down (csrc/moe_gptq_tiles.h) run the whole prefill block without a host read of the routing
+(TGIS_MOE_PATH=tiles forces them at any T; the loop stays as the A/B partner).
 
 Tensor parallelism: every expert's intermediate size is split across ranks (w1 and w3 by rows, w2 by columns, as Llama's
 MLP), the router is replicated, and the block's output is all-reduced once."""
@@ -38,13 +41,20 @@ MOE_FUSED_MAX_TOKENS = int(os.getenv("TGIS_MOE_FUSED_MAX_TOKENS", "64"))
 # per-expert gptq_gemm launches and host read cost what they cost at f16 while the kernels read a quarter of the bytes) and
 # lose at 256 (0.93 against 0.76 ms).
 MOE_GPTQ_FUSED_MAX_TOKENS = int(os.getenv("TGIS_MOE_GPTQ_FUSED_MAX_TOKENS", "128"))
+# what an eager forward above its threshold takes, by "the experts are GPTQ": dense experts the loop, GPTQ experts the int4
+# tile GEMMs (csrc/moe_gptq_tiles.h), which never read the routing on the host.  On 8x7B layer shapes
+# (profiles/mixtral_gptq_tiles_bench.jsonl) tiles / loop / slab kernels take 0.62 / 0.73 / 0.90 ms at 256
+# tokens, 0.80 / 1.05 / 1.70 at 512, 1.36 / 1.70 / 3.34 at 1024 and 2.42 / 2.43 / 6.50 at 2048.  At 128 the tiles (0.472) and the
+# slab kernels (0.481) are about the run's spread apart and at 64 the slab kernels win (0.27 against 0.44): the threshold stays.
+MOE_PATH_ABOVE = {False: "loop", True: "tiles"}
 
 
 def moe_path_override():
-    """TGIS_MOE_PATH = fused | loop forces one implementation on eager forwards (tests, A/B runs); unset / auto: the rule."""
+    """TGIS_MOE_PATH = fused | loop | tiles forces one implementation on eager forwards (tests, A/B runs); unset / auto: the
+    rule.  tiles is the int4 tile path: GPTQ experts only."""
     v = os.getenv("TGIS_MOE_PATH", "auto").lower()
-    if v not in ("auto", "fused", "loop"):
-        raise ValueError(f"TGIS_MOE_PATH must be auto, fused or loop, got {v!r}")
+    if v not in ("auto", "fused", "loop", "tiles"):
+        raise ValueError(f"TGIS_MOE_PATH must be auto, fused, loop or tiles, got {v!r}")
     return None if v == "auto" else v
 
 
@@ -208,6 +218,14 @@ class MixtralSparseMoe:
         h = native.moe_gemm_up(x, self.experts.gate_up, r)
         return native.moe_gemm_down(h, self.experts.down, r, partial=partial)
 
+    def tiles(self, x: torch.Tensor, partial: bool):
+        """GPTQ experts past MOE_GPTQ_FUSED_MAX_TOKENS tokens: router GEMM, the three route launches that also cut the tile
+        list, and the two int4 tile GEMMs.  Nothing of the routing is read on the host."""
+        logits = native.dense_gemm(x, self.router, workspace(x.device), out_f32=True)
+        r = native.moe_route_tiles(logits, self.top_k, renorm=True)
+        h = native.moe_gptq_tile_gemm_up(x, self.experts.gate_up, r)
+        return native.moe_gptq_tile_gemm_down(h, self.experts.down, r, partial=partial)
+
     def loop(self, x: torch.Tensor, r: native.Routing) -> torch.Tensor:
         E, k = self.E, self.top_k
         lists = r.lists.tolist()  # the one host read: counts and offsets
@@ -234,18 +252,23 @@ class MixtralSparseMoe:
         next add + RMSNorm finishes."""
         T = x.shape[0]
         tp = self.process_group.size()
-        use_fused = T <= (MOE_GPTQ_FUSED_MAX_TOKENS if self.quantize == "gptq" else MOE_FUSED_MAX_TOKENS)
+        gptq = self.quantize == "gptq"
+        path = "fused" if T <= (MOE_GPTQ_FUSED_MAX_TOKENS if gptq else MOE_FUSED_MAX_TOKENS) else MOE_PATH_ABOVE[gptq]
         if torch.cuda.is_current_stream_capturing():
-            use_fused = True  # a captured step cannot read the routing
+            path = "fused"  # a captured step keeps the slab kernels and tgis_moe_route
         else:
             forced = moe_path_override()
-            if forced is not None:
-                use_fused = forced == "fused"
-        r = self.route(x)
-        if not use_fused:
-            out = self.loop(x, r)
+            if forced == "tiles" and not gptq:
+                raise ValueError("TGIS_MOE_PATH=tiles: the tile path is the int4 tile GEMMs and this model's experts are "
+                                 "16-bit (dense prefills keep the loop path)")
+            path = forced or path
+        partial = tp == 1 and DEFER_REDUCE and T <= native.PARTIAL_MAX_M
+        if path == "tiles":
+            out = self.tiles(x, partial)
+        elif path == "loop":
+            out = self.loop(x, self.route(x))
         else:
-            out = self.fused(x, r, partial=tp == 1 and DEFER_REDUCE and T <= native.PARTIAL_MAX_M)
+            out = self.fused(x, self.route(x), partial=partial)
         if tp > 1:
             pg = self.process_group
             collective(lambda t=out: torch.distributed.all_reduce(t, group=pg))

@@ -91,6 +91,10 @@ SIGNATURES = {
     "tgis_moe_tile_gemm_down_bytes": (_c_i64, [_c_i64, _c_i64, _c_int, _c_int]),
     "tgis_moe_tile_gemm_down": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _c_int,
                                          _c_int, _c_int, _c_int, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "tgis_moe_gptq_tile_gemm_up": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _c_i64,
+                                            _c_i64, _c_int, _c_int, _c_int, _vp]),
+    "tgis_moe_gptq_tile_gemm_down": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64,
+                                              _c_i64, _c_int, _c_int, _c_int, _c_int, _vp, _c_i64, _vp, _c_i64, _vp]),
     "tgis_lora_a_bytes": (_c_i64, [_c_i64, _c_int, _c_int]),
     "tgis_lora_b_bytes": (_c_i64, [_c_i64, _c_int]),
     "tgis_lora_group": (_c_int, [_vp, _c_i64, _c_int, _vp, _vp, _vp, _vp]),
@@ -927,6 +931,40 @@ def moe_gptq_gemm_down(h: torch.Tensor, w: MoeGptqWeights, r: Routing, partial: 
     _check(lib.tgis_moe_gptq_gemm_down(_ptr(h), h.stride(0), _ptr(w.image), w.stride, _ptr(r.offsets), _ptr(r.slot_rows),
                                        _ptr(r.expert_w), r.T, w.K, w.N, w.groups, w.E, r.top_k, dtype_code(h.dtype), form,
                                        _ptr(scratch), nbytes, _ptr(out), w.N, _stream()), "tgis_moe_gptq_gemm_down")
+    if not partial:
+        return out
+    return Partial(scratch, r.top_k, w.N, r.T, w.N, None)
+
+
+# ---- int4 expert images under the tile list (GPTQ Mixtral prefills; csrc/moe_gptq_tiles.h) --------------------------
+def moe_gptq_tile_gemm_up(x: torch.Tensor, w: MoeGptqWeights, r: Routing, out=None) -> torch.Tensor:
+    """moe_gptq_gemm_up over a routing of moe_route_tiles: h [T top_k, I] in f16, an expert's nibbles read once per tile."""
+    assert x.dim() == 2 and x.stride(1) == 1 and x.shape == (r.T, w.K) and w.flags & 1 and w.E == r.E
+    assert r.tiles is not None, "the tile GEMMs need a routing of moe_route_tiles"
+    if out is None:
+        out = torch.empty((r.T * r.top_k, w.N // 2), dtype=x.dtype, device=x.device)
+    _check(load_library().tgis_moe_gptq_tile_gemm_up(_ptr(x), x.stride(0), _ptr(w.image), w.stride, _ptr(r.offsets),
+                                                     _ptr(r.slot_rows), _ptr(r.tiles), r.tile_bound, _ptr(out), out.stride(0),
+                                                     r.T, w.K, w.N, w.groups, w.E, r.top_k, dtype_code(x.dtype), _stream()),
+           "tgis_moe_gptq_tile_gemm_up")
+    return out
+
+
+def moe_gptq_tile_gemm_down(h: torch.Tensor, w: MoeGptqWeights, r: Routing, partial: bool = False):
+    """moe_gptq_gemm_down over a routing of moe_route_tiles: a Partial with S = top_k (partial, T <= PARTIAL_MAX_M) or the
+    finished f16 [T, hidden] tensor."""
+    assert h.dim() == 2 and h.stride(1) == 1 and h.shape == (r.T * r.top_k, w.K)
+    assert not (w.flags & 1) and w.E == r.E and r.tiles is not None
+    lib = load_library()
+    form = 0 if partial else 1
+    assert not partial or r.T <= PARTIAL_MAX_M
+    nbytes = lib.tgis_moe_tile_gemm_down_bytes(r.T, w.N, r.top_k, form)
+    scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=h.device)
+    out = None if partial else torch.empty((r.T, w.N), dtype=h.dtype, device=h.device)
+    _check(lib.tgis_moe_gptq_tile_gemm_down(_ptr(h), h.stride(0), _ptr(w.image), w.stride, _ptr(r.offsets), _ptr(r.slot_rows),
+                                            _ptr(r.tiles), r.tile_bound, _ptr(r.expert_w), r.T, w.K, w.N, w.groups, w.E,
+                                            r.top_k, dtype_code(h.dtype), form, _ptr(scratch), nbytes, _ptr(out), w.N,
+                                            _stream()), "tgis_moe_gptq_tile_gemm_down")
     if not partial:
         return out
     return Partial(scratch, r.top_k, w.N, r.T, w.N, None)

@@ -18,7 +18,9 @@ Both sides of every comparison run in this one process on one device, after a wa
 quantised, router and head dense) AND, first, for the f16 model it is compared with, in the same run; every line carries
 "quantize".  The roofline counts the bytes the int4 kernels read: half a byte per weight plus 4 bytes per (group, column).
 Keep the lines in profiles/mixtral_gptq_bench.jsonl.  --moe-tokens 64,128,256 replaces the row counts of the "moe" lines (the
-crossover behind MOE_FUSED_MAX_TOKENS); --ring N loads lib/libtgis_hip_ring<N>.so, a library built with another int4 weight
+crossover behind MOE_FUSED_MAX_TOKENS; the GPTQ lines also carry tiles_ms, the int4 tile path, alternating with fused_ms and
+loop_ms, and route_tiles_ms: profiles/mixtral_gptq_tiles_bench.jsonl is --gptq-only --layers 1 --skip-steps --moe-tokens
+64,128,256,512,1024,2048); --ring N loads lib/libtgis_hip_ring<N>.so, a library built with another int4 weight
 ring (TGIS_LIB_SUFFIX=_ring<N> tools/build.sh -DTGIS_MOE_GPTQ_RING=<N>), for the sweep of DESIGN.md section 6.
 
     python tools/bench_mixtral.py --quantize gptq [--skip-steps] [--moe-tokens 1,8,32] [--ring 16]"""
@@ -61,6 +63,25 @@ def weight_bytes(K, N, quantize, groupsize=128):
     return K * N // 2 + (K // groupsize) * N * 4 if quantize == "gptq" else K * N * 2
 
 
+def tile_paths(moe, x, logits, partial, iters, passes=3):
+    """GPTQ experts: the tile path (router GEMM, route_tiles, the two int4 tile GEMMs) next to the slab kernels and the loop,
+    the three ALTERNATING pass by pass in this process (each pass a median of timed_ms's rounds), and the route launches
+    alone.  *_ms: the median over the passes; *_ms_passes: every pass, the run-to-run spread a difference is read against."""
+    from tgis_amd import native
+
+    paths = {"tiles": lambda: moe.tiles(x, partial), "fused": lambda: moe.fused(x, moe.route(x), partial),
+             "loop": lambda: moe.loop(x, moe.route(x))}
+    seen = {name: [] for name in paths}
+    for _ in range(passes):
+        for name, fn in paths.items():
+            seen[name].append(timed_ms(fn, iters))
+    out = {"route_tiles_ms": timed_ms(lambda: native.moe_route_tiles(logits, moe.top_k), iters)}
+    for name, ms in seen.items():
+        out[name + "_ms"] = statistics.median(ms)
+        out[name + "_ms_passes"] = [round(v, 4) for v in ms]
+    return out
+
+
 def moe_alone(moe, T, dtype, device, seed):
     """One layer's routed block at T rows: each launch alone, the four together, and the loop path."""
     from tgis_amd import native
@@ -87,6 +108,8 @@ def moe_alone(moe, T, dtype, device, seed):
         "fused_ms": timed_ms(lambda: moe.fused(x, moe.route(x), partial), iters),
         "loop_ms": timed_ms(lambda: moe.loop(x, moe.route(x)), iters),
     }
+    if moe.quantize == "gptq":
+        res.update(tile_paths(moe, x, logits, partial, iters))
     expert_bytes = hit * 3 * weight_bytes(moe.hidden, moe.experts.down.K, moe.quantize)
     res["expert_weight_bytes_hit"] = expert_bytes
     res["fused_frac_of_hbm_peak"] = round(expert_bytes / HBM_PEAK * 1e3 / res["fused_ms"], 4)
@@ -129,6 +152,7 @@ def main():
     ap.add_argument("--moe-tokens", default=None, help="row counts of the routed block alone, e.g. 64,128,256")
     ap.add_argument("--ring", type=int, default=None, choices=(4, 8, 16),
                     help="load lib/libtgis_hip_ring<N>.so: the library built with an int4 weight ring of N k64-steps")
+    ap.add_argument("--gptq-only", action="store_true", help="with --quantize gptq: skip the f16 model's lines")
     args = ap.parse_args()
     if args.ring is not None:  # before tgis_amd.native is imported: it reads TGIS_HIP_LIB once
         lib = os.path.join(ROOT, "text-generation-inference_amd", "lib", f"libtgis_hip_ring{args.ring}.so")
@@ -150,6 +174,8 @@ def main():
     total_len = L_in + W + K + 10
     moe_rows = MOE_ROWS if args.moe_tokens is None else tuple(int(t) for t in args.moe_tokens.split(","))
     configs = [(name, None) for name in args.dtypes.split(",")] if args.quantize is None else [("f16", None), ("f16", "gptq")]
+    if args.gptq_only:
+        configs = [c for c in configs if c[1] == "gptq"]
     ring = None
     if args.quantize is not None:
         import ctypes
