@@ -204,8 +204,8 @@ int tgis_gptq8_prepare(const int32_t* qweight, const int32_t* qzeros, const void
  * the call; this launch does not touch it) followed by the fp32 split-K slabs (utils/gptq/quant_linear.py:130-192,259). */
 int64_t tgis_gptq8_gemm_workspace_bytes(int64_t M, int64_t K, int64_t N);
 
-/* out[M,N] f16 = x[M,K] f16 @ dequant(W) (+ bias), 1 <= M <= 64 (a larger M is an argument error: the caller dequantises
- * with tgis_gptq8_dequant_f16 and uses a library GEMM).  ldx / ldo: row strides in elements (ldx % 8 == 0, x 16-byte
+/* out[M,N] f16 = x[M,K] f16 @ dequant(W) (+ bias), 1 <= M <= 64 (a larger M is an argument error: it belongs to
+ * tgis_gptq8_tile_gemm_f16, or to tgis_gptq8_dequant_f16 and a library GEMM).  ldx / ldo: row strides in elements (ldx % 8 == 0, x 16-byte
  * aligned).  perm (int32 [K] or NULL) gathers x columns, -1 reads a zero.  act 0, or 1: x is [M, 2K] and the operand is
  * silu(x[:, :K]) * x[:, K:].  Deterministic: k-parts and split-K slabs are summed in fixed order.  No allocation, no
  * synchronisation.  Replaces QuantLinear.forward, utils/gptq/quant_linear.py:130-192,259. */
@@ -217,6 +217,20 @@ int tgis_gptq8_gemm_f16(const void* x, int64_t ldx, const void* prepared, const 
  * ((q - z - 1).float() * s.float()).half().  Replaces the dequantisation inside QuantLinear.forward,
  * utils/gptq/quant_linear.py:130-192,259. */
 int tgis_gptq8_dequant_f16(const void* prepared, void* w_out, int64_t K, int64_t N, int64_t groups, void* stream);
+
+/* The tile GEMM for forwards above 64 rows: out[M,N] f16 = x[M,K] f16 @ dequant(W) (+ bias) for any M >= 1, over the same
+ * image, with the dequantised weights of tgis_gptq8_dequant_f16 bit for bit and fp32 accumulation.  One launch: row tiles
+ * of 64 (M <= 128) or 128 rows x 128 (N >= 8192) or 64 columns per block, no k split across blocks, no workspace; the same
+ * input gives the same bytes.  ldx / ldo: row strides in elements (ldx % 8 == 0, x 16-byte aligned, ldo >= N).  perm (int32
+ * [K] or NULL) gathers x columns, -1 reads a zero.  The operand is x as it stands (SiLU * up is a launch of its own in
+ * front).  No allocation, no synchronisation.  Replaces QuantLinear.forward, utils/gptq/quant_linear.py:130-192,259. */
+int tgis_gptq8_tile_gemm_f16(const void* x, int64_t ldx, const void* prepared, const void* bias, const int32_t* perm,
+                             void* out, int64_t ldo, int64_t M, int64_t K, int64_t N, int64_t groups, void* stream);
+
+/* Host only: the largest M tgis_gptq8_tile_gemm_f16 should be given for this matrix (act_order: the call passes a perm);
+ * above it, tgis_gptq8_dequant_f16 + a library GEMM is the faster path.  A multiple of 64; 64 = never.  Measured
+ * (DESIGN.md section 6).  Call site: QuantLinear.forward, utils/gptq/quant_linear.py:259. */
+int64_t tgis_gptq8_tile_rows(int64_t K, int64_t N, int64_t groups, int act_order);
 
 /* ---- dense skinny GEMM (replaces F.linear / torch.mm at decode sizes, utils/layers.py:110-111,
  *      lm_head utils/layers.py:261) -------------------------------------------------------------- */

@@ -1,5 +1,6 @@
-// GPTQ 8-bit linear for gfx950: one-time repack ("prepare"), fused dequant + MFMA GEMM for decode-sized M (1..64) and a
-// full dequant kernel for the large-M (library GEMM) path.  Layout, arithmetic and kernel body: gptq8_gemm_body.h.
+// GPTQ 8-bit linear for gfx950: one-time repack ("prepare"), fused dequant + MFMA GEMM for decode-sized M (1..64), the tile
+// GEMM for forwards above that (gptq8_tiles.h) and a full dequant kernel for the library GEMM path beyond the rows the tile
+// GEMM is given (tgis_gptq8_tile_rows).  Layout, arithmetic and decode kernel body: gptq8_gemm_body.h.
 //
 // Replaces the Triton QuantLinear the reference gives 8-bit checkpoints (utils/gptq/quant_linear.py:130-192,259).
 #include <algorithm>
@@ -161,7 +162,7 @@ extern "C" int tgis_gptq8_gemm_f16(const void* x, int64_t ldx, const void* prepa
                                    void* out, int64_t ldo, int64_t M, int64_t K, int64_t N, int64_t groups, int act,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
     TGIS_CHECK_ARG(x && prepared && out, "tgis_gptq8_gemm_f16: null tensor");
-    TGIS_CHECK_ARG(M >= 1 && M <= 64, "tgis_gptq8_gemm_f16: serves 1 <= M <= 64 rows (M=%ld); above, dequantise + library GEMM",
+    TGIS_CHECK_ARG(M >= 1 && M <= 64, "tgis_gptq8_gemm_f16: serves 1 <= M <= 64 rows (M=%ld); above, tgis_gptq8_tile_gemm_f16",
                    (long)M);
     int rc = check_shape("tgis_gptq8_gemm_f16", K, N, groups);
     if (rc != TGIS_OK) return rc;
@@ -230,3 +231,5 @@ extern "C" int tgis_debug_gptq8_plan(int64_t M, int64_t K, int64_t N, int64_t gr
     info[6] = act_order != 0, info[7] = act;
     return TGIS_OK;
 }
+
+#include "gptq8_tiles.h"

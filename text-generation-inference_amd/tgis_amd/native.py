@@ -53,6 +53,8 @@ SIGNATURES = {
     "tgis_gptq8_gemm_f16": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
                                      _c_int, _vp, _c_i64, _vp]),
     "tgis_gptq8_dequant_f16": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp]),
+    "tgis_gptq8_tile_gemm_f16": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _vp]),
+    "tgis_gptq8_tile_rows": (_c_i64, [_c_i64, _c_i64, _c_i64, _c_int]),
     "tgis_dense_gemm_rope": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64, _c_i64,
                                       _c_i64, _c_i64, _c_i64, _c_int, _vp]),
     "tgis_dense_gemm_rope_kv8": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _c_i64,
@@ -567,7 +569,8 @@ def gptq_dequant(w: GptqWeight, out=None) -> torch.Tensor:
 
 
 # ---- GPTQ, 8 bits --------------------------------------------------------------------------------------
-GPTQ8_MAX_M = 64  # rows the fused 8-bit kernel serves (above: gptq8_dequant + a library GEMM)
+GPTQ8_MAX_M = 64  # rows the decode kernel serves (above: gptq8_tile_gemm up to Gptq8Weight.tile_rows(), then gptq8_dequant
+# + a library GEMM)
 
 
 class Gptq8Weight(_GptqImage):
@@ -581,6 +584,11 @@ class Gptq8Weight(_GptqImage):
 
     def workspace_bytes(self, M: int) -> int:
         return load_library().tgis_gptq8_gemm_workspace_bytes(M, self.K, self.N)
+
+    def tile_rows(self) -> int:
+        """Largest M gptq8_tile_gemm should be given (beyond: dequantise + library GEMM); 64 = never."""
+        return _asked_once(self, "tile_rows", lambda: load_library().tgis_gptq8_tile_rows(
+            self.K, self.N, self.groups, int(self.perm is not None)))
 
 
 def gptq8_gemm(x, w: Gptq8Weight, ws: Workspace, bias=None, act: int = 0, out=None):
@@ -596,6 +604,21 @@ def gptq8_gemm(x, w: Gptq8Weight, ws: Workspace, bias=None, act: int = 0, out=No
         load_library().tgis_gptq8_gemm_f16(_ptr(x), x.stride(0), _ptr(w.image), _ptr(bias), _ptr(w.perm), _ptr(out),
                                            out.stride(0), M, w.K, w.N, w.groups, act, ws.ptr, ws.nbytes, _stream()),
         "tgis_gptq8_gemm_f16")
+    return out
+
+
+def gptq8_tile_gemm(x, w: Gptq8Weight, bias=None, out=None):
+    """out[M, N] = x @ dequant(W) (+ bias) for any M in one launch of the tile kernel (csrc/gptq8_tiles.h): no dense copy of
+    W, no workspace; an act-order matrix gathers x by w.perm inside the launch."""
+    assert x.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1
+    M = x.shape[0]
+    assert x.shape[1] == w.in_features, (x.shape, w.in_features)
+    if out is None:
+        out = torch.empty((M, w.N), dtype=torch.float16, device=x.device)
+    _check(
+        load_library().tgis_gptq8_tile_gemm_f16(_ptr(x), x.stride(0), _ptr(w.image), _ptr(bias), _ptr(w.perm), _ptr(out),
+                                                out.stride(0), M, w.K, w.N, w.groups, _stream()),
+        "tgis_gptq8_tile_gemm_f16")
     return out
 
 

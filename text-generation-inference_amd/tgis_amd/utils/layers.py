@@ -299,9 +299,18 @@ class Ex4bitLinearV2(GptqLinear):
     __call__ = forward
 
 
+def gptq8_path_override():
+    """TGIS_GPTQ8_PATH = tiles | dequant forces one path on 8-bit forwards above 64 rows (tests, A/B runs); unset / auto: the
+    measured rule, Gptq8Weight.tile_rows()."""
+    v = os.getenv("TGIS_GPTQ8_PATH", "auto").lower()
+    if v not in ("auto", "tiles", "dequant"):
+        raise ValueError(f"TGIS_GPTQ8_PATH must be auto, tiles or dequant, got {v!r}")
+    return None if v == "auto" else v
+
+
 class Gptq8Linear(GptqLinear):
     """8-bit GPTQ linear: the QuantLinear the reference builds for bits = 8 (utils/layers.py:184-199,
-    utils/gptq/quant_linear.py:259).  The 8-bit kernel has none of the fused forms, so every capability of `Linear` keeps its
+    utils/gptq/quant_linear.py:259).  The 8-bit kernels have none of the fused forms, so every capability of `Linear` keeps its
     default: the models then run rotary + cache write as a launch of their own, down_proj(act=1), and get a reduced f16
     tensor where they ask for partial=True."""
     BITS = 8
@@ -326,6 +335,11 @@ class Gptq8Linear(GptqLinear):
             return native.gptq8_gemm(x, self.q_handle, workspace(x.device), bias=self.bias, act=act)
         if act:
             x = native.act_mul(x, self.q_handle.in_features)
+        # above the decode kernel's rows: the tile GEMM (no dense copy of W, the act-order gather inside the launch) up to
+        # the rows it was measured faster at, dequantise + library GEMM beyond
+        forced = gptq8_path_override()
+        if forced == "tiles" or (forced is None and x.shape[0] <= self.q_handle.tile_rows()):
+            return native.gptq8_tile_gemm(x, self.q_handle, bias=self.bias)
         return self.large_m(x)
 
     __call__ = forward

@@ -7,7 +7,14 @@ of 8 TB/s that (a) reaches on K N + groups N 4 bytes.  Then the step: a syntheti
 the synthetic InferenceEngine(gptq_bits=8), median of three blocks of --steps decode steps, wall clock around a device
 synchronize.  One JSON line per measurement.
 
-    python tools/gptq8_bench.py [--reps 200] [--skip-step] > profiles/NAME.json"""
+--prefill: forwards above 64 rows.  Per projection, plain and act-order, and M in PREFILL_ROWS: tgis_gptq8_tile_gemm_f16
+against the path it replaces (the act-order index_select, tgis_gptq8_dequant_f16 into scratch, torch.matmul).  The two
+alternate --repeats times within the run; each turn is one event-bracketed window of back-to-back launches (about
+--window-ms long) after warm-up launches of that shape.  A line holds the minimum over the turns of either path, the largest
+(max - min) / min seen between the turns of either ("spread") and the largest |difference| of the two outputs.
+
+    python tools/gptq8_bench.py [--reps 200] [--skip-step] > profiles/NAME.json
+    python tools/gptq8_bench.py --prefill > profiles/gptq8_tiles_bench.jsonl"""
 import argparse
 import json
 import os
@@ -78,6 +85,70 @@ def projections(args, dev):
         torch.cuda.empty_cache()
 
 
+PREFILL_ROWS = (65, 128, 256, 512, 1024, 2048, 4096)
+
+
+def window_us(fn, reps):
+    """us per call of `reps` back-to-back launches between one pair of events."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / reps
+
+
+def prefill(args, dev):
+    from tgis_amd.utils import layers
+
+    for name, K, N in SHAPES:
+        for act_order in (False, True):
+            g = torch.Generator(device=dev).manual_seed(K + N)
+            G = K // GS
+            qw = torch.randint(-2**31, 2**31 - 1, (K // 4, N), generator=g, device=dev, dtype=torch.int32)
+            qz = torch.randint(-2**31, 2**31 - 1, (G, N // 4), generator=g, device=dev, dtype=torch.int32)
+            s = (torch.rand((G, N), generator=g, device=dev) * 1e-3 + 1e-3).half()
+            g_idx = None
+            if act_order:
+                g_idx = torch.empty(K, dtype=torch.int32, device=dev)
+                g_idx[torch.randperm(K, generator=g, device=dev)] = torch.arange(K, device=dev, dtype=torch.int32) // GS
+            w = native.Gptq8Weight(qw, qz, s, g_idx, 8, GS)
+            assert (w.perm is not None) == act_order
+            del qw, qz, s
+            scratch = layers._dequant_scratch(dev, K, N)
+            for M in PREFILL_ROWS:
+                x = (torch.randn((M, K), generator=g, device=dev) * 0.1).half()
+                o = torch.empty((M, N), dtype=torch.float16, device=dev)
+
+                def tiles():
+                    return native.gptq8_tile_gemm(x, w, out=o)
+
+                def today():
+                    xx = layers._gather_columns(x, w) if act_order else x
+                    return torch.matmul(xx, native.gptq8_dequant(w, out=scratch))
+
+                paths = {"tiles": tiles, "today": today}
+                diff = float((tiles().float() - today().float()).abs().max())
+                reps, turns = {}, {"tiles": [], "today": []}
+                for k, fn in paths.items():
+                    for _ in range(args.warm):
+                        fn()
+                    reps[k] = max(5, min(500, int(args.window_ms * 1e3 / max(window_us(fn, 5), 1.0))))
+                for _ in range(args.repeats):
+                    for k, fn in paths.items():
+                        turns[k].append(window_us(fn, reps[k]))
+                t, d = min(turns["tiles"]), min(turns["today"])
+                spread = max((max(v) - min(v)) / min(v) for v in turns.values())
+                print(json.dumps({"proj": name, "K": K, "N": N, "act_order": act_order, "M": M, "tiles_us": round(t, 1),
+                                  "today_us": round(d, 1), "tiles_over_today": round(t / d, 3), "spread": round(spread, 3),
+                                  "tiles_turns_us": [round(v, 1) for v in turns["tiles"]],
+                                  "today_turns_us": [round(v, 1) for v in turns["today"]],
+                                  "tiles_tflops": round(2.0 * M * K * N / t * 1e-6, 1), "max_abs_diff": diff}), flush=True)
+            del w
+            torch.cuda.empty_cache()
+
+
 def step(args, dev):
     kw, quantize, dtype_s, B, ctx = bench.CONFIGS["llama2-7b-gptq"]
     cfg = LlamaConfig(**kw)
@@ -118,10 +189,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--skip-step", action="store_true")
     ap.add_argument("--skip-projections", action="store_true")
+    ap.add_argument("--prefill", action="store_true", help="the tile GEMM against dequantise + library GEMM above 64 rows")
+    ap.add_argument("--repeats", type=int, default=3, help="--prefill: alternating turns per path")
+    ap.add_argument("--window-ms", type=float, default=40.0, help="--prefill: length of a timed window")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     native.load_library()
+    if args.prefill:
+        return prefill(args, dev)
     if not args.skip_projections:
         projections(args, dev)
     if not args.skip_step:
